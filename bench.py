@@ -13,7 +13,8 @@ t = max over ranks of the barrier-bracketed wall time of the K steps.  Weak scal
 owns its own batch of 32 candidates (different gate perturbations); the evaluation needs no
 collective — the only exchange is the final winner selection, outside the timed region.
 
-The JSON line also carries:
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, ms_per_step, ...).  --dump-outputs DIR
+also writes the last timed step's objective and gradient there (dump_outputs).  With --full the JSON line also carries:
   roofline      the dominant kernel of the timed region.  Batches the chip holds at once are evaluated by ONE launch (k_eval_cluster,
                 csrc/frx_eval_kernel.hpp): SURVEY.md §8d's bytes of a full objective evaluation fused on device / its average duration; the
                 penalty integrator alone (the kernel §8d prices per piece) is roofline.penalty_integrator.  Other batches: three stage
@@ -37,6 +38,23 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 FP64_PEAK_TFLOPS = 78.6  # FP64 vector peak = half the 157.3 TF FP32 vector peak of the same guide
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, suffix, f, g, x_off, limit):
+    """--dump-outputs: what a caller of the timed path receives from its last step - `objective` (one value per candidate) and `gradient` (the
+    candidates' gradients back to back, x_off delimits them), float64 - as out_dir/<name><suffix>.npy.  Outputs above `limit` bytes are written as
+    a fixed, seeded sample of whole candidates, in index order; their indices are then in `candidates`."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"objective": f, "gradient": g}
+    if f.nbytes + g.nbytes > limit:
+        perm = np.random.default_rng(0).permutation(len(f))
+        nbytes = np.cumsum(8 * (2 + np.diff(x_off)[perm]))                 # objective, index and gradient of each candidate in sample order
+        idx = np.sort(perm[:int(np.searchsorted(nbytes, limit - 4096, side="right"))])   # (4 KB: the three .npy headers)
+        arrays = {"objective": f[idx], "gradient": np.concatenate([g[x_off[b]:x_off[b + 1]] for b in idx]), "candidates": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def cpu_baseline(cands, params, kappa, x_state, x_off, budget_s=12.0):
@@ -181,7 +199,14 @@ def main():
                     help="N > 1 front end (DESIGN.md 5): 'ranks' = one process per GPU over torch.distributed/RCCL (self-launched when no launcher did it); "
                          "'lib' = ONE process driving frx_multi_* (one host thread + handle per device, ncclCommInitAll inside the library)")
     ap.add_argument("--launch-check", action="store_true", help="start the ranks, meet at a barrier, print the job's shape and leave (no GPU work: the CPU test of the self-launch path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also measure everything else the line can carry: back-to-back and direct-launch forms of the timed steps, stage kernels, "
+                         "rooflines, the large batch, k_lbfgs_pre, the plans and the winner exchange, the CPU baseline, boundary calls (--no-plan, --no-cpu-baseline and "
+                         "--large-batch trim this run); without it the run sets up, warms up, times the K steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (objective, gradient: float64) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch                                   # (before libfrx touches the HIP runtime: torch brings its own copy, and the first one loaded wins)
     n_dev_torch = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -331,10 +356,18 @@ def main():
     sync_all()
     dt_wall = time.perf_counter() - t0
     dt = max(a.elapsed_time(b) for a, b in ev) * 1e-3
+    if args.dump_outputs:
+        if lib_mode:
+            shards = [(prob, f_dev, g_dev)] + [(pr, fd, gd) for pr, _xd, fd, gd, _st in lib_shards]
+            x_off = np.concatenate([[0]] + [s[0].x_off[1:] + sum(p.NX for p, _f, _g in shards[:i]) for i, s in enumerate(shards)])
+            f_out = np.concatenate([f.cpu().numpy() for _p, f, _g in shards]); g_out = np.concatenate([g.cpu().numpy() for _p, _f, g in shards])
+        else:
+            x_off, f_out, g_out = np.asarray(prob.x_off), f_dev.cpu().numpy(), g_dev.cpu().numpy()
+        dump_outputs(args.dump_outputs, "" if rank == 0 else f"_rank{rank}", f_out, g_out, x_off, DUMP_LIMIT_BYTES // (1 if lib_mode else world))
     # (diagnostic) the same graph replayed back to back: the timed replay above starts on an EMPTY queue, so its interval carries one graph submission (10-20 us, i.e.
     # 0.5-1 us per step at K = 20: the first replay of every burst measures 19.9-20.6 us per step, the following ones 19.5, scripts/r05/graph_ramp_probe.py)
     dt_b2b = None
-    if graph is not None:
+    if graph is not None and args.full:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
         with torch.cuda.stream(bench_stream):
             graph.replay(); evs[0].record(bench_stream)
@@ -342,13 +375,15 @@ def main():
         bench_stream.synchronize()
         dt_b2b = min(evs[i].elapsed_time(evs[i + 1]) for i in range(4)) * 1e-3
     # the same K steps as direct launches (untimed by the contract; reported next to the graph figure)
-    e_d0, e_d1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e_d0.record(bench_stream)
-    for _ in range(args.steps):
-        step()
-    e_d1.record(bench_stream)
-    sync_all(); bench_stream.synchronize()
-    dt_direct = e_d0.elapsed_time(e_d1) * 1e-3
+    dt_direct = 0.0
+    if args.full:
+        e_d0, e_d1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e_d0.record(bench_stream)
+        for _ in range(args.steps):
+            step()
+        e_d1.record(bench_stream)
+        sync_all(); bench_stream.synchronize()
+        dt_direct = e_d0.elapsed_time(e_d1) * 1e-3
     if dist:
         t = torch.tensor([dt, dt_wall, dt_direct], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -360,7 +395,7 @@ def main():
     # gone: ranks 1 .. N-1 used to sit in a collective - a spinning host thread each, under the boxes' quota of 16 CPUs - while
     # rank 0 ran those legs.
     r = None
-    if not args.no_plan:
+    if args.full and not args.no_plan:
         if dist: dist.barrier()
         # setup-equivalent host work (SE3GCOPTER::setup incl. H->V enumeration, CPU.hpp:1076-1186, and the first half of optimize:
         # setInitial/backwardT/backwardP, CPU.hpp:1237-1240), timed on a second handle built from the H-polytopes alone
@@ -422,17 +457,39 @@ def main():
         prob.close()
         return
 
+    fused_G = prob.eval_fused()                                        # the form the timed steps took (queries, no GPU work)
+    solo_wgs = prob.eval_solo()
+    head = {
+        "metric": "constraint-samples/s", "value": world * samples_per_step * args.steps / dt, "unit": "samples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "ms_per_step_host_wall": dt_wall / args.steps * 1e3, "value_host_wall": world * samples_per_step * args.steps / dt_wall,
+        "timing": "HIP events on the launch stream around the K steps (first launch -> last kernel end), inside the barrier + synchronize bracket whose host wall clock is ms_per_step_host_wall; max over ranks",
+        "launch": ((f"ONE hipGraph of the K steps ({'K kernel nodes: one k_eval_cluster launch per step' if fused_G else 'K kernel nodes: one k_eval_solo launch per step' if solo_wgs else '3 K kernel nodes'}, captured from K calls of frx_objective_eval_device)") if graph is not None
+                   else (graph_note or ("K direct launches of k_eval_cluster" if fused_G else "K direct launches of k_eval_solo" if solo_wgs else "K x 3 direct kernel launches"))),
+        "warmup_graph_replays": GRAPH_WARM_REPLAYS if graph is not None else 0,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"{args.config}: {B} candidate trajs/GPU x {N} pieces x {kappa} quadrature intervals "
+                               f"({samples_per_step} constraint samples/step/GPU), 16-gate Zhangjiajie-like corridor, K_i=8",
+                   "step": "one batched objective evaluation x->(f,grad), inputs resident in HBM: " + ("forward map + penalty integral + adjoint in ONE launch (k_eval_cluster)" if fused_G else "forward map + penalty integral + adjoint in ONE launch (k_eval_solo: one workgroup per candidate)" if solo_wgs else "k_forward + k_penalty + k_backward"),
+                   "state": "iterate after 60 L-BFGS iterations from the reference initial guess",
+                   "parallelism": f"candidates sharded {B}/GPU, no data-path collective",
+                   "front_end": ("frx_multi_* in one process" if lib_mode else "one process per GPU (torch.distributed)") if world > 1 else "one process, one device"},
+    }
+    if not args.full:
+        print(json.dumps(head), flush=True)
+        prob.close()
+        for sh in lib_shards: sh[0].close()
+        return
+
     # the three stage kernels one at a time (HIP events on the library's launch stream, frx_eval_stage_times): the roofline object is
     # reported for the penalty integrator (the kernel SURVEY.md 8d prices); the two knot kernels get sub-objects with their implementation traffic
     stage_us = prob.stage_times(x_state, reps=max(args.steps, 100))
     # ... and the evaluation in the form the timed steps took: ONE launch of clusters (frx::k_eval_cluster, csrc/frx_eval_kernel.hpp) when the batch fits the chip at
     # once - then THAT kernel is the dominant (the only) kernel of the timed region and the roofline object is reported for it, against SURVEY.md 8d's bytes of a
     # "full objective evaluation fused on device"; the penalty integrator alone (the stage kernel) moves to roofline.penalty_integrator.
-    fused_G = prob.eval_fused()
     one_us = min(prob.eval_launch_time(x_state, reps=max(args.steps, 100)) for _ in range(3)) if fused_G else None   # (best of three brackets: a bracket of direct launches also holds the launch path's gaps)
     # batches beyond the clusters' reach in the window where it wins (a GPU's share of the Monte-Carlo config): the SOLO launch - one workgroup per candidate runs the three
     # stage bodies back to back (csrc/frx_solo_kernel.hpp; bit-identical results); timed here in both forms
-    solo_wgs = prob.eval_solo()
     solo_us = min(prob.eval_launch_time(x_state, reps=max(args.steps, 100)) for _ in range(3)) if solo_wgs else None
     one1_us = one_us if fused_G else solo_us                           # the ONE kernel of a timed step, where the step is one launch
     prob.set_eval_fused(False)
@@ -744,28 +801,15 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "constraint-samples/s", "value": world * samples_per_step * args.steps / dt, "unit": "samples/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "ms_per_step_host_wall": dt_wall / args.steps * 1e3, "value_host_wall": world * samples_per_step * args.steps / dt_wall,
-            "timing": "HIP events on the launch stream around the K steps (first launch -> last kernel end), inside the barrier + synchronize bracket whose host wall clock is ms_per_step_host_wall; max over ranks",
-            "launch": ((f"ONE hipGraph of the K steps ({'K kernel nodes: one k_eval_cluster launch per step' if fused_G else 'K kernel nodes: one k_eval_solo launch per step' if solo_wgs else '3 K kernel nodes'}, captured from K calls of frx_objective_eval_device)") if graph is not None
-                       else (graph_note or ("K direct launches of k_eval_cluster" if fused_G else "K direct launches of k_eval_solo" if solo_wgs else "K x 3 direct kernel launches"))),
+            **head,
             "evaluation_form": ({"kernel": "frx::k_eval_cluster", "workgroups_per_candidate": fused_G, "what": "one launch per evaluation: a cluster of workgroups per candidate (leader: forward map and adjoint; members: penalty integral), csrc/frx_eval_kernel.hpp",
                                  "us_per_evaluation_back_to_back_launches": one_us, "us_per_evaluation_as_three_stage_launches": three_us}
                                 if fused_G else
                                 {"kernel": "frx::k_eval_solo", "workgroups_per_cu": solo_wgs, "what": "one launch per evaluation: ONE workgroup per candidate runs forward map, penalty integral of its own pieces and adjoint back to back (the stage kernels' bodies; bit-identical results), csrc/frx_solo_kernel.hpp",
                                  "us_per_evaluation_back_to_back_launches": solo_us, "us_per_evaluation_as_three_stage_launches": three_us}
                                 if solo_wgs else {"kernel": "three stage kernels", "us_per_evaluation_back_to_back_launches": three_us}),
-            "warmup_graph_replays": GRAPH_WARM_REPLAYS if graph is not None else 0,
             "ms_per_step_graph_replayed_back_to_back": (dt_b2b / args.steps * 1e3) if dt_b2b else None,
             "ms_per_step_direct_launches": dt_direct / args.steps * 1e3, "value_direct_launches": world * samples_per_step * args.steps / dt_direct,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{args.config}: {B} candidate trajs/GPU x {N} pieces x {kappa} quadrature intervals "
-                                   f"({samples_per_step} constraint samples/step/GPU), 16-gate Zhangjiajie-like corridor, K_i=8",
-                       "step": "one batched objective evaluation x->(f,grad), inputs resident in HBM: " + ("forward map + penalty integral + adjoint in ONE launch (k_eval_cluster)" if fused_G else "forward map + penalty integral + adjoint in ONE launch (k_eval_solo: one workgroup per candidate)" if solo_wgs else "k_forward + k_penalty + k_backward"),
-                       "state": "iterate after 60 L-BFGS iterations from the reference initial guess",
-                       "parallelism": f"candidates sharded {B}/GPU, no data-path collective",
-                       "front_end": ("frx_multi_* in one process" if lib_mode else "one process per GPU (torch.distributed)") if world > 1 else "one process, one device"},
             "roofline": {**({"bound": "hbm", "kernel": "frx::k_eval_cluster" if fused_G else "frx::k_eval_solo", "selected_by": "the dominant (only) kernel of the timed region: one launch per evaluation",
                              "achieved": eval_bytes / (one1_us * 1e-6) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": eval_bytes / (one1_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
                              "algorithmic_bytes_per_launch": eval_bytes, "algorithmic_bytes_definition": "SURVEY.md 8d, full objective evaluation fused on device: penalty bytes (sum over pieces of 312 + 48 K_i) + 16 n + 24 sum(nv) per candidate",

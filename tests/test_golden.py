@@ -10,7 +10,7 @@ import pytest
 from conftest import ROOT
 
 sys_path = os.path.join(ROOT, "tests", "golden")
-FILES = sorted(f for f in glob.glob(os.path.join(sys_path, "*.npz")) if not os.path.basename(f).startswith(("corridor_", "refvs_", "mc512_")))   # corridor fixtures: test_next_rows.py; Monte-Carlo verdicts: test_gpu_configs.py + the CPU sample below
+FILES = sorted(f for f in glob.glob(os.path.join(sys_path, "*.npz")) if not os.path.basename(f).startswith(("corridor_", "refvs_", "mc512_", "refpin_")))   # corridor fixtures: test_next_rows.py; reference outputs: test_reference_pin.py; Monte-Carlo verdicts: test_gpu_configs.py + the CPU sample below
 
 
 def load_case(path, sc):

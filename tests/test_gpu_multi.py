@@ -102,7 +102,7 @@ def test_bench_eight_ranks_control_flow_on_one_device():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"FRX_BENCH_DEVICE": "0", "FRX_BENCH_BACKEND": "gloo"})
-    args = ["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--large-batch", "0"]
+    args = ["--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--large-batch", "0"]
     p8 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8"] + args, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p8.returncode == 0, p8.stderr[-3000:]
     d8 = json.loads([l for l in p8.stdout.splitlines() if l.startswith("{")][-1])
