@@ -66,6 +66,7 @@ ABI_SYMBOLS = [
     "frx_problem_set_resident", "frx_optimize_path", "frx_penalty_problem_create", "frx_eval_status",
     "frx_dilate_batch", "frx_multi_create", "frx_multi_destroy", "frx_multi_info", "frx_multi_layout", "frx_multi_initial_guess", "frx_multi_optimize", "frx_multi_last_exchange",
     "frx_map_mark_cloud", "frx_map_is_blocked", "frx_grid_search", "frx_jps_plan", "frx_route_plan",
+    "frx_trajectory_check", "frx_trajectory_check_device",
 ]
 # diagnostics, include/frx_debug.h: not part of the drop-in boundary
 DEBUG_SYMBOLS = [
@@ -73,6 +74,11 @@ DEBUG_SYMBOLS = [
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
     "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
 ]
+
+# frx_trajectory_check (include/frx.h): fields of a row and flag bits
+CHECK_FIELDS = ("corridor", "speed", "thrust_min", "thrust_max", "body_rate", "acc", "worst_t", "worst_k")
+CHECK_MAX_INTERVALS = 16384
+CHECK_FLAG_CORRIDOR, CHECK_FLAG_SPEED, CHECK_FLAG_THRUST_MIN, CHECK_FLAG_THRUST_MAX, CHECK_FLAG_BODY_RATE, CHECK_FLAG_NONFINITE = 1, 2, 4, 8, 16, 32
 
 _lib = None
 
@@ -143,6 +149,8 @@ def lib():
         L.frx_penalty_eval.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
         L.frx_penalty_eval_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_forward.argtypes = [C.c_void_p, _dp, _dp, _dp]
+        L.frx_trajectory_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_check_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.frx_optimize.argtypes = [C.c_void_p, C.POINTER(LbfgsParams), _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
         L.frx_optimize_stats.argtypes = [C.c_void_p, _dp]
         L.frx_lbfgs_minimize_batch.argtypes = [C.c_int, _ip, _dp, _dp, _ip, _ip, _ip, C.POINTER(LbfgsParams), BATCH_EVAL_FN,
@@ -553,6 +561,22 @@ class Problem:
 
     def penalty_device(self, T_ptr: int, C_ptr: int, out_ptr: int, stream: int = 0):
         _check(lib().frx_penalty_eval_device(self.h, T_ptr, C_ptr, out_ptr, stream))
+
+    def trajectory_check(self, T, Cf, intervals: int = 256):
+        """Dense feasibility certificate of the batch (T, C) against the handle's corridors and limits (frx_trajectory_check):
+        dict(piece (P, 8), candidate (B, 8), flags (B,) uint32) plus the candidate rows' fields by name (CHECK_FIELDS)."""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1); Cf = np.ascontiguousarray(Cf, dtype=np.float64).reshape(-1)
+        if T.size != self.P or Cf.size != 18 * self.P:
+            raise ValueError(f"trajectory_check: expected {self.P} durations and {18 * self.P} coefficients, got {T.size} and {Cf.size}")
+        piece = np.zeros((self.P, 8)); cand = np.zeros((self.B, 8)); flags = np.zeros(self.B, np.uint32)
+        _check(lib().frx_trajectory_check(self.h, T.ctypes.data, Cf.ctypes.data, int(intervals), piece.ctypes.data, cand.ctypes.data, flags.ctypes.data))
+        out = dict(piece=piece, candidate=cand, flags=flags)
+        out.update({name: cand[:, i] for i, name in enumerate(CHECK_FIELDS)})
+        return out
+
+    def trajectory_check_device(self, T_ptr: int, C_ptr: int, out_ptr: int, intervals: int = 256, stream: int = 0):
+        """frx_trajectory_check_device: the piece rows (P x 8 doubles at out_ptr) as one launch on `stream`, device pointers, no synchronisation."""
+        _check(lib().frx_trajectory_check_device(self.h, T_ptr, C_ptr, int(intervals), out_ptr, stream))
 
     def forward(self, x):
         T = np.zeros(self.P); Cf = np.zeros(self.P * 18)

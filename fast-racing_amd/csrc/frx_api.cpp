@@ -227,6 +227,7 @@ struct frx_problem {
     DevBuf<double> d_wq;                                    // [P][4]: per waypoint {|xi|^2, sum_a V_a xi_a^2}, forward map -> adjoint of the same evaluation
     // pinned staging
     PinBuf<double> h_x, h_f, h_g, h_T, h_C, h_out20;
+    DevBuf<double> d_check;                                 // [P][8] rows of frx_trajectory_check, allocated on its first call
     // device-vector L-BFGS state (allocated on first use)
     DevBuf<double> d_xp, d_gp, d_dir, d_S, d_Y, d_ys, d_gt;
     PinBuf<frx::DvCommand> h_cmd;
@@ -979,6 +980,68 @@ int frx_penalty_eval(frx_problem *p, const double *T, const double *C, double *c
             for (int v = 0; v < 18; v++) gdC[18 * (size_t)gp + v] += o[2 + v];
         }
         cost[b] += s;
+    }
+    return FRX_OK;
+}
+
+int frx_trajectory_check_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, double *piece_out_dev, void *hip_stream) {
+    if (!p || !T_dev || !C_dev || !piece_out_dev) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
+    int lpp = 0, ppw = 0;
+    if (!frx::check_geometry(intervals, p->Kmax, &lpp, &ppw)) return fail(FRX_ERR_CAPACITY, "frx_trajectory_check: a corridor block of " + std::to_string(p->Kmax) + " half-spaces exceeds a wave's LDS");
+    HIP_TRY((hipError_t)frx::launch_check(p->dp, p->Kmax, T_dev, C_dev, intervals, piece_out_dev, hip_stream));
+    return FRX_OK;
+}
+
+int frx_trajectory_check(frx_problem *p, const double *T, const double *C, int intervals, double *piece_out, double *cand_out, unsigned *flags) {
+    if (!p || !T || !C || !cand_out) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
+    HIP_TRY(hipSetDevice(p->device));
+    if (!p->d_check.p) HIP_TRY(p->d_check.alloc((size_t)p->P * FRX_CHECK_FIELDS));
+    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
+    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
+    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+    const int rc = frx_trajectory_check_device(p, p->d_T.p, p->d_C.p, intervals, p->d_check.p, p->stream);
+    if (rc != FRX_OK) return rc;
+    double *rows = p->h_out20.p;                                            // (P x 20 doubles of staging: the P x 8 rows fit)
+    HIP_TRY(hipMemcpyAsync(rows, p->d_check.p, sizeof(double) * FRX_CHECK_FIELDS * (size_t)p->P, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (piece_out) std::memcpy(piece_out, rows, sizeof(double) * FRX_CHECK_FIELDS * (size_t)p->P);
+    // per candidate, in piece order: max (min for THRUST_MIN), NaN propagating; the worst reach keeps the first piece that attains it
+    auto nmax = [](double a, double b) { return (a > b || a != a) ? a : b; };
+    auto nmin = [](double a, double b) { return (a < b || a != a) ? a : b; };
+    for (int b = 0; b < p->B; b++) {
+        double *o = cand_out + (size_t)FRX_CHECK_FIELDS * b;
+        double t0 = 0.0;
+        for (int gp = p->poff[b]; gp < p->poff[b + 1]; gp++) {
+            const double *r = rows + (size_t)FRX_CHECK_FIELDS * gp;
+            if (gp == p->poff[b]) {
+                for (int f = 0; f < 6; f++) o[f] = r[f];
+                o[FRX_CHECK_WORST_T] = r[FRX_CHECK_WORST_T]; o[FRX_CHECK_WORST_K] = 0.0;
+            } else {
+                const double a = o[FRX_CHECK_CORRIDOR], c = r[FRX_CHECK_CORRIDOR];
+                if ((c > a && a == a) || (c != c && a == a)) { o[FRX_CHECK_WORST_T] = t0 + r[FRX_CHECK_WORST_T]; o[FRX_CHECK_WORST_K] = (double)(gp - p->poff[b]); }
+                o[FRX_CHECK_CORRIDOR] = nmax(a, c);
+                o[FRX_CHECK_SPEED] = nmax(o[FRX_CHECK_SPEED], r[FRX_CHECK_SPEED]);
+                o[FRX_CHECK_THRUST_MIN] = nmin(o[FRX_CHECK_THRUST_MIN], r[FRX_CHECK_THRUST_MIN]);
+                o[FRX_CHECK_THRUST_MAX] = nmax(o[FRX_CHECK_THRUST_MAX], r[FRX_CHECK_THRUST_MAX]);
+                o[FRX_CHECK_BODY_RATE] = nmax(o[FRX_CHECK_BODY_RATE], r[FRX_CHECK_BODY_RATE]);
+                o[FRX_CHECK_ACC] = nmax(o[FRX_CHECK_ACC], r[FRX_CHECK_ACC]);
+            }
+            t0 += T[gp];
+        }
+        if (flags) {
+            unsigned fl = 0u;
+            if (o[FRX_CHECK_CORRIDOR] > 0.0) fl |= FRX_CHECK_FLAG_CORRIDOR;
+            if (o[FRX_CHECK_SPEED] > p->cfg.vel_max) fl |= FRX_CHECK_FLAG_SPEED;
+            if (o[FRX_CHECK_THRUST_MIN] < p->cfg.thr_acc_min) fl |= FRX_CHECK_FLAG_THRUST_MIN;
+            if (o[FRX_CHECK_THRUST_MAX] > p->cfg.thr_acc_max) fl |= FRX_CHECK_FLAG_THRUST_MAX;
+            if (o[FRX_CHECK_BODY_RATE] > p->cfg.body_rate_max) fl |= FRX_CHECK_FLAG_BODY_RATE;
+            for (int f = 0; f < FRX_CHECK_FIELDS; f++)
+                if (!std::isfinite(o[f])) fl |= FRX_CHECK_FLAG_NONFINITE;
+            flags[b] = fl;
+        }
     }
     return FRX_OK;
 }

@@ -89,6 +89,12 @@ int launch_eval_solo(const DevProblem &dp, const LaunchGeom &g, const double *x,
                      const double *tap_d = nullptr, const int *tap_flags = nullptr, void *tap_res = nullptr,
                      unsigned *tap_arrive = nullptr, volatile unsigned *tap_flag = nullptr, unsigned tap_round = 0);
 
+// ---- dense feasibility check of a batch of trajectories (frx_check_kernel.hpp) ----
+// lanes per piece (a power of two) and pieces per wave for `intervals` + 1 samples per piece; 0 when a corridor block of Kmax half-spaces does not fit a wave's LDS
+int check_geometry(int intervals, int Kmax, int *lpp, int *ppw);
+// out: [P][8] (frx.h FRX_CHECK_*) of the pieces (T, C) against the handle's corridor blocks and limits; T / C / out are device pointers
+int launch_check(const DevProblem &dp, int Kmax, const double *T, const double *C, int intervals, double *out, void *stream);
+
 // ---- device-vector L-BFGS (frx_lbfgs_kernels.hpp) ----
 struct DvBuffers;
 struct DvLaunch {

@@ -213,6 +213,47 @@ int frx_wait(frx_problem *p);
  * T[n_pieces], C[n_pieces][6][3] as frx_optimize returns them; either output may be NULL. */
 int frx_traj_max_rates(int n_pieces, const double *T, const double *C, double *max_vel, double *max_acc);
 
+/* Dense feasibility certificate of a batch of results, on the device that holds the handle's corridors.  The reference judges a result by
+ * getMaxVelRate / getMaxAccRate alone (MinCoPlan_CPU.cpp:131-132; checkMaxVelRate / checkMaxAccRate, trajectory.hpp:275-315, are never
+ * called) and never checks the SE(3) constraints it optimises against; the penalty samples them at kappa + 1 nodes per piece only
+ * (CPU.hpp:188-408), so a trajectory can leave its corridor or break a limit between the nodes and still score zero.
+ * Every fine piece is sampled at s_j = j (T / M), j = 0..M, M = intervals (1..FRX_CHECK_MAX_INTERVALS; the penalty's abscissa form, so at
+ * M = kappa both sample the same points) with the reference's definitions (CPU.hpp:260-299, 322-328, 347-398): h = a + g e3,
+ * R = [xB yB zB](h), E = diag(ellipsoid).  Fields of a row (FRX_CHECK_FIELDS doubles):
+ *   FRX_CHECK_CORRIDOR    max over j and the piece's half-spaces k of n_k.(p - p_k) + |E R^T n_k|: how far the body reaches past a face,
+ *                         WITHOUT safeMargin (<= 0: inside)
+ *   FRX_CHECK_SPEED       max |v|        FRX_CHECK_THRUST_MIN  min |h|        FRX_CHECK_THRUST_MAX  max |h|
+ *   FRX_CHECK_BODY_RATE   max |omega_xy|, omega_xy = (xB.j, yB.j) / |h| (the quantity the body-rate penalty limits)
+ *   FRX_CHECK_ACC         max |a| (the sampled counterpart of getMaxAccRate)
+ *   FRX_CHECK_WORST_T     local time s_j of the worst CORRIDOR sample (lowest j on ties)
+ *   FRX_CHECK_WORST_K     index k of its half-space within the piece's polytope (lowest k on ties)
+ * A candidate's row reduces its pieces in piece order (max; min for THRUST_MIN); there WORST_T is the time from the candidate's start and
+ * WORST_K the local index of the piece.  A non-finite sample makes its field NaN (never hidden by a max).  Rows are bit-identical run to
+ * run and independent of the rest of the batch.  Flags per candidate, against the handle's own limits with no slack: FRX_CHECK_FLAG_*.
+ *   frx_trajectory_check        blocking: T[total fine pieces], C[total fine pieces x 18] on the host as frx_optimize returns them;
+ *                               piece_out (P x 8) and flags (B) may be NULL, cand_out (B x 8) may not.
+ *   frx_trajectory_check_device a pure launch on the caller's stream (no copy, no synchronisation): piece rows only, device pointers.
+ * Serves both kinds of handle (frx_problem_create[_from_h], frx_penalty_problem_create).  FRX_ERR_CAPACITY when a piece's corridor has
+ * too many half-spaces for the kernel's LDS (several hundred). */
+#define FRX_CHECK_MAX_INTERVALS 16384
+#define FRX_CHECK_FIELDS 8
+#define FRX_CHECK_CORRIDOR 0
+#define FRX_CHECK_SPEED 1
+#define FRX_CHECK_THRUST_MIN 2
+#define FRX_CHECK_THRUST_MAX 3
+#define FRX_CHECK_BODY_RATE 4
+#define FRX_CHECK_ACC 5
+#define FRX_CHECK_WORST_T 6
+#define FRX_CHECK_WORST_K 7
+#define FRX_CHECK_FLAG_CORRIDOR 1u      /* CORRIDOR > 0 */
+#define FRX_CHECK_FLAG_SPEED 2u         /* SPEED > vel_max */
+#define FRX_CHECK_FLAG_THRUST_MIN 4u    /* THRUST_MIN < thr_acc_min */
+#define FRX_CHECK_FLAG_THRUST_MAX 8u    /* THRUST_MAX > thr_acc_max */
+#define FRX_CHECK_FLAG_BODY_RATE 16u    /* BODY_RATE > body_rate_max */
+#define FRX_CHECK_FLAG_NONFINITE 32u    /* a non-finite value in the candidate's row */
+int frx_trajectory_check(frx_problem *p, const double *T, const double *C, int intervals, double *piece_out, double *cand_out, unsigned *flags);
+int frx_trajectory_check_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, double *piece_out_dev, void *hip_stream);
+
 /* Replaces ~cuda_computer / kill_kernel (cc.cu:44-49, 566-579; GPU.hpp:907-909). */
 void frx_problem_destroy(frx_problem *p);
 
