@@ -66,7 +66,7 @@ ABI_SYMBOLS = [
     "frx_problem_set_resident", "frx_optimize_path", "frx_penalty_problem_create", "frx_eval_status",
     "frx_dilate_batch", "frx_multi_create", "frx_multi_destroy", "frx_multi_info", "frx_multi_layout", "frx_multi_initial_guess", "frx_multi_optimize", "frx_multi_last_exchange",
     "frx_map_mark_cloud", "frx_map_is_blocked", "frx_grid_search", "frx_jps_plan", "frx_route_plan",
-    "frx_trajectory_check", "frx_trajectory_check_device",
+    "frx_trajectory_check", "frx_trajectory_check_device", "frx_trajectory_sample", "frx_trajectory_sample_device",
 ]
 # diagnostics, include/frx_debug.h: not part of the drop-in boundary
 DEBUG_SYMBOLS = [
@@ -79,6 +79,9 @@ DEBUG_SYMBOLS = [
 CHECK_FIELDS = ("corridor", "speed", "thrust_min", "thrust_max", "body_rate", "acc", "worst_t", "worst_k")
 CHECK_MAX_INTERVALS = 16384
 CHECK_FLAG_CORRIDOR, CHECK_FLAG_SPEED, CHECK_FLAG_THRUST_MIN, CHECK_FLAG_THRUST_MAX, CHECK_FLAG_BODY_RATE, CHECK_FLAG_NONFINITE = 1, 2, 4, 8, 16, 32
+# frx_trajectory_sample (include/frx.h): doubles of a row and the named parts of it (FRX_SAMPLE_*)
+SAMPLE_FIELDS = 20
+SAMPLE_VIEWS = dict(pos=slice(0, 3), vel=slice(3, 6), acc=slice(6, 9), jerk=slice(9, 12), thrust=12, quat=slice(13, 17), omega=slice(17, 20))
 
 _lib = None
 
@@ -151,6 +154,8 @@ def lib():
         L.frx_forward.argtypes = [C.c_void_p, _dp, _dp, _dp]
         L.frx_trajectory_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_trajectory_check_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_sample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_optimize.argtypes = [C.c_void_p, C.POINTER(LbfgsParams), _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
         L.frx_optimize_stats.argtypes = [C.c_void_p, _dp]
         L.frx_lbfgs_minimize_batch.argtypes = [C.c_int, _ip, _dp, _dp, _ip, _ip, _ip, C.POINTER(LbfgsParams), BATCH_EVAL_FN,
@@ -577,6 +582,32 @@ class Problem:
     def trajectory_check_device(self, T_ptr: int, C_ptr: int, out_ptr: int, intervals: int = 256, stream: int = 0):
         """frx_trajectory_check_device: the piece rows (P x 8 doubles at out_ptr) as one launch on `stream`, device pointers, no synchronisation."""
         _check(lib().frx_trajectory_check_device(self.h, T_ptr, C_ptr, int(intervals), out_ptr, stream))
+
+    def trajectory_sample(self, T, Cf, n_samples: int, dt: float = 0.0, t0: float = 0.0, times=None):
+        """Every candidate of the batch (T, C) at n_samples times with its SE(3) outputs (frx_trajectory_sample): times (B, n_samples) from each
+        candidate's start, else t0 + s dt (dt > 0) or n_samples points over each duration (dt == 0).  dict(rows (B, S, 20)) plus the named
+        views of the rows (SAMPLE_VIEWS: pos, vel, acc, jerk (B, S, 3), thrust (B, S), quat (B, S, 4) as w, x, y, z, omega (B, S, 3))."""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1); Cf = np.ascontiguousarray(Cf, dtype=np.float64).reshape(-1)
+        if T.size != self.P or Cf.size != 18 * self.P:
+            raise ValueError(f"trajectory_sample: expected {self.P} durations and {18 * self.P} coefficients, got {T.size} and {Cf.size}")
+        S = int(n_samples)
+        tp = None
+        if times is not None:
+            times = np.ascontiguousarray(times, dtype=np.float64)
+            if times.shape != (self.B, S):
+                raise ValueError(f"trajectory_sample: times must have shape ({self.B}, {S}), got {times.shape}")
+            tp = times.ctypes.data
+        rows = np.empty((self.B, max(S, 0), SAMPLE_FIELDS))
+        _check(lib().frx_trajectory_sample(self.h, T.ctypes.data, Cf.ctypes.data, S, float(t0), float(dt), tp, rows.ctypes.data))
+        out = dict(rows=rows)
+        out.update({name: rows[..., sl] for name, sl in SAMPLE_VIEWS.items()})
+        return out
+
+    def trajectory_sample_device(self, T_ptr: int, C_ptr: int, out_ptr: int, n_samples: int, dt: float = 0.0, t0: float = 0.0, times_ptr: int = 0,
+                                 stream: int = 0):
+        """frx_trajectory_sample_device: the rows (B x n_samples x 20 doubles at out_ptr, 16-byte aligned) as one launch on `stream`, device pointers
+        (times_ptr = 0: no times array), no copy, no synchronisation."""
+        _check(lib().frx_trajectory_sample_device(self.h, T_ptr, C_ptr, int(n_samples), float(t0), float(dt), times_ptr or None, out_ptr, stream))
 
     def forward(self, x):
         T = np.zeros(self.P); Cf = np.zeros(self.P * 18)

@@ -9,6 +9,7 @@
 #include <cfloat>
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -228,6 +229,7 @@ struct frx_problem {
     // pinned staging
     PinBuf<double> h_x, h_f, h_g, h_T, h_C, h_out20;
     DevBuf<double> d_check;                                 // [P][8] rows of frx_trajectory_check, allocated on its first call
+    DevBuf<double> d_sample;                                // frx_trajectory_sample: [B][S][20] rows, then [B][S] times; grown as needed
     // device-vector L-BFGS state (allocated on first use)
     DevBuf<double> d_xp, d_gp, d_dir, d_S, d_Y, d_ys, d_gt;
     PinBuf<frx::DvCommand> h_cmd;
@@ -1043,6 +1045,55 @@ int frx_trajectory_check(frx_problem *p, const double *T, const double *C, int i
             flags[b] = fl;
         }
     }
+    return FRX_OK;
+}
+
+// argument rules of both forms of frx_trajectory_sample; *n_out = B x S x FRX_SAMPLE_FIELDS
+static int sample_args(frx_problem *p, const double *T, const double *C, int n_samples, double t0, double dt, const double *times, const double *out,
+                       size_t *n_out) {
+    if (!p || !T || !C || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (n_samples < 1) return fail(FRX_ERR_INVALID_ARG, "n_samples must be >= 1");
+    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0) return fail(FRX_ERR_INVALID_ARG, "t0 and dt must be finite and dt >= 0");
+    if (!times && dt == 0.0 && n_samples < 2) return fail(FRX_ERR_INVALID_ARG, "n_samples must be >= 2 when dt == 0 (samples spread over each duration)");
+    size_t n = 0;
+    if (__builtin_mul_overflow((size_t)n_samples, (size_t)p->B, &n) || __builtin_mul_overflow(n, (size_t)FRX_SAMPLE_FIELDS, &n))
+        return fail(FRX_ERR_INVALID_ARG, "n_samples x B x FRX_SAMPLE_FIELDS overflows size_t");
+    if (!frx::sample_fits(p->maxN)) return fail(FRX_ERR_CAPACITY, "frx_trajectory_sample: the prefix sums of " + std::to_string(p->maxN) + " pieces exceed the kernel's LDS");
+    *n_out = n;
+    return FRX_OK;
+}
+
+int frx_trajectory_sample_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_samples, double t0, double dt, const double *times_dev,
+                                 double *out_dev, void *hip_stream) {
+    size_t n_out = 0;
+    const int rc = sample_args(p, T_dev, C_dev, n_samples, t0, dt, times_dev, out_dev, &n_out);
+    if (rc != FRX_OK) return rc;
+    if ((uintptr_t)out_dev % 16) return fail(FRX_ERR_INVALID_ARG, "out_dev must be 16-byte aligned");
+    HIP_TRY((hipError_t)frx::launch_sample(p->dp, p->maxN, T_dev, C_dev, n_samples, t0, dt, times_dev, out_dev, hip_stream));
+    return FRX_OK;
+}
+
+int frx_trajectory_sample(frx_problem *p, const double *T, const double *C, int n_samples, double t0, double dt, const double *times, double *out) {
+    size_t n_out = 0;
+    const int rc = sample_args(p, T, C, n_samples, t0, dt, times, out, &n_out);
+    if (rc != FRX_OK) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n_times = times ? n_out / FRX_SAMPLE_FIELDS : 0, need = n_out + n_times;   // (rows first: 16-byte aligned)
+    if (need > SIZE_MAX / sizeof(double)) return fail(FRX_ERR_ALLOC, "frx_trajectory_sample: output too large");
+    if (p->d_sample.n < need && p->d_sample.alloc(need) != hipSuccess) {
+        (void)hipGetLastError();                                            // (a failed allocation is no error of a later launch)
+        return fail(FRX_ERR_ALLOC, "frx_trajectory_sample: cannot allocate " + std::to_string(need * sizeof(double)) + " bytes on the device");
+    }
+    double *d_out = p->d_sample.p, *d_times = times ? p->d_sample.p + n_out : nullptr;
+    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
+    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
+    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+    if (times) HIP_TRY(hipMemcpyAsync(d_times, times, sizeof(double) * n_times, hipMemcpyHostToDevice, p->stream));
+    const int lrc = frx_trajectory_sample_device(p, p->d_T.p, p->d_C.p, n_samples, t0, dt, d_times, d_out, p->stream);
+    if (lrc != FRX_OK) return lrc;
+    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
     return FRX_OK;
 }
 

@@ -95,6 +95,14 @@ int check_geometry(int intervals, int Kmax, int *lpp, int *ppw);
 // out: [P][8] (frx.h FRX_CHECK_*) of the pieces (T, C) against the handle's corridor blocks and limits; T / C / out are device pointers
 int launch_check(const DevProblem &dp, int Kmax, const double *T, const double *C, int intervals, double *out, void *stream);
 
+// ---- batched sampling with SE(3) outputs (frx_sample_kernel.hpp) ----
+// 1 when candidates of up to maxN fine pieces fit the kernel's LDS
+int sample_fits(int maxN);
+// out: [B][S][20] (frx.h FRX_SAMPLE_*) at the times [B][S] (times != null), t0 + s dt (dt > 0) or s total_b / (S - 1) (dt == 0); out 16-byte aligned;
+// T / C / times / out are device pointers
+int launch_sample(const DevProblem &dp, int maxN, const double *T, const double *C, int S, double t0, double dt, const double *times, double *out,
+                  void *stream);
+
 // ---- device-vector L-BFGS (frx_lbfgs_kernels.hpp) ----
 struct DvBuffers;
 struct DvLaunch {

@@ -254,6 +254,45 @@ int frx_traj_max_rates(int n_pieces, const double *T, const double *C, double *m
 int frx_trajectory_check(frx_problem *p, const double *T, const double *C, int intervals, double *piece_out, double *cand_out, unsigned *flags);
 int frx_trajectory_check_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, double *piece_out_dev, void *hip_stream);
 
+/* Batched sampling of results with their SE(3) outputs, on the device.  The reference's traj_server evaluates one PolynomialTrajectory message at
+ * control rate (traj_server.cpp:397-456: position, velocity, acceleration, jerk) and its controller derives attitude and thrust from the
+ * acceleration; frx_msg_sample is that call for one time.  These entries sample every candidate of the handle's batch at S = n_samples times
+ * each and write the flat state together with the flatness map the penalty and the check constrain (CPU.hpp:260-299).
+ *   T, C        the batch's fine pieces as frx_optimize / frx_forward return them: T[P], C[P x 18], the handle's piece layout
+ *   times       times != NULL: t = times[b S + s] (t0 and dt are not used)
+ *               times == NULL, dt > 0: t_s = t0 + s dt;  dt == 0: t_s = s (total_b / (S - 1)), S >= 2 points over each candidate's duration
+ *               Every time is measured from the candidate's own start.
+ * Piece location: cum[0] = 0, cum[i + 1] = cum[i] + T[i] (left to right in piece order); t is clamped to [0, cum[N]]; the piece is the first i with
+ * t <= cum[i + 1] (traj_server's `t > dur` rule: a knot time stays in the earlier piece); the local time is t - cum[i].  Past the end the state
+ * of the end is held (traj_server extrapolates the last piece instead).  A NaN time gives a row of NaN.
+ * Row of FRX_SAMPLE_FIELDS doubles, out[b][s][FRX_SAMPLE_FIELDS] row-major:
+ *   FRX_SAMPLE_POS (3), FRX_SAMPLE_VEL (3), FRX_SAMPLE_ACC (3), FRX_SAMPLE_JERK (3)      p, v, a, j
+ *   FRX_SAMPLE_THRUST     |h|, h = a + g e3 (collective thrust per unit mass)
+ *   FRX_SAMPLE_QUAT (4)   (w, x, y, z) of R = [xB yB zB], zB = h / |h|, yB = normalise(0, zB.z, -zB.y), xB = yB x zB (the arithmetic of the check
+ *                         and the penalty): Hamilton convention, R(q) = R maps body to world; the branch is taken on the largest of
+ *                         (trace, R00, R11, R22), the earlier one on a tie, then the sign is chosen so that w >= 0
+ *   FRX_SAMPLE_OMEGA (3)  body rates in the body frame: omega_x = -(yB.j) / |h|, omega_y = (xB.j) / |h|,
+ *                         omega_z = -(xB.y dzB.z - xB.z dzB.y) / |(0, zB.z, -zB.y)| with dzB = (j - zB (zB.j)) / |h|;
+ *                         |omega_xy| is the quantity the body-rate penalty and FRX_CHECK_BODY_RATE limit
+ * There is no special case where h = 0 or zB.y = zB.z = 0: the arithmetic gives inf / NaN there, as in the penalty.  A non-finite T or C touches
+ * its own candidate's rows only; rows are bit-identical run to run, between the two forms and whatever else is in the batch.
+ *   frx_trajectory_sample         blocking, host pointers; keeps one device buffer per handle and grows it (FRX_ERR_ALLOC when it cannot).
+ *   frx_trajectory_sample_device  a pure launch on the caller's stream, device pointers: no copy, no synchronisation, no allocation (capturable in
+ *                                 a hipGraph); out_dev 16-byte aligned.
+ * FRX_ERR_INVALID_ARG: n_samples < 1 (< 2 with times == NULL and dt == 0), dt < 0, t0 or dt not finite, T, C or out NULL, S x B x 20 overflowing
+ * size_t.  Serves both kinds of handle (frx_problem_create[_from_h], frx_penalty_problem_create). */
+#define FRX_SAMPLE_FIELDS 20
+#define FRX_SAMPLE_POS 0
+#define FRX_SAMPLE_VEL 3
+#define FRX_SAMPLE_ACC 6
+#define FRX_SAMPLE_JERK 9
+#define FRX_SAMPLE_THRUST 12
+#define FRX_SAMPLE_QUAT 13
+#define FRX_SAMPLE_OMEGA 17
+int frx_trajectory_sample(frx_problem *p, const double *T, const double *C, int n_samples, double t0, double dt, const double *times, double *out);
+int frx_trajectory_sample_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_samples, double t0, double dt,
+                                 const double *times_dev, double *out_dev, void *hip_stream);
+
 /* Replaces ~cuda_computer / kill_kernel (cc.cu:44-49, 566-579; GPU.hpp:907-909). */
 void frx_problem_destroy(frx_problem *p);
 
