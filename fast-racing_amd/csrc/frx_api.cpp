@@ -267,7 +267,7 @@ struct frx_problem {
     std::vector<double> trace;                              // FRX_TRACE: per command of candidate 0 {flags, step, f, dg, dginit, xx, gg}
     // one launch per evaluation (frx_eval_kernel.hpp): granules and control words of its clusters, zeroed once; eval_fused: 1 = frx_objective_eval[_device] take it
     // (set at create when the geometry applies and the chip holds the whole batch at once; FRX_EVAL_FUSED=0 / frx_debug_set_eval_fused turn it off)
-    DevBuf<unsigned long long> d_ev_ll; unsigned *d_ev_words = nullptr;   // one allocation: [78 P] granule words, then the [64 B + 1] control words
+    DevBuf<unsigned long long> d_ev_ll; unsigned *d_ev_words = nullptr;   // one allocation: [40 P] granule words, then the [64 B + 1] control words
     int eval_fused = 0, eval_fused_G = 0, eval_fused_stamps = 0;
     unsigned long long eval_fused_ticks = 25000000ull;      // bound of every wait inside the launch, ticks of the 100 MHz counter: 250 ms (a healthy evaluation takes ~20 us; FRX_EVAL_TIMEOUT_MS)
     std::vector<unsigned char> ev_args, ev_args_up;         // the one-launch evaluation's constant arguments (frx::eval_cluster_args): as they should be / as the device copy holds them
@@ -559,7 +559,7 @@ int frx_problem_create(const frx_config *cfg, int device, int B, const int *coar
     CR(p->d_pcrw.alloc((size_t)(p->geo.pcr_steps * 8 + 4) * p->P)); p->geo.pcrw = p->d_pcrw.p;
     CR(p->d_wq.alloc((size_t)4 * p->P)); CR(hipMemset(p->d_wq.p, 0, sizeof(double) * 4 * p->P));
     if (p->eval_fused_G) {
-        const size_t n_ll = (size_t)78 * p->P, n_w64 = ((size_t)64 * B + 2) / 2;
+        const size_t n_ll = (size_t)40 * p->P, n_w64 = ((size_t)64 * B + 2) / 2;
         CR(p->d_ev_ll.alloc(n_ll + n_w64)); CR(hipMemset(p->d_ev_ll.p, 0, sizeof(unsigned long long) * (n_ll + n_w64)));   // (not on the handle's stream: the first evaluation may come on the caller's)
         p->d_ev_words = (unsigned *)(p->d_ev_ll.p + n_ll);
         { NumaScope numa_alloc(device); CR(p->h_ev_status.alloc(16)); }

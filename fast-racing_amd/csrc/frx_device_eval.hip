@@ -12,6 +12,12 @@
 namespace frx {
 
 static bool eval_argp() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_ARGPTR"); return !(e && e[0] == '0'); }(); return on; }   // FRX_EVAL_ARGPTR=0: the by-value form (A/B)
+static bool eval_early_t() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_EARLY_T"); return !(e && e[0] == '0'); }(); return on; }   // FRX_EVAL_EARLY_T=0: the staged-durations form (A/B)
+// the instantiation the launcher takes: argument pointer (or not) x early durations (or not)
+static const void *eval_fn() {
+    return eval_argp() ? (eval_early_t() ? (const void *)k_eval_cluster<true, true> : (const void *)k_eval_cluster<true, false>)
+                       : (eval_early_t() ? (const void *)k_eval_cluster<false, true> : (const void *)k_eval_cluster<false, false>);
+}
 
 // (see launch_set_limits, frx_device.hip: the dynamic-LDS limit of a kernel only grows, per device)
 int eval_cluster_raise_limit(size_t bytes) {
@@ -21,7 +27,7 @@ int eval_cluster_raise_limit(size_t bytes) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
     if (bytes <= held[dev]) return 0;
-    const hipError_t e = hipFuncSetAttribute(eval_argp() ? (const void *)k_eval_cluster<true> : (const void *)k_eval_cluster<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    const hipError_t e = hipFuncSetAttribute(eval_fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess) held[dev] = bytes;
     return (int)e;
 }
@@ -38,7 +44,7 @@ int eval_cluster_geometry(LaunchGeom &g) {
 }
 int eval_cluster_blocks_per_cu(size_t lds_bytes) {
     int n = 0;
-    const void *fn = eval_argp() ? (const void *)k_eval_cluster<true> : (const void *)k_eval_cluster<false>;
+    const void *fn = eval_fn();
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds_bytes) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return n;
 }
@@ -48,7 +54,7 @@ size_t eval_cluster_args_bytes() { return sizeof(EvalClusterArgs); }
 void eval_cluster_args(const DevProblem &dp, const LaunchGeom &g, double *T, double *C, unsigned long long *ll, unsigned *words, void *out) {
     EvalClusterArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.dp = dp; a.T = T; a.C = C; a.out20ll = ll; a.ctll = ll + (size_t)40 * dp.P; a.words = words; a.status = words + (size_t)64 * dp.B;
+    a.dp = dp; a.T = T; a.C = C; a.out20ll = ll; a.words = words; a.status = words + (size_t)64 * dp.B;
     a.G = g.ev_G; a.maxCN = g.maxCN; a.maxXb = g.maxXb; a.maxVb = g.maxVb; a.nsteps = g.pcr_steps; a.lpp = g.lpp; a.ppw = g.ppw; a.Kmax = g.Kmax; a.pen_lds = eval_pen_lds(g); a.maxN19 = g.maxN * 19;
     std::memcpy(out, &a, sizeof(a));
 }
@@ -61,8 +67,14 @@ int launch_eval_cluster(const LaunchGeom &g, int B, const void *args_host, const
     c.test_drop_members = timeout_ticks == 1ull ? 1 : 0;               // (test mode, frx_debug_set_eval_fused(p, 2): members that never arrive and a 50 us bound)
     if (c.test_drop_members) c.timeout_ticks = 5000ull;
     const dim3 grid(8 * g.ev_G * ((B + 7) / 8));
-    if (eval_argp() && args_dev) hipLaunchKernelGGL(k_eval_cluster<true>, grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
-    else hipLaunchKernelGGL(k_eval_cluster<false>, grid, dim3(256), g.lds_ev, (hipStream_t)stream, *(const EvalClusterArgs *)args_host, c);
+    const bool et = eval_early_t();
+    if (eval_argp() && args_dev) {
+        if (et) hipLaunchKernelGGL((k_eval_cluster<true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+        else hipLaunchKernelGGL((k_eval_cluster<true, false>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+    } else {
+        if (et) hipLaunchKernelGGL((k_eval_cluster<false, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, *(const EvalClusterArgs *)args_host, c);
+        else hipLaunchKernelGGL((k_eval_cluster<false, false>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, *(const EvalClusterArgs *)args_host, c);
+    }
     return (int)hipGetLastError();
 }
 } // namespace frx

@@ -6,14 +6,16 @@
 // (32 candidates x 64 pieces) each is one wave's dependent chain of 4.6-7.7 us of which 1.5-2.5 us are the launch itself - start of the grid,
 // the first trip to HBM for operands the previous kernel just had in LDS, the drain at the end (the same bodies inside the resident round kernel,
 // frx_round_kernel.hpp, take 5.2 / 3.1 / 5.2 us).  Here an evaluation is one grid of CLUSTERS, one per candidate:
-//   workgroup 0       LEADER: stages x and the polytopes once, runs the forward map, whose (C, T) leave as granules, then - while the members integrate - everything
-//                     of the adjoint that does not need the penalty partials, polls the partials, finishes the adjoint, writes f and the gradient
-//   workgroups 1..G-1 MEMBERS, every WAVE on its own: fetch the corridor blocks of its wave-task (ppw pieces), wait at the cluster's gate word, poll the task's
-//                     (C, T) granules, integrate the penalty, send the 20 partials per piece as granules and leave
-// BOTH directions travel as self-validating granules (rk_ll_put, frx_kernels.hpp): no drain, no flag behind the payload, no barrier on either side - the
-// round kernel's (C, T) hand-off (write-through stores, drain, barrier, phase word; poll, barrier, loads) measures 1.3 us + a load trip, this one a load trip.
-// Same integrand and sums as the stage kernels (f is bit-identical); the adjoint runs in the resident order of operations (backward_knot_wsp64), whose gradient
-// differs from the stage kernel's in the last bits (<= 1e-11 relative, tests/test_gpu_parity.py).
+//   every workgroup   runs the forward map on the same x (forward_knot_body, MODE 5: x and the polytopes staged into its own LDS, (C, T) kept there, nothing to global memory),
+//                     so (C, T) never travel between workgroups.  Early-duration form (ET, the default; FRX_EVAL_EARLY_T=0 takes the staged form): wave 0 - the matrix
+//                     wave - loads tau into registers as its first loads and forms the durations on its own, waves 1-3 stage xi and the polytopes; one early barrier
+//                     (counters zeroed, the status word broadcast) and the barrier in front of the coefficient collection are the only workgroup barriers of the forward map
+//   workgroup 0       LEADER: then everything of the adjoint that does not need the penalty partials, polls the partials, finishes the adjoint, writes f and the gradient
+//   workgroups 1..G-1 MEMBERS, every WAVE on its own behind the forward map: the corridor blocks of its wave-task (ppw pieces; loaded behind the forward map's own loads,
+//                     in flight under it), the penalty samples out of the workgroup's (C, T) copy, the 20 partials per piece out as self-validating granules
+//                     (rk_ll_put, frx_kernels.hpp: no drain, no flag behind the payload) and leave
+// Same integrand and sums as the stage kernels (f is bit-identical; both forms of the forward map too); the adjoint runs in the resident order of operations
+// (backward_knot_wsp64), whose gradient differs from the stage kernel's in the last bits (<= 1e-11 relative, tests/test_gpu_parity.py).
 //
 // Tags instead of zeroed buffers: the launch is captured in hipGraphs (bench.py replays one), so nothing on the host may run between two of them.  Every
 // cluster keeps the tag of its last COMPLETED evaluation in device memory (`done`); an evaluation uses tag = done + 1 for its flag and its granules, and the
@@ -34,7 +36,6 @@ struct EvalClusterArgs {                      // constant for the life of a hand
     DevProblem dp;
     double *T, *C;
     ll_u64 *out20ll;                         // [P][20] granules: the penalty partials, members -> leader (its own buffer: the round kernel's carries tags of its own)
-    ll_u64 *ctll;                            // [P][19] granules: coefficients and duration of every piece, leader -> members
     unsigned *words;                         // [B][64]: cluster k's 256-byte block: word 0 = gate (tag << 4 | the leader's XCD + 1: (C, T) are out), words 8 .. 8 + G - 2 = tag << 4 | XCD + 1 of
                                              // members 1 .. G-1 (written at their entry), word 32 = tag of the last completed evaluation
     unsigned *status;                        // [1] sticky error word
@@ -71,7 +72,13 @@ struct EvalCallArgs {                         // what changes per call
     int test_drop_members;                   // tests (frx_debug_set_eval_fused(p, 2)): the members leave at once, as if they never got a CU - the leader's wait for the partials expires
     int force_wt;                            // 1 = every payload store write-through, as if no two workgroups shared an XCD (tests: FRX_EVAL_FUSED_WT=1)
 };
-template <bool ARGP>
+// The early barrier of the early-duration form (forward_knot_body<.., ET>): the caller's loads behind the body's, then one barrier that zeroes the counters and makes the
+// status early-out workgroup-uniform.
+template <class F> struct EvalEarlySync {
+    const F &f; long long *st; bool steps;
+    __device__ __forceinline__ bool sync() const { return f(); }
+};
+template <bool ARGP, bool ET>
 __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::conditional<ARGP, const EvalClusterArgs *__restrict__, EvalClusterArgs>::type arg, EvalCallArgs call) {
     const EvalClusterArgs &a = [&]() -> const EvalClusterArgs & { if constexpr (ARGP) return *arg; else return arg; }();
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -86,11 +93,15 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     const int p0 = a.dp.poff[c], N = a.dp.poff[c + 1] - p0;
     const int ntasks = (N + a.ppw - 1) / a.ppw;                     // wave-tasks of this candidate: ppw pieces each; members 1 .. G-1 hold 4 (G - 1) >= ntasks waves
     if (wg != 0 && ((wg - 1) * 4 >= ntasks || call.test_drop_members)) return;   // a member without a task
+    unsigned st0 = 0u;                                              // (ET: thread 0's copy of the status word, the workgroup's first load)
+    if constexpr (ET) { if (t == 0) st0 = __hip_atomic_load(a.status, FRX_RLX_AGENT); }
+    else {
     // A wait of an EARLIER launch expired and nobody has cleared the word yet (the capturable form has no host-synchronous point of its own: replays of a captured
     // graph go on until the caller polls frx_eval_status): nothing is evaluated, nothing spins; the objective values say so.
     if (__builtin_expect(__hip_atomic_load(a.status, FRX_RLX_AGENT) != 0u, 0)) {
         if (wg == 0 && threadIdx.x == 0) call.f[k] = __builtin_nan("");
         return;
+    }
     }
     unsigned tag = __hip_atomic_load(done, FRX_RLX_AGENT) + 1u;     // (stays in a vector register: nothing waits for the load until the tag is used)
     if (tag >= (1u << 28)) tag = 1u;
@@ -115,11 +126,48 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     const int gp0 = p0 + task * a.ppw, npieces = has_task ? min(a.ppw, N - task * a.ppw) : 0;
     const int hstride = (a.Kmax + 1) * 4;
     double *wsm = sm + L.mem + (size_t)wave * a.pen_lds, *hS = wsm, *red = wsm + (size_t)a.ppw * hstride;
+    double2 hv[4];                                                  // (ET, members) the first trip of the corridor blocks, loaded behind the forward map's loads
+    const double2 *h2 = (const double2 *)(a.dp.hblk + (size_t)gp0 * hstride);
+    const int nh2 = (npieces * hstride) >> 1;
+    bool bad = false;
+    if constexpr (ET) {
+        if (k == 0 && wg == 1 && wave == 0 && lane == 0 && a.dp.stamps) a.dp.stamps[44] = (long long)wall_clock64();
+        const auto early = [&]() -> bool {
+            if (has_task) {
+#pragma unroll
+                for (int u = 0; u < 4; u++) { const int i = lane + 64 * u; hv[u] = h2[i < nh2 ? i : nh2 - 1]; }
+            }
+            unsigned *w = (unsigned *)(ev + 24 * 64);               // forward_knot_body's progress words (its rowbuf is ev)
+            if (t == 0) { w[0] = 0u; w[2] = 0u; w[3] = 0u; w[4] = 0u; w[5] = st0; }
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            bad = *(volatile unsigned *)(w + 5) != 0u;
+            if (!bad && wg == 0 && t == 0) __hip_atomic_store(flag, (tag << 4) | (my_xcc ? my_xcc : 15u), FRX_RLX_AGENT);
+            return bad;
+        };
+        const int wg_last = min(a.G - 1, (ntasks - 1) / 4 + 1);           // the last-dispatched member with a task
+        long long *est = nullptr;
+        if (a.dp.stamps && k == 0 && (wg == 0 || wg == wg_last)) est = a.dp.stamps + (wg == 0 ? 50 : 60);
+        const EvalEarlySync<decltype(early)> es{early, est, wg == 0};
+        forward_knot_body<false, 64, 5, 0, true>(a.dp, call.x, a.T, a.C, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, a.nsteps, c, ev, ctl, true, &ro, nullptr, nullptr, &es);
+        if (bad) {                                                   // an earlier launch's wait expired (see above): uniform over the workgroup
+            if (wg == 0 && t == 0) call.f[k] = __builtin_nan("");
+            return;
+        }
+        if (has_task) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) { const int i = lane + 64 * u; if (i < nh2) { hS[2 * i] = hv[u].x; hS[2 * i + 1] = hv[u].y; } }
+            for (int i0 = lane + 4 * 64; i0 < nh2; i0 += 4 * 64) {
+                double2 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) { const int i = i0 + 64 * u; v[u] = h2[i < nh2 ? i : nh2 - 1]; }
+#pragma unroll
+                for (int u = 0; u < 4; u++) { const int i = i0 + 64 * u; if (i < nh2) { hS[2 * i] = v[u].x; hS[2 * i + 1] = v[u].y; } }
+            }
+        }
+    } else {
     if (wg == 0) { if (t == 0) __hip_atomic_store(flag, (tag << 4) | (my_xcc ? my_xcc : 15u), FRX_RLX_AGENT); }
     else if (has_task) {   // corridor blocks of the wave's task: constant, in flight under the forward map
         if (k == 0 && wg == 1 && wave == 0 && lane == 0 && a.dp.stamps) a.dp.stamps[44] = (long long)wall_clock64();
-        const double2 *h2 = (const double2 *)(a.dp.hblk + (size_t)gp0 * hstride);
-        const int nh2 = (npieces * hstride) >> 1;
         for (int i0 = lane; i0 < nh2; i0 += 4 * 64) {
             double2 v[4];
 #pragma unroll
@@ -129,6 +177,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
         }
     }
     forward_knot_body<false, 64, 5>(a.dp, call.x, a.T, a.C, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, a.nsteps, c, ev, ctl, true, &ro);   // MODE 1 | 4: stages x and the polytopes itself, (C, T) into ctl only
+    }
     if (wg != 0) {
         // every WAVE of a member is on its own from here (no workgroup barrier below): its samples out of the workgroup's (C, T) copy, its partials as granules
         if (!has_task) return;

@@ -1185,8 +1185,10 @@ __device__ __forceinline__ void lds_wait_ge(lds_vuptr w, unsigned want) {
 // Executes exactly ONE s_barrier (after its second step - or its last, or the final inverse, when there are fewer): the caller's axis
 // waves meet it there once their knot positions are in LDS (measured: they arrive ~2.6 k cycles after the durations are known, the
 // matrix wave's build + first step take 1.5 k).
+// NOBAR (the early-duration form of forward_knot_body): no s_barrier at all - the axis waves take the multipliers by the step counter alone.
+template <bool NOBAR = false>
 __device__ __forceinline__ void pcr_matrix_wave64(double *rowbuf, int kk, int N, double hL, double hR, double *pw, int pws, double *save, size_t sstride,
-                                                  size_t gk0, int nsteps, lds_vuptr progress) {
+                                                  size_t gk0, int nsteps, lds_vuptr progress, long long *est = nullptr) {
     const int nrow = 64;
     const bool act = kk >= 1 && kk <= N - 1;
     int nst = 0;
@@ -1250,7 +1252,8 @@ __device__ __forceinline__ void pcr_matrix_wave64(double *rowbuf, int kk, int N,
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (kk == 0) *progress = (unsigned)(it + 1);
-        if (it == (nst > 1 ? 1 : 0)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the axis waves need about two steps' time for the waypoint map
+        if constexpr (NOBAR) { if (est && kk == 0) est[it] = (long long)wall_clock64(); }
+        else if (it == (nst > 1 ? 1 : 0)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the axis waves need about two steps' time for the waypoint map
     }
     if (act) {                                                      // D^-1 of the decoupled rows
 #pragma unroll
@@ -1259,7 +1262,8 @@ __device__ __forceinline__ void pcr_matrix_wave64(double *rowbuf, int kk, int N,
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (kk == 0) *progress = (unsigned)(nst + 1);
-    if (nst == 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if constexpr (NOBAR) { if (est && kk == 0) est[6] = (long long)wall_clock64(); }
+    else if (nst == 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 #undef MR2
 #undef RS
@@ -1276,10 +1280,15 @@ __device__ __forceinline__ void pcr_matrix_wave64(double *rowbuf, int kk, int N,
 // RB > 0 (with NR = 64 and a ct_lds copy only): the caller's scratch holds RB doubles of row buffer instead of 36 nrow - the wave-specialised path uses the (D^-1, L)
 // rows of two buffers ([0, 1280) doubles) and the progress words at 24 nrow = 1536; the coefficients are collected in ct_lds (the solo launch, frx_solo_kernel.hpp: LDS is
 // what keeps a second workgroup off its CU).
-template <bool SH, int NR = 0, int MODE = 0, int RB = 0>
+// ET (early durations; NR = 64, MODE & 1, a ct_lds copy; the one-launch evaluation): wave 0 - the matrix wave - loads tau into registers as its first loads, takes no share
+// of the staging and forms the durations on its own; waves 1-3 stage xi and the polytopes.  No workgroup barrier in front of the coefficient collection: the axis waves meet
+// each other at LDS arrival counters and read Tf once wave 0 has flagged it.  The caller zeroes nothing itself: `es->sync()` is called once every wave has issued its loads,
+// zeroes the counters behind the caller's own loads and ends in the workgroup's one early barrier; it returns true when the workgroup is to do nothing (uniformly).
+// es->st (optional): 100 MHz stamps - [0] durations formed, [1] staged, [2] waypoint map done, es->steps: [3 + s] matrix step s done, [9] matrix wave done; otherwise [3] matrix wave done.
+template <bool SH, int NR = 0, int MODE = 0, int RB = 0, bool ET = false, class ES = void>
 __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const double *__restrict__ x, double *__restrict__ Tout, double *__restrict__ Cout,
                                int maxCN, int maxXb, int maxVb, int nrow_rt, double *__restrict__ pcrw, int nsteps, int b, double *sm, double *ct_lds = nullptr, bool wt = true, const ResidentOps *ro = nullptr,
-                               const KnotPre *pre = nullptr, const GranuleOut *go = nullptr) {
+                               const KnotPre *pre = nullptr, const GranuleOut *go = nullptr, const ES *es = nullptr) {
     // ct_lds (optional, LDS, 19 doubles per piece: 18 coefficients + duration): a copy for the backward pass of the same workgroup
     const int nrow = NR > 0 ? NR : nrow_rt;
     const int k = threadIdx.x, nthr = NR > 0 ? 256 : (int)blockDim.x;
@@ -1323,7 +1332,70 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
         for (int q = 0; q < 3; q++) { r_bs[q] = dp.headPVA[b * 9 + 3 * q + kbs]; r_bs[3 + q] = dp.tailPVA[b * 9 + 3 * q + kbs]; }
     }
     lds_vuptr progress = (lds_vuptr)(unsigned *)(rowbuf + (size_t)24 * nrow);   // step counter of the matrix wave (wsp64; the rhs buffers behind the rows are unused there)
-    if (wsp64 && k == 0) *progress = 0u;
+    // ET: progress[2] = axis waves staged, [3] = axis waves' knot positions written, [4] = Tf written (wave 0); zeroed by es->sync()
+    unsigned *const arrive = (unsigned *)(rowbuf + (size_t)24 * nrow);
+    if (!ET && wsp64 && k == 0) *progress = 0u;
+    double hMine = 1.0;
+    long long *est = nullptr;
+    bool est_steps = false;
+    if constexpr (ET) { est = es->st; est_steps = es->steps; }
+    if constexpr (ET) {
+        static_assert(NR == 64 && (MODE & 1), "early durations: the wave-specialised <= 64-piece path of a caller that stages");
+        const int wave = __builtin_amdgcn_readfirstlane(k >> 6), kk = k & 63;
+        const int nT = dp.soft ? cN : cN - 1;                      // tau of this candidate: x[x0, x0 + nT)
+        const int nx = dp.xoff[b + 1] - x0;
+        const int v0 = dp.cvoff[b], nvd = 3 * (dp.cvoff[b + 1] - v0);
+        const double *vsrc = dp.vrec + 3 * (size_t)v0;
+        constexpr int UX = 4, UV = 16, NA = 192;                   // the first staging trip of the three axis waves, held in registers across the early barrier
+        double tau = 0.0, sx[UX], sv[UV];
+        if (wave == 0) {
+            if (kk < nT) tau = x[x0 + kk];
+        } else {
+#pragma unroll
+            for (int u = 0; u < UX; u++) { const int i = nT + t2 + u * NA; sx[u] = nx > 0 ? x[x0 + (i < nx ? i : nx - 1)] : 0.0; }
+#pragma unroll
+            for (int u = 0; u < UV; u++) { const int i = t2 + u * NA; sv[u] = nvd > 0 ? vsrc[i < nvd ? i : nvd - 1] : 0.0; }
+        }
+        if (es->sync()) return;
+        if (wave == 0) {
+            // forwardT (CPU.hpp:626-676) and splitToFineT (CPU.hpp:930-944) inside the wave, the same expressions in the same order as below; LDS operations of one wave
+            // complete in order, so lane 0 sees the other lanes' writes without a barrier
+            if (kk < nT) xs[kk] = tau;                                // (the adjoint reads tau from ro->xs)
+            if (dp.soft) {
+                if (kk < cN) Tc[kk] = tau_to_T(tau, dp.c2 != 0);
+            } else if (kk == 0) {
+                const int Ms1 = cN - 1;
+                double sum = 0.0;
+                for (int i = 0; i < Ms1; i++) Tc[i] = tau_to_T(xs[i], dp.c2 != 0);
+                Tc[Ms1] = 0.0;
+                for (int i = 0; i <= Ms1; i++) sum += Tc[i];
+                const double den = 1.0 + sum;
+                for (int i = 0; i <= Ms1; i++) Tc[i] /= den;
+                sum = 0.0;
+                for (int i = 0; i <= Ms1; i++) sum += Tc[i];
+                Tc[Ms1] = 1.0 - sum;
+                for (int i = 0; i <= Ms1; i++) Tc[i] *= dp.sumT;
+            }
+            if (kk < N) {
+                hMine = Tc[r_pc - c0] / r_piv;
+                Tf[kk] = hMine;
+                ct_lds[kk * 19 + 18] = hMine;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (kk == 0) { progress[4] = 1u; if (est) est[0] = (long long)wall_clock64(); }
+        } else {
+#pragma unroll
+            for (int u = 0; u < UX; u++) { const int i = nT + t2 + u * NA; if (i < nx) xs[i] = sx[u]; }
+#pragma unroll
+            for (int u = 0; u < UV; u++) { const int i = t2 + u * NA; if (i < nvd) vs[i] = sv[u]; }
+            stage_to_lds<4>(xs, x + x0, nx, nT + t2 + UX * NA, NA);   // (longer candidates: the rest)
+            stage_to_lds<8>(vs, vsrc, nvd, t2 + UV * NA, NA);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (kk == 0) __hip_atomic_fetch_add(arrive + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            lds_wait_ge(progress + 2, 3u);
+            if (est && k == 64) est[1] = (long long)wall_clock64();
+        }
+    } else {
     {   // coalesced staging: every later access is an LDS access (the per-waypoint loops would otherwise serialise
         // one global-memory latency per vertex)
         if (!ro || (MODE & 1)) {
@@ -1339,7 +1411,8 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
     // 1.3 k cycles either way.  What that stretch WAS waiting for were the index-table loads, see KnotPre.)
     __syncthreads();
     FWD_STAMP(1);
-
+    }
+    if constexpr (!ET) {
     // forwardT (CPU.hpp:626-676)
     if (dp.soft) {
         for (int i = k; i < cN; i += nthr) Tc[i] = tau_to_T(xs[i], dp.c2 != 0);
@@ -1358,13 +1431,13 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
     }
     __syncthreads();
     // splitToFineT (CPU.hpp:930-944)
-    double hMine = 1.0;
     if (k < N) {
         hMine = Tc[r_pc - c0] / r_piv;
         Tf[k] = hMine;
         if ((MODE & 2) && SH && go && go->ll) rk_ll_put(go->ll + 2 * ((size_t)(p0 + k) * 19 + 18), hMine, go->tag, go->mxw ? true : wt);   // (mxw: where the consumers run is not known yet - early, off the critical path: write-through)
         else if (!(MODE & 4)) stg<SH>(Tout + p0 + k, hMine, wt);             // (MODE & 4: (C, T) stay in the caller's ct_lds copy and never go to global memory - the solo launch)
         if (ct_lds) ct_lds[k * 19 + 18] = hMine;
+    }
     }
     FWD_STAMP(2);
     if (wsp64) {
@@ -1376,7 +1449,9 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
             // durations left and right of knot kk: the left one comes from the neighbouring lane (lane = piece = knot)
             const double hLs = lane_up1(hMine);
             const bool act0 = kk >= 1 && kk <= N - 1;
-            pcr_matrix_wave64(rowbuf, kk, N, act0 ? hLs : 1.0, act0 ? hMine : 1.0, pwf, pws, ro ? nullptr : pcrw, (size_t)(nsteps * 8 + 4), (size_t)p0, nsteps, progress);
+            pcr_matrix_wave64<ET>(rowbuf, kk, N, act0 ? hLs : 1.0, act0 ? hMine : 1.0, pwf, pws, ro ? nullptr : pcrw, (size_t)(nsteps * 8 + 4), (size_t)p0, nsteps, progress,
+                                  (est && est_steps) ? est + 3 : nullptr);
+            if (est && !est_steps && kk == 0) est[3] = (long long)wall_clock64();
             FWD_STAMP(5);
         } else {
             const int ax = wave - 1;
@@ -1414,6 +1489,13 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
                 KN(KP, t2, N) = r_bs[3]; KN(KV, t2, N) = r_bs[4]; KN(KA, t2, N) = r_bs[5];
             }
             FWD_STAMP_AX(8);
+            if constexpr (ET) {                                                  // the three axis waves among themselves, then Tf from wave 0
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (kk == 0) __hip_atomic_fetch_add(arrive + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                lds_wait_ge(progress + 3, 3u);
+                lds_wait_ge(progress + 4, 1u);
+                if (est && k == 64) est[2] = (long long)wall_clock64();
+            } else
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // meets the matrix wave's only barrier: knot positions and Tf are in LDS
             FWD_STAMP_AX(9);
             // right-hand side of knot kk for this axis (knot_row_rhs; the fixed end states move to the right-hand side)
