@@ -67,18 +67,26 @@ ABI_SYMBOLS = [
     "frx_dilate_batch", "frx_multi_create", "frx_multi_destroy", "frx_multi_info", "frx_multi_layout", "frx_multi_initial_guess", "frx_multi_optimize", "frx_multi_last_exchange",
     "frx_map_mark_cloud", "frx_map_is_blocked", "frx_grid_search", "frx_jps_plan", "frx_route_plan",
     "frx_trajectory_check", "frx_trajectory_check_device", "frx_trajectory_sample", "frx_trajectory_sample_device",
+    "frx_trajectory_clearance", "frx_trajectory_clearance_workspace", "frx_trajectory_clearance_device",
 ]
 # diagnostics, include/frx_debug.h: not part of the drop-in boundary
 DEBUG_SYMBOLS = [
     "frx_debug_trace", "frx_resident_profile", "frx_debug_direction_log", "frx_debug_direction_log_read", "frx_debug_set_resident_retry",
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
     "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
+    "frx_debug_set_clear_chunk",
 ]
 
 # frx_trajectory_check (include/frx.h): fields of a row and flag bits
 CHECK_FIELDS = ("corridor", "speed", "thrust_min", "thrust_max", "body_rate", "acc", "worst_t", "worst_k")
 CHECK_MAX_INTERVALS = 16384
 CHECK_FLAG_CORRIDOR, CHECK_FLAG_SPEED, CHECK_FLAG_THRUST_MIN, CHECK_FLAG_THRUST_MAX, CHECK_FLAG_BODY_RATE, CHECK_FLAG_NONFINITE = 1, 2, 4, 8, 16, 32
+# frx_trajectory_clearance (include/frx.h): fields of a row, flag bits, the largest cloud; CLEAR_TILE sample states and CLEAR_PASS cloud points are what a
+# workgroup of the kernel holds at a time (fast-racing_amd/csrc/frx_device.hpp), the sizes at which it takes another turn of a loop
+CLEAR_FIELDS = ("ell", "dist", "worst_t", "worst_i")
+CLEAR_MAX_POINTS = 1 << 24
+CLEAR_FLAG_COLLISION, CLEAR_FLAG_NONFINITE = 1, 2
+CLEAR_TILE, CLEAR_PASS = 64, 1024
 # frx_trajectory_sample (include/frx.h): doubles of a row and the named parts of it (FRX_SAMPLE_*)
 SAMPLE_FIELDS = 20
 SAMPLE_VIEWS = dict(pos=slice(0, 3), vel=slice(3, 6), acc=slice(6, 9), jerk=slice(9, 12), thrust=12, quat=slice(13, 17), omega=slice(17, 20))
@@ -156,6 +164,10 @@ def lib():
         L.frx_trajectory_check_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.frx_trajectory_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         L.frx_trajectory_sample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_clearance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_clearance_workspace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.frx_trajectory_clearance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_debug_set_clear_chunk.argtypes = [C.c_void_p, C.c_int]
         L.frx_optimize.argtypes = [C.c_void_p, C.POINTER(LbfgsParams), _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
         L.frx_optimize_stats.argtypes = [C.c_void_p, _dp]
         L.frx_lbfgs_minimize_batch.argtypes = [C.c_int, _ip, _dp, _dp, _ip, _ip, _ip, C.POINTER(LbfgsParams), BATCH_EVAL_FN,
@@ -608,6 +620,37 @@ class Problem:
         """frx_trajectory_sample_device: the rows (B x n_samples x 20 doubles at out_ptr, 16-byte aligned) as one launch on `stream`, device pointers
         (times_ptr = 0: no times array), no copy, no synchronisation."""
         _check(lib().frx_trajectory_sample_device(self.h, T_ptr, C_ptr, int(n_samples), float(t0), float(dt), times_ptr or None, out_ptr, stream))
+
+    def trajectory_clearance(self, T, Cf, obs, intervals: int = 256):
+        """Clearance of the batch (T, C) against the obstacle cloud obs (n_obs, 3) (frx_trajectory_clearance): dict(piece (P, 4), cand (B, 4),
+        flags (B,) uint32) plus the candidate rows' fields by name (CLEAR_FIELDS: ell >= 1 means free, dist in metres, worst_t, worst_i)."""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1); Cf = np.ascontiguousarray(Cf, dtype=np.float64).reshape(-1)
+        if T.size != self.P or Cf.size != 18 * self.P:
+            raise ValueError(f"trajectory_clearance: expected {self.P} durations and {18 * self.P} coefficients, got {T.size} and {Cf.size}")
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != 3:
+            raise ValueError(f"trajectory_clearance: obs must have shape (n_obs, 3), got {obs.shape}")
+        piece = np.zeros((self.P, 4)); cand = np.zeros((self.B, 4)); flags = np.zeros(self.B, np.uint32)
+        _check(lib().frx_trajectory_clearance(self.h, T.ctypes.data, Cf.ctypes.data, int(intervals), obs.shape[0], obs.ctypes.data, piece.ctypes.data,
+                                              cand.ctypes.data, flags.ctypes.data))
+        out = dict(piece=piece, cand=cand, flags=flags)
+        out.update({name: cand[:, i] for i, name in enumerate(CLEAR_FIELDS)})
+        return out
+
+    def trajectory_clearance_workspace(self, n_obs: int, intervals: int = 256) -> int:
+        """frx_trajectory_clearance_workspace: bytes of scratch trajectory_clearance_device needs for a cloud of n_obs points (0: none)."""
+        n = C.c_size_t(0)
+        _check(lib().frx_trajectory_clearance_workspace(self.h, int(intervals), int(n_obs), C.byref(n)))
+        return int(n.value)
+
+    def trajectory_clearance_device(self, T_ptr: int, C_ptr: int, obs_ptr: int, n_obs: int, work_ptr: int, out_ptr: int, intervals: int = 256, stream: int = 0):
+        """frx_trajectory_clearance_device: the piece rows (P x 4 doubles at out_ptr) as pure launches on `stream`, device pointers (work_ptr: the scratch
+        trajectory_clearance_workspace asks for, 0 when that is 0), no copy, no synchronisation, no allocation."""
+        _check(lib().frx_trajectory_clearance_device(self.h, T_ptr, C_ptr, int(intervals), int(n_obs), obs_ptr, work_ptr or None, out_ptr, stream))
+
+    def set_clear_chunk(self, points: int):
+        """Tests (frx_debug_set_clear_chunk): cloud points per chunk of every later clearance call on the handle, 0 = the library's own split."""
+        _check(lib().frx_debug_set_clear_chunk(self.h, int(points)))
 
     def forward(self, x):
         T = np.zeros(self.P); Cf = np.zeros(self.P * 18)

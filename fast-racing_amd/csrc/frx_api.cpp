@@ -230,6 +230,8 @@ struct frx_problem {
     PinBuf<double> h_x, h_f, h_g, h_T, h_C, h_out20;
     DevBuf<double> d_check;                                 // [P][8] rows of frx_trajectory_check, allocated on its first call
     DevBuf<double> d_sample;                                // frx_trajectory_sample: [B][S][20] rows, then [B][S] times; grown as needed
+    DevBuf<double> d_clear;                                 // frx_trajectory_clearance: [P][4] rows, the cloud [n_obs][3], then the partials [P][chunks][4]; grown as needed
+    int clear_chunk = 0;                                    // tests (frx_debug_set_clear_chunk): > 0 = cloud points per chunk, 0 = the library's own split
     // device-vector L-BFGS state (allocated on first use)
     DevBuf<double> d_xp, d_gp, d_dir, d_S, d_Y, d_ys, d_gt;
     PinBuf<frx::DvCommand> h_cmd;
@@ -1045,6 +1047,96 @@ int frx_trajectory_check(frx_problem *p, const double *T, const double *C, int i
             flags[b] = fl;
         }
     }
+    return FRX_OK;
+}
+
+// argument rules of every form of frx_trajectory_clearance, checked before the handle is read; then the split of the cloud
+static int clear_args(frx_problem *p, const void *T, const void *C, int intervals, int n_obs, const void *obs, const void *out, int *chunk, int *nchunks) {
+    if (!p || !T || !C || !obs || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
+    if (n_obs < 1 || n_obs > FRX_CLEAR_MAX_POINTS) return fail(FRX_ERR_INVALID_ARG, "n_obs must lie in 1.." + std::to_string(FRX_CLEAR_MAX_POINTS));
+    if (!frx::clear_geometry(p->P, n_obs, p->clear_chunk, chunk, nchunks))
+        return fail(FRX_ERR_CAPACITY, "frx_trajectory_clearance: " + std::to_string(p->P) + " pieces x the cloud's chunks exceed a grid");
+    return FRX_OK;
+}
+
+int frx_trajectory_clearance_workspace(frx_problem *p, int intervals, int n_obs, size_t *bytes) {
+    int chunk = 0, nchunks = 0;
+    const int rc = clear_args(p, bytes, bytes, intervals, n_obs, bytes, bytes, &chunk, &nchunks);
+    if (rc != FRX_OK) return rc;
+    *bytes = nchunks > 1 ? sizeof(double) * FRX_CLEAR_FIELDS * (size_t)p->P * (size_t)nchunks : 0;   // one chunk: the kernel writes the rows itself
+    return FRX_OK;
+}
+
+int frx_trajectory_clearance_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, int n_obs, const double *obs_dev, void *work_dev,
+                                    double *piece_out_dev, void *hip_stream) {
+    int chunk = 0, nchunks = 0;
+    const int rc = clear_args(p, T_dev, C_dev, intervals, n_obs, obs_dev, piece_out_dev, &chunk, &nchunks);
+    if (rc != FRX_OK) return rc;
+    if (nchunks > 1 && !work_dev) return fail(FRX_ERR_INVALID_ARG, "work_dev is NULL and frx_trajectory_clearance_workspace asks for scratch");
+    HIP_TRY((hipError_t)frx::launch_clear(p->dp, T_dev, C_dev, intervals, n_obs, obs_dev, chunk, nchunks, (double *)work_dev, piece_out_dev, hip_stream));
+    return FRX_OK;
+}
+
+int frx_trajectory_clearance(frx_problem *p, const double *T, const double *C, int intervals, int n_obs, const double *obs, double *piece_out, double *cand_out,
+                             unsigned *flags) {
+    int chunk = 0, nchunks = 0;
+    const int rc = clear_args(p, T, C, intervals, n_obs, obs, cand_out, &chunk, &nchunks);
+    if (rc != FRX_OK) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n_rows = (size_t)FRX_CLEAR_FIELDS * p->P, n_cloud = 3 * (size_t)n_obs, n_work = nchunks > 1 ? n_rows * (size_t)nchunks : 0;
+    const size_t need = n_rows + n_cloud + n_work;
+    if (p->d_clear.n < need && p->d_clear.alloc(need) != hipSuccess) {
+        (void)hipGetLastError();                                            // (a failed allocation is no error of a later launch)
+        return fail(FRX_ERR_ALLOC, "frx_trajectory_clearance: cannot allocate " + std::to_string(need * sizeof(double)) + " bytes on the device");
+    }
+    double *d_rows = p->d_clear.p, *d_obs = d_rows + n_rows, *d_work = n_work ? d_obs + n_cloud : nullptr;
+    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
+    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
+    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(d_obs, obs, sizeof(double) * n_cloud, hipMemcpyHostToDevice, p->stream));
+    const int lrc = frx_trajectory_clearance_device(p, p->d_T.p, p->d_C.p, intervals, n_obs, d_obs, d_work, d_rows, p->stream);
+    if (lrc != FRX_OK) return lrc;
+    double *rows = p->h_out20.p;                                            // (P x 20 doubles of staging: the P x 4 rows fit)
+    HIP_TRY(hipMemcpyAsync(rows, d_rows, sizeof(double) * n_rows, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (piece_out) std::memcpy(piece_out, rows, sizeof(double) * n_rows);
+    // per candidate, in piece order, the kernel's order on (ELL, piece): NaN beats any number, then the smaller value, then the earlier piece; DIST is a
+    // NaN-propagating min; the prefix of durations is summed left to right as frx_trajectory_check sums it
+    for (int b = 0; b < p->B; b++) {
+        double *o = cand_out + (size_t)FRX_CLEAR_FIELDS * b;
+        double t0 = 0.0;
+        for (int gp = p->poff[b]; gp < p->poff[b + 1]; gp++) {
+            const double *r = rows + (size_t)FRX_CLEAR_FIELDS * gp;
+            if (gp == p->poff[b]) {
+                for (int f = 0; f < FRX_CLEAR_FIELDS; f++) o[f] = r[f];
+            } else {
+                const double a = o[FRX_CLEAR_ELL], c = r[FRX_CLEAR_ELL];
+                if (a == a && (c < a || c != c)) {
+                    o[FRX_CLEAR_ELL] = c; o[FRX_CLEAR_WORST_T] = t0 + r[FRX_CLEAR_WORST_T]; o[FRX_CLEAR_WORST_I] = r[FRX_CLEAR_WORST_I];
+                }
+                const double d = o[FRX_CLEAR_DIST], e = r[FRX_CLEAR_DIST];
+                o[FRX_CLEAR_DIST] = (d < e || d != d) ? d : e;
+            }
+            t0 += T[gp];
+        }
+        if (flags) {
+            unsigned fl = 0u;
+            if (o[FRX_CLEAR_ELL] < 1.0) fl |= FRX_CLEAR_FLAG_COLLISION;
+            for (int f = 0; f < FRX_CLEAR_FIELDS; f++)
+                if (!std::isfinite(o[f])) fl |= FRX_CLEAR_FLAG_NONFINITE;
+            flags[b] = fl;
+        }
+    }
+    return FRX_OK;
+}
+
+// Tests: points > 0 makes every later clearance call on the handle split the cloud into chunks of that many points (the last one shorter), whatever the
+// number of pieces; 0 returns to the library's own split.  The workspace query follows it.
+int frx_debug_set_clear_chunk(frx_problem *p, int points) {
+    if (!p || points < 0) return fail(FRX_ERR_INVALID_ARG, "null handle or a negative chunk");
+    p->clear_chunk = points;
     return FRX_OK;
 }
 

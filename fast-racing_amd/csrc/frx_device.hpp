@@ -103,6 +103,30 @@ int sample_fits(int maxN);
 int launch_sample(const DevProblem &dp, int maxN, const double *T, const double *C, int S, double t0, double dt, const double *times, double *out,
                   void *stream);
 
+// ---- clearance of a batch of trajectories against the obstacle cloud (frx_clear_kernel.hpp) ----
+enum { CLEAR_TILE = 64,                  // sample states a workgroup holds in LDS at a time
+       CLEAR_PASS = 1024,                // cloud points a workgroup holds in registers at a time (256 lanes x 4)
+       CLEAR_TARGET_WGS = 2048 };        // workgroups the cloud is split for when there are few pieces: 8 per CU of a 256-CU device, a constant so that
+                                         // the split (and with it the workspace) depends on (P, n_obs) alone
+// points per cloud chunk and chunks per piece: force > 0 takes that many points per chunk, else enough chunks of whole passes to reach CLEAR_TARGET_WGS
+// workgroups (one chunk when P alone does).  0 when P x chunks does not fit a grid.
+inline int clear_geometry(int P, int n_obs, int force, int *chunk, int *nchunks) {
+    long long c = force;
+    if (force <= 0) {
+        const long long want = P < CLEAR_TARGET_WGS ? CLEAR_TARGET_WGS / P : 1;
+        c = ((long long)n_obs + want - 1) / want;
+        c = (c + CLEAR_PASS - 1) / CLEAR_PASS * CLEAR_PASS;
+    }
+    const long long nc = ((long long)n_obs + c - 1) / c;
+    if ((long long)P * nc > 0x7fffffffLL) return 0;
+    *chunk = (int)(c < n_obs ? c : n_obs); *nchunks = (int)nc;
+    return 1;
+}
+// rows: [P][4] (frx.h FRX_CLEAR_*) of the pieces (T, C) against obs [n_obs][3]; work: [P][nchunks][4] partials, not touched when nchunks == 1;
+// every pointer is a device pointer.  Pure launches: two kernels, one when nchunks == 1.
+int launch_clear(const DevProblem &dp, const double *T, const double *C, int intervals, int n_obs, const double *obs, int chunk, int nchunks,
+                 double *work, double *rows, void *stream);
+
 // ---- device-vector L-BFGS (frx_lbfgs_kernels.hpp) ----
 struct DvBuffers;
 struct DvLaunch {

@@ -28,6 +28,8 @@
 #ifndef FRX_H
 #define FRX_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -292,6 +294,48 @@ int frx_trajectory_check_device(frx_problem *p, const double *T_dev, const doubl
 int frx_trajectory_sample(frx_problem *p, const double *T, const double *C, int n_samples, double t0, double dt, const double *times, double *out);
 int frx_trajectory_sample_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_samples, double t0, double dt,
                                  const double *times_dev, double *out_dev, void *hip_stream);
+
+/* Clearance of a batch of results against the obstacle cloud itself, on the device.  frx_trajectory_check measures how far the body reaches past the
+ * faces of corridors the library (or the caller) built; nothing there sees the point cloud the corridors came from, so a defect in corridor
+ * generation, in the piece <-> polytope map or in a caller's own corridors is invisible to it.  The reference has no such test either
+ * (MinCoPlan_CPU.cpp:131-132 prints getMaxVelRate / getMaxAccRate and flies).
+ * Every fine piece is sampled at s_j = j (T / M), j = 0..M, M = intervals (1..FRX_CHECK_MAX_INTERVALS; the step is formed first, then multiplied,
+ * as in the check).  At each sample: p and the frame R = [xB yB zB](h), h = a + g e3, in the check's arithmetic; E = diag(ellipsoid).  For every
+ * cloud point o_i, i = 0..n_obs-1 (obs: n_obs x 3 doubles as frx_dilate_batch takes them):
+ *   u = o_i - p (the difference is formed first);  q = (xB.u / e0)^2 + (yB.u / e1)^2 + (zB.u / e2)^2;  r = u.u
+ * q is the square of decomp_util's Ellipsoid::dist for the body ellipsoid C = R E: q < 1 means the point is inside the body.
+ * Fields of a row (FRX_CLEAR_FIELDS doubles):
+ *   FRX_CLEAR_ELL       sqrt(min q), dimensionless; >= 1 means free (one IEEE square root of the minimum)
+ *   FRX_CLEAR_DIST      sqrt(min r), metres from the body centre (its minimiser is not reported)
+ *   FRX_CLEAR_WORST_T   local time s_j of the sample that attains min q
+ *   FRX_CLEAR_WORST_I   index i of the cloud point that attains it
+ * The worst (q, j, i) is taken under a total order: NaN beats any number, then the smaller q, then the lower j, then the lower i.  min r propagates
+ * NaN.  A non-finite T, C or cloud point therefore shows as NaN and is never hidden by a minimum.  A candidate's row reduces its pieces in piece order
+ * with the same order (an earlier piece before a later one); there WORST_T is the time from the candidate's start, the durations summed left to
+ * right.  Flags per candidate: FRX_CLEAR_FLAG_*.  Rows are bit-identical run to run, between the forms, whatever else is in the batch and however the
+ * cloud is split over workgroups.
+ *   frx_trajectory_clearance            blocking, host pointers: T[total fine pieces], C[total fine pieces x 18], obs[n_obs x 3]; piece_out (P x 4)
+ *                                       and flags (B) may be NULL, cand_out (B x 4) may not.  Keeps one device buffer per handle for the cloud and
+ *                                       grows it (FRX_ERR_ALLOC when it cannot).
+ *   frx_trajectory_clearance_workspace  bytes of scratch the device form needs: a function of (total fine pieces, intervals, n_obs) alone, never of
+ *                                       the device.  0 when the cloud is not split (work_dev may then be NULL).
+ *   frx_trajectory_clearance_device     pure launches on the caller's stream, device pointers: no copy, no synchronisation, no allocation
+ *                                       (capturable in a hipGraph); piece rows only.
+ * FRX_ERR_INVALID_ARG: n_obs < 1 or > FRX_CLEAR_MAX_POINTS, intervals out of range, NULL pointers.  Serves both kinds of handle
+ * (frx_problem_create[_from_h], frx_penalty_problem_create). */
+#define FRX_CLEAR_MAX_POINTS (1 << 24)
+#define FRX_CLEAR_FIELDS 4
+#define FRX_CLEAR_ELL 0
+#define FRX_CLEAR_DIST 1
+#define FRX_CLEAR_WORST_T 2
+#define FRX_CLEAR_WORST_I 3
+#define FRX_CLEAR_FLAG_COLLISION 1u     /* ELL < 1 */
+#define FRX_CLEAR_FLAG_NONFINITE 2u     /* a non-finite value in the candidate's row */
+int frx_trajectory_clearance(frx_problem *p, const double *T, const double *C, int intervals, int n_obs, const double *obs, double *piece_out,
+                             double *cand_out, unsigned *flags);
+int frx_trajectory_clearance_workspace(frx_problem *p, int intervals, int n_obs, size_t *bytes);
+int frx_trajectory_clearance_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, int n_obs, const double *obs_dev,
+                                    void *work_dev, double *piece_out_dev, void *hip_stream);
 
 /* Replaces ~cuda_computer / kill_kernel (cc.cu:44-49, 566-579; GPU.hpp:907-909). */
 void frx_problem_destroy(frx_problem *p);
