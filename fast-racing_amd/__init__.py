@@ -68,13 +68,14 @@ ABI_SYMBOLS = [
     "frx_map_mark_cloud", "frx_map_is_blocked", "frx_grid_search", "frx_jps_plan", "frx_route_plan",
     "frx_trajectory_check", "frx_trajectory_check_device", "frx_trajectory_sample", "frx_trajectory_sample_device",
     "frx_trajectory_clearance", "frx_trajectory_clearance_workspace", "frx_trajectory_clearance_device",
+    "frx_corridor_generate_batch", "frx_corridor_generate_batch_device",
 ]
 # diagnostics, include/frx_debug.h: not part of the drop-in boundary
 DEBUG_SYMBOLS = [
     "frx_debug_trace", "frx_resident_profile", "frx_debug_direction_log", "frx_debug_direction_log_read", "frx_debug_set_resident_retry",
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
     "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
-    "frx_debug_set_clear_chunk",
+    "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device",
 ]
 
 # frx_trajectory_check (include/frx.h): fields of a row and flag bits
@@ -168,6 +169,11 @@ def lib():
         L.frx_trajectory_clearance_workspace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.frx_trajectory_clearance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_debug_set_clear_chunk.argtypes = [C.c_void_p, C.c_int]
+        L.frx_corridor_generate_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_corridor_generate_batch_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_debug_map_blocked_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_optimize.argtypes = [C.c_void_p, C.POINTER(LbfgsParams), _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
         L.frx_optimize_stats.argtypes = [C.c_void_p, _dp]
         L.frx_lbfgs_minimize_batch.argtypes = [C.c_int, _ip, _dp, _dp, _ip, _ip, _ip, C.POINTER(LbfgsParams), BATCH_EVAL_FN,
@@ -281,6 +287,58 @@ def corridor_generate(path, obs, bbox, map_height: float, max_seg: float = 4.0, 
     return [h_rec[6 * h_off[k]:6 * h_off[k + 1]].reshape(-1, 6).T.copy() for k in range(n.value)]
 
 
+# frx_corridor_generate_batch (include/frx.h): a path's status
+CHAIN_OK, CHAIN_BOX_POINTS, CHAIN_PLANES, CHAIN_POLYS = 0, 1, 2, 3
+
+
+def unpack_corridors(n_polys, h_off, h_rec):
+    """The CSR of frx_corridor_generate_batch (n_polys per path, h_off over all cells in path order, records of 6 doubles) as a list per path of 6 x K arrays."""
+    h_rec = np.asarray(h_rec, dtype=np.float64).reshape(-1); out = []; c = 0
+    for n in n_polys:
+        out.append([h_rec[6 * h_off[c + k]:6 * h_off[c + k + 1]].reshape(-1, 6).T.copy() for k in range(int(n))])
+        c += int(n)
+    return out
+
+
+def corridor_generate_batch(paths, obs, bbox, map_height: float, max_seg: float = 4.0, blocked=None, cap_polys: int = 128, cap_planes: int = 96, device: int = 0,
+                            raw: bool = False):
+    """Greedy safe-flight corridors of a batch of paths on the device (frx_corridor_generate_batch), what corridor_generate gives path by path with
+    blocked = a VoxelMap (or None: nothing blocks).  Returns (list per path of 6 x K_i arrays, status per path: CHAIN_*); a path with a non-zero status has no
+    cells.  raw=True: (n_polys, h_off, h_rec, status) as the library packs them, ready for Problem(..., enumerate_v=True, packed=...)."""
+    assert blocked is None or isinstance(blocked, VoxelMap), "the device walks sight lines on a VoxelMap; a Python callable cannot run there"
+    paths = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in paths]
+    obs = np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, 3); bbox = np.ascontiguousarray(bbox, dtype=np.float64)
+    B = len(paths)
+    off = np.zeros(B + 1, np.int32); off[1:] = np.cumsum([len(p) for p in paths])
+    flat = np.ascontiguousarray(np.concatenate(paths).reshape(-1)) if B else np.zeros(0)
+    n_polys = np.zeros(max(B, 1), np.int32); status = np.zeros(max(B, 1), np.int32); h_off = np.zeros(max(B, 1) * cap_polys + 1, np.int32); need = C.c_int()
+    mp = C.cast(C.pointer(blocked._s), C.c_void_p) if blocked is not None else None
+    cap_rec = 32 * int(off[-1]) + 64                                  # a first guess; the library reports the need when it is too small
+    for _ in range(2):
+        h_rec = np.zeros(6 * cap_rec)
+        rc = lib().frx_corridor_generate_batch(device, B, off.ctypes.data, flat.ctypes.data, len(obs), obs.ctypes.data if len(obs) else None, bbox.ctypes.data,
+                                               map_height, max_seg, mp, cap_polys, cap_planes, n_polys.ctypes.data, status.ctypes.data, cap_rec, C.byref(need),
+                                               h_off.ctypes.data, h_rec.ctypes.data)
+        if rc != -5 or need.value <= cap_rec:                             # FRX_ERR_CAPACITY with a larger need: once more with that room
+            break
+        cap_rec = need.value
+    _check(rc)
+    n_cells = int(n_polys.sum())
+    if raw:
+        return n_polys[:B].copy(), h_off[:n_cells + 1].copy(), h_rec[:6 * h_off[n_cells]].copy(), status[:B].copy()
+    return unpack_corridors(n_polys[:B], h_off, h_rec), status[:B].copy()
+
+
+def corridor_generate_batch_device(n_paths, path_off_dev, path_dev, n_obs, obs_dev, bbox, map_height, max_seg, map_struct, cap_polys, cap_planes, h_slot_dev,
+                                   cell_planes_dev, n_polys_dev, status_dev, stream=0):
+    """frx_corridor_generate_batch_device: one launch on `stream`; device addresses as integers, map_struct = a VoxelMapStruct whose cells point to device
+    memory, or None.  Slots: h_slot [n_paths][cap_polys][cap_planes][6], cell_planes [n_paths][cap_polys], n_polys, status."""
+    bbox = np.ascontiguousarray(bbox, dtype=np.float64)
+    _check(lib().frx_corridor_generate_batch_device(n_paths, path_off_dev, path_dev, n_obs, obs_dev, bbox.ctypes.data, map_height, max_seg,
+                                                    C.cast(C.pointer(map_struct), C.c_void_p) if map_struct is not None else None, cap_polys, cap_planes,
+                                                    h_slot_dev, cell_planes_dev, n_polys_dev, status_dev, stream))
+
+
 class VoxelMapStruct(C.Structure):
     """frx_voxel_map (include/frx.h)."""
     _fields_ = [("origin", C.c_double * 3), ("dim", C.c_int * 3), ("res", C.c_double), ("cells", C.c_void_p)]
@@ -313,6 +371,13 @@ class VoxelMap:
     def is_blocked(self, a, b) -> bool:
         a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
         return bool(lib().frx_map_is_blocked(a.ctypes.data, b.ctypes.data, C.byref(self._s)))
+
+    def is_blocked_device(self, a, b, device: int = 0):
+        """frx_debug_map_blocked_device: the device's sight line on pairs a[i], b[i] (n x 3 each) -> bool array."""
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3); b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros(len(a), np.int32)
+        _check(lib().frx_debug_map_blocked_device(device, C.byref(self._s), len(a), a.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out.astype(bool)
 
     def plan(self, start, goal, eps: float = 1.0, use_jps: bool = False, cap: int = 1 << 16):
         """frx_jps_plan -> dict(status, raw_path, path, sample_path, expanded)."""

@@ -69,16 +69,19 @@ __device__ __forceinline__ void set_shape(const M3 &R, double a0, double a1, dou
 
 constexpr double kDecompEpsDev = 1e-10;                         // decomp_basis/data_type.h:129
 
+// One cell, LineSegment3D::dilate(offset) of segment p1-p2, by the 256 lanes of a workgroup: the body k_dilate and k_corridor_chain (frx_chain_kernel.hpp) share.
+// Returns the number of records written to out[cap_planes][6] (tangent planes in the reference's order, then the six planes of the local box), -1 when the local
+// box holds more than pcap points, -2 when the cell needs more than cap_planes records; the same value on every lane.  lds_out (LDS, or null) receives the same
+// records; C and d are the ellipsoid.  The caller's lanes must all have left any earlier use of sm (a barrier) before the call.
 // LDS (doubles): pts[pcap][3] | shape[32] (Cinv 0-8, d 9-11, scalar scratch) | box[6][6] | red[2 * 8] | then int: live[pcap], in0[pcap], cnt[257]
-__global__ __launch_bounds__(256) void k_dilate(DilateArgs a) {
+__device__ __forceinline__ int dilate_cell(cg::V3 p1, cg::V3 p2, cg::V3 bbox, double offset, const double *obs, int n_obs, int pcap, int cap_planes,
+                                           double *sm, double *out, double *lds_out, cg::M3 &C, cg::V3 &d_out) {
     using namespace cg;
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int seg = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    double *pts = sm, *shape = pts + (size_t)3 * a.pcap, *box = shape + 32, *red = box + 36;
-    int *live = (int *)(red + 16), *in0 = live + a.pcap, *cnt = in0 + a.pcap;
-    const V3 p1{a.p1[3 * seg], a.p1[3 * seg + 1], a.p1[3 * seg + 2]}, p2{a.p2[3 * seg], a.p2[3 * seg + 1], a.p2[3 * seg + 2]};
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    double *pts = sm, *shape = pts + (size_t)3 * pcap, *box = shape + 32, *red = box + 36;
+    int *live = (int *)(red + 16), *in0 = live + pcap, *cnt = in0 + pcap;
     // ---- local bounding box (line_segment.h:47-85) ----
-    const bool has_box = sqrt(a.bbox[0] * a.bbox[0] + a.bbox[1] * a.bbox[1] + a.bbox[2] * a.bbox[2]) != 0.0;
+    const bool has_box = sqrt(bbox.x * bbox.x + bbox.y * bbox.y + bbox.z * bbox.z) != 0.0;
     if (t == 0 && has_box) {
         V3 dir = sub(p2, p1); dir = scl(dir, 1.0 / nrm(dir));
         V3 h{dir.y, -dir.x, 0.0};
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(256) void k_dilate(DilateArgs a) {
         h = scl(h, 1.0 / nrm(h));
         const V3 v{dir.y * h.z - dir.z * h.y, dir.z * h.x - dir.x * h.z, dir.x * h.y - dir.y * h.x};
         const V3 nn[6] = {h, scl(h, -1.0), dir, scl(dir, -1.0), v, scl(v, -1.0)};
-        const V3 pp[6] = {add(p1, scl(h, a.bbox[1])), sub(p1, scl(h, a.bbox[1])), add(p2, scl(dir, a.bbox[0])), sub(p1, scl(dir, a.bbox[0])), add(p1, scl(v, a.bbox[2])), sub(p1, scl(v, a.bbox[2]))};
+        const V3 pp[6] = {add(p1, scl(h, bbox.y)), sub(p1, scl(h, bbox.y)), add(p2, scl(dir, bbox.x)), sub(p1, scl(dir, bbox.x)), add(p1, scl(v, bbox.z)), sub(p1, scl(v, bbox.z))};
         for (int k = 0; k < 6; k++) { box[6 * k] = nn[k].x; box[6 * k + 1] = nn[k].y; box[6 * k + 2] = nn[k].z; box[6 * k + 3] = pp[k].x; box[6 * k + 4] = pp[k].y; box[6 * k + 5] = pp[k].z; }
     }
     __syncthreads();
@@ -98,19 +101,19 @@ __global__ __launch_bounds__(256) void k_dilate(DilateArgs a) {
         return in;
     };
     // ---- candidate points, compacted in cloud order (thread t owns the contiguous chunk [t c, (t+1) c)) ----
-    const int chunk = (a.n_obs + 255) / 256, i0 = t * chunk, i1 = min(i0 + chunk, a.n_obs);
+    const int chunk = (n_obs + 255) / 256, i0 = t * chunk, i1 = min(i0 + chunk, n_obs);
     int mine = 0;
-    for (int i = i0; i < i1; i++) mine += inside_box(V3{a.obs[3 * i], a.obs[3 * i + 1], a.obs[3 * i + 2]}) ? 1 : 0;
+    for (int i = i0; i < i1; i++) mine += inside_box(V3{obs[3 * i], obs[3 * i + 1], obs[3 * i + 2]}) ? 1 : 0;
     cnt[t] = mine;
     __syncthreads();
     if (t == 0) { int s = 0; for (int k = 0; k < 256; k++) { const int c = cnt[k]; cnt[k] = s; s += c; } cnt[256] = s; }
     __syncthreads();
     const int M = cnt[256];
-    if (M > a.pcap) { if (t == 0) a.n_planes[seg] = -1; return; }
+    if (M > pcap) return -1;
     {
         int w = cnt[t];
         for (int i = i0; i < i1; i++) {
-            const V3 q{a.obs[3 * i], a.obs[3 * i + 1], a.obs[3 * i + 2]};
+            const V3 q{obs[3 * i], obs[3 * i + 1], obs[3 * i + 2]};
             if (inside_box(q)) { pts[3 * w] = q.x; pts[3 * w + 1] = q.y; pts[3 * w + 2] = q.z; w++; }
         }
     }
@@ -140,10 +143,10 @@ __global__ __launch_bounds__(256) void k_dilate(DilateArgs a) {
     auto publish_shape = [&](const M3 &Cinv) { for (int k = 0; k < 9; k++) shape[k] = Cinv.m[k]; };
     // ---- find_ellipsoid (line_segment.h:136-214) ----
     const double f = nrm(sub(p1, p2)) / 2;
-    double a0 = f + a.offset, a1 = f, a2 = f;
+    double a0 = f + offset, a1 = f, a2 = f;
     if (a0 > 0) { const double ratio = a1 / a0; a0 *= ratio; a1 *= ratio; a2 *= ratio; }
     const M3 Ri = rotation_from_direction(sub(p2, p1));
-    M3 Rf = Ri, C, Cinv;
+    M3 Rf = Ri, Cinv;
     const V3 d = scl(add(p1, p2), 0.5);
     set_shape(Ri, a0, a1, a2, C, Cinv);
     if (t == 0) { publish_shape(Cinv); shape[9] = d.x; shape[10] = d.y; shape[11] = d.z; }
@@ -187,27 +190,41 @@ __global__ __launch_bounds__(256) void k_dilate(DilateArgs a) {
     for (int i = t; i < M; i += 256) live[i] = 1;
     __syncthreads();
     int np = 0;
-    double *out = a.h_rec + (size_t)seg * a.cap_planes * 6;
     for (;;) {
         const int ic = argmin_live();
         if (ic < 0) break;
         const V3 c{pts[3 * ic], pts[3 * ic + 1], pts[3 * ic + 2]};
         V3 n = mul(Q, sub(c, d)); n = scl(n, 1.0 / nrm(n));        // ellipsoid.h:53-58
-        if (np >= a.cap_planes) { if (t == 0) a.n_planes[seg] = -2; return; }
-        if (t == 0) { out[6 * np] = n.x; out[6 * np + 1] = n.y; out[6 * np + 2] = n.z; out[6 * np + 3] = c.x; out[6 * np + 4] = c.y; out[6 * np + 5] = c.z; }
+        if (np >= cap_planes) return -2;
+        if (t == 0) {
+            out[6 * np] = n.x; out[6 * np + 1] = n.y; out[6 * np + 2] = n.z; out[6 * np + 3] = c.x; out[6 * np + 4] = c.y; out[6 * np + 5] = c.z;
+            if (lds_out) { lds_out[6 * np] = n.x; lds_out[6 * np + 1] = n.y; lds_out[6 * np + 2] = n.z; lds_out[6 * np + 3] = c.x; lds_out[6 * np + 4] = c.y; lds_out[6 * np + 5] = c.z; }
+        }
         np++;
         for (int i = t; i < M; i += 256) if (live[i] && !(n.x * (pts[3 * i] - c.x) + n.y * (pts[3 * i + 1] - c.y) + n.z * (pts[3 * i + 2] - c.z) < 0)) live[i] = 0;
         __syncthreads();
     }
     if (has_box) {
-        if (np + 6 > a.cap_planes) { if (t == 0) a.n_planes[seg] = -2; return; }
-        if (t < 36) out[6 * np + t] = box[t];
+        if (np + 6 > cap_planes) return -2;
+        if (t < 36) { out[6 * np + t] = box[t]; if (lds_out) lds_out[6 * np + t] = box[t]; }
         np += 6;
     }
-    if (t == 0) {
+    d_out = d;
+    return np;
+}
+
+__global__ __launch_bounds__(256) void k_dilate(DilateArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int seg = blockIdx.x;
+    const cg::V3 p1{a.p1[3 * seg], a.p1[3 * seg + 1], a.p1[3 * seg + 2]}, p2{a.p2[3 * seg], a.p2[3 * seg + 1], a.p2[3 * seg + 2]};
+    cg::M3 C; cg::V3 d;
+    const int np = dilate_cell(p1, p2, cg::V3{a.bbox[0], a.bbox[1], a.bbox[2]}, a.offset, a.obs, a.n_obs, a.pcap, a.cap_planes, sm, a.h_rec + (size_t)seg * a.cap_planes * 6, nullptr, C, d);
+    if (threadIdx.x == 0) {
         a.n_planes[seg] = np;
-        if (a.ell_C) for (int k = 0; k < 9; k++) a.ell_C[9 * seg + k] = C.m[k];
-        if (a.ell_d) { a.ell_d[3 * seg] = d.x; a.ell_d[3 * seg + 1] = d.y; a.ell_d[3 * seg + 2] = d.z; }
+        if (np >= 0) {
+            if (a.ell_C) for (int k = 0; k < 9; k++) a.ell_C[9 * seg + k] = C.m[k];
+            if (a.ell_d) { a.ell_d[3 * seg] = d.x; a.ell_d[3 * seg + 1] = d.y; a.ell_d[3 * seg + 2] = d.z; }
+        }
     }
 }
 

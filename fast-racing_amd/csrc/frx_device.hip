@@ -1,5 +1,5 @@
-// hipcc translation unit: the gfx950 stage kernels, the L-BFGS vector kernels, the corridor kernel and their launchers.
-// (The resident round kernel and the one-launch evaluation have translation units of their own - frx_device_round.hip, frx_device_eval.hip - so that the three
+// hipcc translation unit: the gfx950 stage kernels, the L-BFGS vector kernels and their launchers.
+// (The resident round kernel and the one-launch evaluation have translation units of their own - frx_device_round.hip, frx_device_eval.hip; the corridor kernels are in frx_device_chain.hip - so that the three
 // compile side by side: k_round's six instantiations alone take longer than everything else together.)
 #include <hip/hip_runtime.h>
 
@@ -9,7 +9,6 @@
 
 #include "frx_kernels.hpp"
 #include "frx_lbfgs_kernels.hpp"
-#include "frx_corridor_kernels.hpp"
 
 namespace frx {
 
@@ -134,19 +133,6 @@ __global__ __launch_bounds__(64) void k_clock_probe(double *out, unsigned long l
 }
 int launch_clock_probe(double *out, unsigned long long *stamps, int blocks, unsigned long long ticks, void *stream) {
     hipLaunchKernelGGL(k_clock_probe, dim3(blocks), dim3(64), 0, (hipStream_t)stream, out, stamps, ticks);
-    return (int)hipGetLastError();
-}
-
-size_t dilate_lds_bytes(int pcap) { return sizeof(double) * ((size_t)3 * pcap + 32 + 36 + 16) + sizeof(int) * ((size_t)2 * pcap + 257 + 3); }
-int launch_dilate(const DilateLaunch &d, void *stream) {
-    DilateArgs a;
-    a.p1 = d.p1; a.p2 = d.p2; a.obs = d.obs; a.bbox[0] = d.bbox[0]; a.bbox[1] = d.bbox[1]; a.bbox[2] = d.bbox[2]; a.offset = d.offset;
-    a.S = d.S; a.n_obs = d.n_obs; a.cap_planes = d.cap_planes; a.pcap = d.pcap;
-    a.n_planes = d.n_planes; a.h_rec = d.h_rec; a.ell_C = d.ell_C; a.ell_d = d.ell_d;
-    const size_t lds = dilate_lds_bytes(d.pcap);
-    hipError_t e = hipFuncSetAttribute((const void *)k_dilate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_dilate, dim3(d.S), dim3(256), lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

@@ -196,4 +196,17 @@ size_t dilate_lds_bytes(int pcap);
 int launch_clock_probe(double *out, unsigned long long *stamps, int blocks, unsigned long long ticks, void *stream);   // stamps [2 blocks]: shader cycles, 100 MHz ticks per block
 int launch_dilate(const DilateLaunch &d, void *stream);
 
+// ---- whole corridors on the device, one workgroup per path (frx_chain_kernel.hpp) ----
+struct ChainLaunch {
+    const int *path_off; const double *path, *obs;                 // device pointers: [n_paths + 1], [path_off[n_paths]][3], [n_obs][3]
+    double map_origin[3], map_res; int map_dim[3]; const signed char *map_cells;   // map_cells: device pointer or null (nothing blocks)
+    double bbox[3], map_height, max_seg;
+    int n_paths, n_obs, cap_polys, cap_planes, pcap;
+    double *h_slot; int *cell_planes, *n_polys, *status;           // [n_paths][cap_polys][cap_planes][6], [n_paths][cap_polys], [n_paths], [n_paths]
+};
+enum { CHAIN_PCAP = 4096, CHAIN_MAX_PLANES = 512 };                 // candidate points of a cell in LDS; the largest cap_planes whose records fit beside them
+size_t chain_lds_bytes(int pcap, int cap_planes);
+int launch_chain(const ChainLaunch &c, void *stream);
+int launch_map_blocked_pairs(const ChainLaunch &map_of, int n, const double *a, const double *b, int *out, void *stream);   // tests: only the map fields are read
+
 } // namespace frx

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/frx.h"
+#include "../../include/frx_debug.h"
 #include "frx_device.hpp"
 #include "frx_internal.hpp"
 
@@ -362,6 +363,137 @@ int frx_dilate_batch(int device, int n_seg, const double *p1, const double *p2, 
     for (int s = 0; s < n_seg; s++)
         if (n_planes[s] < 0) return frx::set_error(FRX_ERR_CAPACITY, n_planes[s] == -1 ? "frx_dilate_batch: more than 4096 obstacle points inside one cell's local box"
                                                                                          : "frx_dilate_batch: more half-spaces than cap_planes");
+    return FRX_OK;
+}
+
+// ---- whole corridors for a batch of paths (frx_chain_kernel.hpp): the device form is one launch, the blocking form is that launch between an upload and a
+// host compaction of the slotted records into the CSR frx_problem_create_from_h takes ----
+static int chain_launch_args(const char *who, int n_paths, int n_obs, const double *bbox, double max_seg, const frx_voxel_map *map, int cap_polys, int cap_planes) {
+    if (n_paths < 1 || n_obs < 0 || !bbox || cap_polys < 1) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null or out-of-range argument");
+    if (cap_planes < 8) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": cap_planes < 8 (six box planes, floor and ceiling)");
+    if (cap_planes > frx::CHAIN_MAX_PLANES) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": cap_planes > " + std::to_string((int)frx::CHAIN_MAX_PLANES) + " (a cell's records stay in LDS)");
+    if (!(max_seg > 0)) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": max_seg must be above 0");
+    if (map && (!(map->res > 0) || map->dim[0] <= 0 || map->dim[1] <= 0 || map->dim[2] <= 0 || !map->cells))
+        return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": the map needs cells, res > 0 and dim > 0 on all three axes");
+    if (map && double(map->dim[0]) * map->dim[1] * map->dim[2] > 2.0e9) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": more than 2e9 map cells");
+    if ((double)n_paths * cap_polys > 2.0e9) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": n_paths x cap_polys exceeds 2e9");
+    return FRX_OK;
+}
+
+int frx_corridor_generate_batch_device(int n_paths, const int *path_off_dev, const double *path_dev, int n_obs, const double *obs_dev, const double *bbox,
+                                       double map_height, double max_seg, const frx_voxel_map *map, int cap_polys, int cap_planes, double *h_slot_dev,
+                                       int *cell_planes_dev, int *n_polys_dev, int *status_dev, void *hip_stream) {
+    const int rc = chain_launch_args("frx_corridor_generate_batch_device", n_paths, n_obs, bbox, max_seg, map, cap_polys, cap_planes);
+    if (rc != FRX_OK) return rc;
+    if (!path_off_dev || !path_dev || (n_obs && !obs_dev) || !h_slot_dev || !cell_planes_dev || !n_polys_dev || !status_dev)
+        return frx::set_error(FRX_ERR_INVALID_ARG, "frx_corridor_generate_batch_device: null argument");
+    frx::ChainLaunch L;
+    L.path_off = path_off_dev; L.path = path_dev; L.obs = obs_dev;
+    for (int i = 0; i < 3; i++) { L.map_origin[i] = map ? map->origin[i] : 0.0; L.map_dim[i] = map ? map->dim[i] : 0; L.bbox[i] = bbox[i]; }
+    L.map_res = map ? map->res : 1.0; L.map_cells = map ? map->cells : nullptr;
+    L.map_height = map_height; L.max_seg = max_seg;
+    L.n_paths = n_paths; L.n_obs = n_obs; L.cap_polys = cap_polys; L.cap_planes = cap_planes; L.pcap = frx::CHAIN_PCAP;
+    L.h_slot = h_slot_dev; L.cell_planes = cell_planes_dev; L.n_polys = n_polys_dev; L.status = status_dev;
+    const hipError_t e = (hipError_t)frx::launch_chain(L, hip_stream);
+    if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string("frx_corridor_generate_batch_device: ") + hipGetErrorString(e));
+    return FRX_OK;
+}
+
+int frx_corridor_generate_batch(int device, int n_paths, const int *path_off, const double *path, int n_obs, const double *obs, const double *bbox, double map_height,
+                                double max_seg, const frx_voxel_map *map, int cap_polys, int cap_planes, int *n_polys, int *status, int cap_rec, int *n_rec,
+                                int *h_off, double *h_rec) {
+    const char *who = "frx_corridor_generate_batch";
+    int rc = chain_launch_args(who, n_paths, n_obs, bbox, max_seg, map, cap_polys, cap_planes);
+    if (rc != FRX_OK) return rc;
+    if (!path_off || !path || (n_obs && !obs) || !n_polys || !status || !n_rec || !h_off || !h_rec || cap_rec < 0)
+        return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null or out-of-range argument");
+    if (path_off[0] < 0) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": path_off[0] < 0");
+    for (int b = 0; b < n_paths; b++) {
+        if (path_off[b + 1] < path_off[b]) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": path_off is not monotone at path " + std::to_string(b));
+        if (path_off[b + 1] - path_off[b] < 2) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": path " + std::to_string(b) + " has fewer than 2 points");
+    }
+    if (frx_device_count() < 1) return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    DeviceGuard restore_device;
+    if (hipSetDevice(device) != hipSuccess) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": device ordinal out of range");
+    const size_t n_pts = (size_t)path_off[n_paths], n_cells = map ? (size_t)map->dim[0] * map->dim[1] * map->dim[2] : 0;
+    const size_t slots = (size_t)n_paths * cap_polys, cell_bytes = sizeof(double) * 6 * (size_t)cap_planes;
+    int *d_off = nullptr, *d_cp = nullptr, *d_np = nullptr, *d_st = nullptr; double *d_path = nullptr, *d_obs = nullptr, *d_slot = nullptr; signed char *d_cells = nullptr;
+    auto cleanup = [&]() { for (void *q : {(void *)d_off, (void *)d_cp, (void *)d_np, (void *)d_st, (void *)d_path, (void *)d_obs, (void *)d_slot, (void *)d_cells}) if (q) (void)hipFree(q); };
+    if (hipMalloc((void **)&d_off, 4 * (size_t)(n_paths + 1)) != hipSuccess || hipMalloc((void **)&d_cp, 4 * slots) != hipSuccess ||
+        hipMalloc((void **)&d_np, 4 * (size_t)n_paths) != hipSuccess || hipMalloc((void **)&d_st, 4 * (size_t)n_paths) != hipSuccess ||
+        hipMalloc((void **)&d_path, 24 * n_pts) != hipSuccess || hipMalloc((void **)&d_obs, 24 * (size_t)std::max(n_obs, 1)) != hipSuccess ||
+        hipMalloc((void **)&d_slot, cell_bytes * slots) != hipSuccess || (map && hipMalloc((void **)&d_cells, n_cells) != hipSuccess)) {
+        cleanup();
+        return frx::set_error(FRX_ERR_ALLOC, std::string(who) + ": device buffers (" + std::to_string(cell_bytes * slots) + " bytes of record slots)");
+    }
+    hipError_t e = hipMemcpy(d_off, path_off, 4 * (size_t)(n_paths + 1), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_path, path, 24 * n_pts, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_obs) e = hipMemcpy(d_obs, obs, 24 * (size_t)n_obs, hipMemcpyHostToDevice);
+    if (e == hipSuccess && map) e = hipMemcpy(d_cells, map->cells, n_cells, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cleanup(); return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+    frx_voxel_map dmap;
+    if (map) { dmap = *map; dmap.cells = d_cells; }
+    rc = frx_corridor_generate_batch_device(n_paths, d_off, d_path, n_obs, d_obs, bbox, map_height, max_seg, map ? &dmap : nullptr, cap_polys, cap_planes, d_slot, d_cp,
+                                            d_np, d_st, nullptr);
+    if (rc != FRX_OK) { cleanup(); return rc; }
+    std::vector<int> cp(slots);
+    e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipMemcpy(n_polys, d_np, 4 * (size_t)n_paths, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(status, d_st, 4 * (size_t)n_paths, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(cp.data(), d_cp, 4 * slots, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { cleanup(); return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+    // compaction: the cells of the paths that finished, in path order; of a cell's slot only the widest cell's share of every row of the path is fetched
+    long long need = 0;
+    for (int b = 0; b < n_paths; b++) for (int c = 0; c < n_polys[b]; c++) need += cp[(size_t)b * cap_polys + c];
+    *n_rec = (int)std::min<long long>(need, 0x7fffffffLL);
+    if (need > cap_rec) { cleanup(); return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": " + std::to_string(need) + " records, cap_rec is " + std::to_string(cap_rec)); }
+    std::vector<double> stage;
+    int poly = 0, used = 0;
+    h_off[0] = 0;
+    for (int b = 0; b < n_paths && e == hipSuccess; b++) {
+        const int *k = &cp[(size_t)b * cap_polys];
+        const int nc = n_polys[b];
+        if (nc < 1) continue;
+        const size_t widest = (size_t)*std::max_element(k, k + nc), row = sizeof(double) * 6 * widest;
+        stage.resize(6 * widest * nc);
+        e = hipMemcpy2D(stage.data(), row, d_slot + (size_t)b * cap_polys * cap_planes * 6, cell_bytes, row, (size_t)nc, hipMemcpyDeviceToHost);
+        for (int c = 0; c < nc && e == hipSuccess; c++) {
+            std::memcpy(h_rec + 6 * (size_t)used, stage.data() + 6 * widest * c, sizeof(double) * 6 * (size_t)k[c]);
+            used += k[c];
+            h_off[++poly] = used;
+        }
+    }
+    cleanup();
+    if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return FRX_OK;
+}
+
+// Tests: the device's sight line (map_blocked, frx_chain_kernel.hpp) on n_pairs pairs of points, host buffers in and out; out[i] = 0 / 1 as frx_map_is_blocked.
+int frx_debug_map_blocked_device(int device, const frx_voxel_map *map, int n_pairs, const double *a, const double *b, int *out) {
+    if (!map || !map->cells || !(map->res > 0) || map->dim[0] <= 0 || map->dim[1] <= 0 || map->dim[2] <= 0 || n_pairs < 1 || !a || !b || !out)
+        return frx::set_error(FRX_ERR_INVALID_ARG, "frx_debug_map_blocked_device: null or out-of-range argument");
+    if (frx_device_count() < 1) return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    DeviceGuard restore_device;
+    if (hipSetDevice(device) != hipSuccess) return frx::set_error(FRX_ERR_INVALID_ARG, "frx_debug_map_blocked_device: device ordinal out of range");
+    const size_t n_cells = (size_t)map->dim[0] * map->dim[1] * map->dim[2];
+    double *d_a = nullptr, *d_b = nullptr; int *d_out = nullptr; signed char *d_cells = nullptr;
+    auto cleanup = [&]() { for (void *q : {(void *)d_a, (void *)d_b, (void *)d_out, (void *)d_cells}) if (q) (void)hipFree(q); };
+    if (hipMalloc((void **)&d_a, 24 * (size_t)n_pairs) != hipSuccess || hipMalloc((void **)&d_b, 24 * (size_t)n_pairs) != hipSuccess ||
+        hipMalloc((void **)&d_out, 4 * (size_t)n_pairs) != hipSuccess || hipMalloc((void **)&d_cells, n_cells) != hipSuccess) {
+        cleanup();
+        return frx::set_error(FRX_ERR_ALLOC, "frx_debug_map_blocked_device: device buffers");
+    }
+    hipError_t e = hipMemcpy(d_a, a, 24 * (size_t)n_pairs, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_b, b, 24 * (size_t)n_pairs, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_cells, map->cells, n_cells, hipMemcpyHostToDevice);
+    frx::ChainLaunch L{};
+    for (int i = 0; i < 3; i++) { L.map_origin[i] = map->origin[i]; L.map_dim[i] = map->dim[i]; }
+    L.map_res = map->res; L.map_cells = d_cells;
+    if (e == hipSuccess) e = (hipError_t)frx::launch_map_blocked_pairs(L, n_pairs, d_a, d_b, d_out, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string("frx_debug_map_blocked_device: ") + hipGetErrorString(e));
     return FRX_OK;
 }
 

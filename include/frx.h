@@ -156,6 +156,33 @@ int frx_corridor_generate(int n_path, const double *path, int n_obs, const doubl
 int frx_dilate_batch(int device, int n_seg, const double *p1, const double *p2, const double *bbox, int n_obs, const double *obs, double offset,
                      int cap_planes, int *n_planes, double *h_rec, double *ell_C, double *ell_d);
 
+/* Whole corridors on the DEVICE for a batch of independent paths against one obstacle cloud and one voxel map (csrc/frx_chain_kernel.hpp): what
+ * frx_corridor_generate computes for one path with blocked = frx_map_is_blocked, one 256-thread workgroup per path walking that path's greedy chain
+ * (segment end by length and sight line, the cell as frx_dilate_batch forms it with offset 0, exit index, floor and ceiling, restart at 4/5 of the in-cell
+ * span).  path_off[n_paths + 1] = first point of every path in path[3 path_off[n_paths]]; obs as frx_dilate_batch takes it; map = NULL: nothing blocks.
+ * A path's result depends on that path, the cloud and the map alone and is bit-identical run to run, in either form and in any batch.
+ * status[b]: 0 = ok; 1 = a cell's local box holds more than 4096 cloud points; 2 = a cell needs more than cap_planes records (floor and ceiling included);
+ * 3 = more than cap_polys cells.  A path with a non-zero status has n_polys[b] = 0 and does not disturb the others; the call still returns FRX_OK.
+ *   frx_corridor_generate_batch          blocking, host pointers (map->cells on the host); uploads paths, cloud and cells, then compacts the slots into ONE
+ *                                        CSR over all paths in path order: h_off[sum(n_polys) + 1] (room for n_paths x cap_polys + 1 entries), h_rec[6 cap_rec],
+ *                                        floor and ceiling last in each cell - the layout frx_problem_create_from_h takes with coarse_n = n_polys.
+ *                                        *n_rec = records needed; FRX_ERR_CAPACITY only when that exceeds cap_rec (n_polys and status are valid then).
+ *   frx_corridor_generate_batch_device   ONE launch on hip_stream of the current device: no copy, no synchronisation, no allocation (capturable).  All array
+ *                                        arguments but bbox are device pointers, map is a host struct whose cells point to device memory.  Slotted outputs:
+ *                                        h_slot[n_paths][cap_polys][cap_planes][6], cell_planes[n_paths][cap_polys] (records of each cell), n_polys, status;
+ *                                        slots beyond a path's cells are left untouched.  The caller vouches for path_off (every path >= 2 points, monotone).
+ * FRX_ERR_INVALID_ARG (reported before a device is looked for): NULL arguments, n_paths < 1, a path with fewer than 2 points, non-monotone path_off,
+ * cap_polys < 1, cap_planes < 8 or > 512 (a cell's records stay in LDS beside its 4096 candidate points), max_seg not above 0, a map with res <= 0 or a
+ * dim <= 0.  FRX_ERR_NO_DEVICE without a device.  Not built (csrc/frx_chain_kernel.hpp): a spatial index over the cloud, and a split of one path's
+ * cloud scans over several workgroups - one path runs on one compute unit. */
+struct frx_voxel_map;                                                 /* defined below, with the path-search front end */
+int frx_corridor_generate_batch(int device, int n_paths, const int *path_off, const double *path, int n_obs, const double *obs, const double *bbox,
+                                double map_height, double max_seg, const struct frx_voxel_map *map, int cap_polys, int cap_planes, int *n_polys, int *status,
+                                int cap_rec, int *n_rec, int *h_off, double *h_rec);
+int frx_corridor_generate_batch_device(int n_paths, const int *path_off_dev, const double *path_dev, int n_obs, const double *obs_dev, const double *bbox,
+                                       double map_height, double max_seg, const struct frx_voxel_map *map, int cap_polys, int cap_planes, double *h_slot_dev,
+                                       int *cell_planes_dev, int *n_polys_dev, int *status_dev, void *hip_stream);
+
 /* Result wire format.  frx_traj_to_msg fills the array fields of quadrotor_msgs/PolynomialTrajectory the way
  * MavGlobalPlanner::traj2msg does (se3_planner.cpp:31-58): per piece 6 duration-normalised coefficients per axis, highest
  * power first (Piece::normalizePosCoeffMat, trajectory.hpp:131-141), time[] = durations, order[] = 5 (num_order = 5,

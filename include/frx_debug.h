@@ -108,6 +108,10 @@ int frx_debug_compact_from_history(int m, int n, int hs, int bound, int newest, 
  * handle, 0 returns to the library's rule.  Rows do not depend on it. */
 int frx_debug_set_clear_chunk(frx_problem *p, int points);
 
+/* Tests: the sight line of frx_corridor_generate_batch (map_blocked, fast-racing_amd/csrc/frx_chain_kernel.hpp) run on the device for n_pairs pairs of points
+ * a[3 n_pairs], b[3 n_pairs] (host buffers; the map's cells are uploaded): out[i] = 0 / 1, to be compared with frx_map_is_blocked verdict for verdict. */
+int frx_debug_map_blocked_device(int device, const frx_voxel_map *map, int n_pairs, const double *a, const double *b, int *out);
+
 /* Diagnostic (bench): the shader clock the device sustains under a latency-bound FP64 load (one lone wave per CU on every CU, a dependent FMA chain for `ms`
  * milliseconds): shader cycles per tick of the constant 100 MHz counter, as MHz - minimum, mean and maximum over the CUs' workgroups.  A round of the resident kernel
  * is a chain of dependent instructions: its time is cycles / this clock, which is what differs between the boxes of a pool running the same code object. */
