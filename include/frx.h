@@ -152,7 +152,9 @@ int frx_corridor_generate(int n_path, const double *path, int n_obs, const doubl
  * the candidate points compacted in cloud order into LDS, every step of find_ellipsoid / find_polyhedron (decomp_util line_segment.h:136-214,
  * decomp_base.h:63-83) = an arg-min and a filter over them on 256 lanes.  p1, p2: n_seg x 3; h_rec: n_seg x cap_planes x 6 (outer normal, point),
  * n_planes[s] records of it valid (tangent planes in the reference's order, then the six planes of the local box); ell_C (n_seg x 9),
- * ell_d (n_seg x 3) may be NULL.  FRX_ERR_CAPACITY when a cell's local box holds more than 4096 points or needs more than cap_planes planes. */
+ * ell_d (n_seg x 3) may be NULL.  FRX_ERR_CAPACITY when a cell's local box holds more than 4096 points or needs more than cap_planes planes:
+ * n_planes[s] is then -1 (points) or -2 (planes) for every such segment, whose rows of h_rec, ell_C and ell_d are undefined; every other segment's
+ * n_planes and rows are valid and are what the call gives without the refused segments. */
 int frx_dilate_batch(int device, int n_seg, const double *p1, const double *p2, const double *bbox, int n_obs, const double *obs, double offset,
                      int cap_planes, int *n_planes, double *h_rec, double *ell_C, double *ell_d);
 

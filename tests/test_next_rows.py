@@ -1,6 +1,11 @@
 """SURVEY.md §8f "next" rows built so far: f1 (H -> V vertex enumeration) and f3 (result wire format + its consumer)."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_vertex_enumeration_matches_generator_and_reference(frx, sc, ob):
@@ -115,6 +120,9 @@ def test_line_segment_cell_matches_reference_decomp(frx, ob, seed):
     # every obstacle inside the local box is outside (or on) some tangent plane; the segment itself is inside the cell
     for q in (p1, p2, 0.5 * (p1 + p2)):
         assert np.all(np.einsum("dk,dk->k", H[:3], q[:, None] - H[3:]) <= 1e-9)
+    from dilate_reference import unsafe_points                    # (tests/dilate_reference.py: the box filter restated, nothing of the library)
+    deep, in_ellipsoid, seg = unsafe_points(H, Cm, d, p1, p2, bbox, obs, tol=1e-9)
+    assert deep == 0 and in_ellipsoid == 0 and seg <= 1e-9, (deep, in_ellipsoid, seg)
 
 
 def _scene(sc, seed, n_gates=4, n_obs=600):
