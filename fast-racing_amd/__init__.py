@@ -74,7 +74,7 @@ ABI_SYMBOLS = [
 DEBUG_SYMBOLS = [
     "frx_debug_trace", "frx_resident_profile", "frx_debug_direction_log", "frx_debug_direction_log_read", "frx_debug_set_resident_retry",
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
-    "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
+    "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
     "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device",
 ]
 
@@ -141,6 +141,7 @@ def lib():
         L.frx_debug_penalty_kernel.argtypes = [C.c_void_p]
         L.frx_debug_mailbox_numa.argtypes = [C.c_void_p, C.c_void_p]
         L.frx_debug_profile_eval_cluster.argtypes = [C.c_void_p, _dp, C.c_void_p]
+        L.frx_debug_profile_eval_tail.argtypes = [C.c_void_p, _dp, C.c_void_p]
         L.frx_multi_create.argtypes = [C.POINTER(FrxConfig), C.c_int, C.c_void_p, C.c_int, _ip, _dp, _dp, _ip, _dp, _ip, _dp, C.POINTER(C.c_void_p)]
         L.frx_multi_destroy.argtypes = [C.c_void_p]
         L.frx_multi_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
@@ -753,6 +754,12 @@ class Problem:
         """Shader-clock stamps of cluster 0 during one evaluation in the one-launch form (frx_debug.h: frx_debug_profile_eval_cluster)."""
         out = np.zeros(64, np.int64)
         _check(lib().frx_debug_profile_eval_cluster(self.h, np.ascontiguousarray(x, dtype=np.float64), out.ctypes.data))
+        return out
+
+    def profile_eval_tail(self, x):
+        """The same with the stamps of the evaluation's tail in [64..68] (frx_debug.h: frx_debug_profile_eval_tail); 100 MHz ticks from [40] on."""
+        out = np.zeros(80, np.int64)
+        _check(lib().frx_debug_profile_eval_tail(self.h, np.ascontiguousarray(x, dtype=np.float64), out.ctypes.data))
         return out
 
     def set_eval_fused(self, on: bool):

@@ -209,6 +209,8 @@ struct NumaScope {
     ~NumaScope() { if (active) (void)pthread_setaffinity_np(pthread_self(), sizeof(saved), &saved); }
 };
 
+constexpr int FRX_STAMP_SLOTS = 80;                         // words of frx_problem::d_stamps
+
 struct frx_problem {
     frx_config cfg;
     int device = 0, B = 0, P = 0, Pc = 0, NX = 0, Kmax = 0, maxN = 0, maxCN = 0, sumKfine = 0;
@@ -223,7 +225,7 @@ struct frx_problem {
     DevBuf<double> d_head, d_tail, d_hblk, d_vrec;
     // device work space
     DevBuf<double> d_x, d_f, d_g, d_T, d_C, d_band, d_out20;
-    DevBuf<long long> d_stamps;
+    DevBuf<long long> d_stamps;                             // FRX_STAMP_SLOTS words (0..63 as ever; 64.. the tail of the one-launch evaluation, frx_debug_profile_eval_tail)
     DevBuf<double> d_pcrw;
     DevBuf<double> d_wq;                                    // [P][4]: per waypoint {|xi|^2, sum_a V_a xi_a^2}, forward map -> adjoint of the same evaluation
     // pinned staging
@@ -668,7 +670,7 @@ int frx_problem_set_solver(frx_problem *p, int solver) {
 int frx_profile_phases(frx_problem *p, const double *x, long long *out32) {
     if (!p || !x || !out32) return fail(FRX_ERR_INVALID_ARG, "null argument");
     HIP_TRY(hipSetDevice(p->device));
-    if (!p->d_stamps.p) HIP_TRY(p->d_stamps.alloc(64));
+    if (!p->d_stamps.p) HIP_TRY(p->d_stamps.alloc(FRX_STAMP_SLOTS));
     HIP_TRY(hipMemset(p->d_stamps.p, 0, 64 * sizeof(long long)));
     std::vector<double> f(p->B), g(p->NX);
     int rc = frx_objective_eval(p, x, f.data(), g.data());          // warm
@@ -683,12 +685,12 @@ int frx_profile_phases(frx_problem *p, const double *x, long long *out32) {
 
 // Diagnostic: one evaluation at x in the one-launch form with cycle stamps of cluster 0 (forward map 0..12 and adjoint 16..31 as frx_profile_phases; 40..43 the leader's entry,
 // end of the forward map, end of the adjoint, end; 44..48 wave 0 of the first member: entry, gate seen, granules staged, samples done, partials out).
-int frx_debug_profile_eval_cluster(frx_problem *p, const double *x, long long *out64) {
-    if (!p || !x || !out64) return fail(FRX_ERR_INVALID_ARG, "null argument");
+static int profile_eval_cluster(frx_problem *p, const double *x, long long *out, int first, int n) {
+    if (!p || !x || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
     if (!p->eval_fused) return fail(FRX_ERR_INVALID_ARG, "the one-launch evaluation does not apply to this handle");
     HIP_TRY(hipSetDevice(p->device));
-    if (!p->d_stamps.p) HIP_TRY(p->d_stamps.alloc(64));
-    HIP_TRY(hipMemset(p->d_stamps.p, 0, 64 * sizeof(long long)));
+    if (!p->d_stamps.p) HIP_TRY(p->d_stamps.alloc(FRX_STAMP_SLOTS));
+    HIP_TRY(hipMemset(p->d_stamps.p, 0, FRX_STAMP_SLOTS * sizeof(long long)));
     std::vector<double> f(p->B), g(p->NX);
     int rc = frx_objective_eval(p, x, f.data(), g.data());          // warm
     if (rc != FRX_OK) return rc;
@@ -696,9 +698,13 @@ int frx_debug_profile_eval_cluster(frx_problem *p, const double *x, long long *o
     rc = frx_objective_eval(p, x, f.data(), g.data());
     p->dp.stamps = nullptr; p->eval_fused_stamps = 0;
     if (rc != FRX_OK) return rc;
-    HIP_TRY(hipMemcpy(out64, p->d_stamps.p, 64 * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, p->d_stamps.p + first, n * sizeof(long long), hipMemcpyDeviceToHost));
     return FRX_OK;
 }
+int frx_debug_profile_eval_cluster(frx_problem *p, const double *x, long long *out64) { return profile_eval_cluster(p, x, out64, 0, 64); }
+// The same evaluation with the stamps of its tail behind the first 64: out80[64..68] = wave 0 behind the barrier that follows the knot adjoint, wave 0's last gradient
+// store issued, axis wave 1's last store issued, thread 0 has the verdict, thread 0 has issued `done` (100 MHz counter, as 40..48).
+int frx_debug_profile_eval_tail(frx_problem *p, const double *x, long long *out80) { return profile_eval_cluster(p, x, out80, 0, FRX_STAMP_SLOTS); }
 
 // Diagnostic (tests, tuning): drives k_lbfgs_pre alone.  `iters` successive accepted steps on random (x, g) sequences of
 // length n for B candidates; after each the device search direction is compared with a plain host two-loop recursion over
@@ -1623,7 +1629,7 @@ static int optimize_resident(frx_problem *p, const frx_lbfgs_params &pm, double 
     const bool want_stamps = want_prof && std::getenv("FRX_RESIDENT_PROF")[0] != '2';   // FRX_RESIDENT_PROF=2: segment times only (the stamps' stores perturb what they measure)
     if (want_prof && !want_stamps && p->d_stamps.p) HIP_TRY(hipMemsetAsync(p->d_stamps.p, 0, 64 * sizeof(long long), p->stream));
     if (want_stamps) {                                                                // phase stamps of candidate 0's forward / adjoint bodies (last evaluation)
-        if (!p->d_stamps.p) HIP_TRY(p->d_stamps.alloc(64));
+        if (!p->d_stamps.p) HIP_TRY(p->d_stamps.alloc(FRX_STAMP_SLOTS));
         HIP_TRY(hipMemsetAsync(p->d_stamps.p, 0, 64 * sizeof(long long), p->stream));
         p->dp.stamps = p->d_stamps.p;
     }
@@ -1837,7 +1843,7 @@ static int optimize_resident(frx_problem *p, const frx_lbfgs_params &pm, double 
     if (want_prof) {
         p->rprof.resize((size_t)S * (G + 1) * 16 + 32);                                // [S][G][16] segment sums, [S][16] host-wait histogram; the last 32 words: the bodies' cycle stamps
         HIP_TRY(hipMemcpy(p->rprof.data(), p->d_rprof.p, sizeof(unsigned long long) * (size_t)S * (G + 1) * 16, hipMemcpyDeviceToHost));
-        if (!p->d_stamps.p) { HIP_TRY(p->d_stamps.alloc(64)); HIP_TRY(hipMemset(p->d_stamps.p, 0, 64 * sizeof(long long))); }
+        if (!p->d_stamps.p) { HIP_TRY(p->d_stamps.alloc(FRX_STAMP_SLOTS)); HIP_TRY(hipMemset(p->d_stamps.p, 0, 64 * sizeof(long long))); }
         HIP_TRY(hipMemcpy(p->rprof.data() + (size_t)S * (G + 1) * 16, p->d_stamps.p + (rl.stamp_round > 0 ? 32 : 0), 32 * sizeof(long long), hipMemcpyDeviceToHost));   // the last evaluation's stamps, or those of evaluation FRX_RESIDENT_STAMP_ROUND
     }
     for (int q = 0; q < Bsel; q++) {                                                  // (a take-over counts its own candidates, not the per-stage part's failures)

@@ -13,8 +13,10 @@ namespace frx {
 
 static bool eval_argp() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_ARGPTR"); return !(e && e[0] == '0'); }(); return on; }   // FRX_EVAL_ARGPTR=0: the by-value form (A/B)
 static bool eval_early_t() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_EARLY_T"); return !(e && e[0] == '0'); }(); return on; }   // FRX_EVAL_EARLY_T=0: the staged-durations form (A/B)
+static bool eval_tail() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_TAIL"); return !(e && e[0] == '0'); }(); return on; }   // FRX_EVAL_TAIL=0: f and `done` behind a barrier and a status trip at the kernel's end (A/B; with the two switches above at their defaults only)
 // the instantiation the launcher takes: argument pointer (or not) x early durations (or not)
 static const void *eval_fn() {
+    if (!eval_tail() && eval_argp() && eval_early_t()) return (const void *)k_eval_cluster<true, true, false>;
     return eval_argp() ? (eval_early_t() ? (const void *)k_eval_cluster<true, true> : (const void *)k_eval_cluster<true, false>)
                        : (eval_early_t() ? (const void *)k_eval_cluster<false, true> : (const void *)k_eval_cluster<false, false>);
 }
@@ -69,7 +71,8 @@ int launch_eval_cluster(const LaunchGeom &g, int B, const void *args_host, const
     const dim3 grid(8 * g.ev_G * ((B + 7) / 8));
     const bool et = eval_early_t();
     if (eval_argp() && args_dev) {
-        if (et) hipLaunchKernelGGL((k_eval_cluster<true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+        if (et && !eval_tail()) hipLaunchKernelGGL((k_eval_cluster<true, true, false>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+        else if (et) hipLaunchKernelGGL((k_eval_cluster<true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
         else hipLaunchKernelGGL((k_eval_cluster<true, false>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
     } else {
         if (et) hipLaunchKernelGGL((k_eval_cluster<false, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, *(const EvalClusterArgs *)args_host, c);

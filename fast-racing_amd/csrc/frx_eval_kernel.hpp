@@ -18,9 +18,15 @@
 // (backward_knot_wsp64), whose gradient differs from the stage kernel's in the last bits (<= 1e-11 relative, tests/test_gpu_parity.py).
 //
 // Tags instead of zeroed buffers: the launch is captured in hipGraphs (bench.py replays one), so nothing on the host may run between two of them.  Every
-// cluster keeps the tag of its last COMPLETED evaluation in device memory (`done`); an evaluation uses tag = done + 1 for its flag and its granules, and the
-// leader stores it back as its very last action - behind the arrival of every partial, hence behind every member's read of `done` (a member without a task
-// reads nothing and leaves).  Launches on one stream do not overlap, so no workgroup ever sees a tag of the future.
+// cluster keeps the tag of its last COMPLETED evaluation in device memory (`done`); an evaluation uses tag = done + 1 for its flag and its granules, and thread 0
+// of the leader stores it back from inside the adjoint, next to f (EvalTail, frx_kernels.hpp).  That store is behind the workgroup barrier that follows the knot
+// adjoint, and every lane that polls the partials is in front of that barrier: `done` moves behind the arrival of every partial, hence behind every member's read
+// of it (a member without a task reads nothing and leaves).  Nothing else orders on `done` within a launch - the axis waves' gradient stores that are still in
+// flight when it leaves belong to the same kernel, and the next reader of either is a later launch.  Launches on one stream do not overlap, so no workgroup
+// ever sees a tag of the future.  The verdict - did a wait of this leader end without its partials - comes out of a word of the leader's LDS that the polling
+// lanes set next to their CAS on the global word; a word left by an EARLIER launch is caught at entry, and a code another cluster's leader sets during this launch
+// concerns that cluster's f alone (it is NaN, and the host word carries the code).  The leader's tail therefore has no load and no barrier: f, `done` and the
+// gradient's last stores are in flight together (the form before: FRX_EVAL_TAIL=0, 0.64 us between wave 0's last store and `done` on the stamps).
 // Every spin is bounded (EvalClusterArgs::timeout_ticks); an expired wait records RK_ERR_PHASE / RK_ERR_ARRIVE in `status` and the candidate's f becomes NaN.
 // Residency: a leader waits for members of the SAME launch, so all of a cluster's workgroups have to get a CU.  Blocks are dispatched in index order and a
 // cluster's blocks are 8 apart within one group of 8 G consecutive blocks (the XCD mapping of k_round), so the resident blocks of a launch always contain
@@ -78,7 +84,9 @@ template <class F> struct EvalEarlySync {
     const F &f; long long *st; bool steps;
     __device__ __forceinline__ bool sync() const { return f(); }
 };
-template <bool ARGP, bool ET>
+// TAIL (the default; FRX_EVAL_TAIL=0 takes the other form, A/B): thread 0 of the leader stores f and `done` inside the adjoint, right behind the objective's sum
+// (EvalTail, frx_kernels.hpp); otherwise behind a workgroup barrier and a load of the global status word at the kernel's end, as until now.
+template <bool ARGP, bool ET, bool TAIL = true>
 __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::conditional<ARGP, const EvalClusterArgs *__restrict__, EvalClusterArgs>::type arg, EvalCallArgs call) {
     const EvalClusterArgs &a = [&]() -> const EvalClusterArgs & { if constexpr (ARGP) return *arg; else return arg; }();
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -87,7 +95,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     if (k >= a.dp.B) return;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int c = k;
-    // (diagnostic, frx_debug_profile_eval_cluster: cycle stamps of cluster 0 - 40..43 the leader: entry, forward map done, adjoint done, end; 44..48 wave 0 of member 1, see penalty_wave_ll - these in ticks of the 100 MHz counter all workgroups share; 49: the leader's shader clock at entry, the origin of the bodies' own stamps 0..31)
+    // (diagnostic, frx_debug_profile_eval_cluster: cycle stamps of cluster 0 - 40..43 the leader: entry, forward map done, adjoint done, end; 64..68 its tail, see EvalTail; 44..48 wave 0 of member 1, see penalty_wave_ll - these in ticks of the 100 MHz counter all workgroups share; 49: the leader's shader clock at entry, the origin of the bodies' own stamps 0..31)
     if (a.dp.stamps && k == 0 && wg == 0 && t == 0) { a.dp.stamps[40] = (long long)wall_clock64(); a.dp.stamps[49] = (long long)__builtin_readcyclecounter(); }
     unsigned *flag = a.words + (size_t)k * 64, *done = flag + 32;
     const int p0 = a.dp.poff[c], N = a.dp.poff[c + 1] - p0;
@@ -118,6 +126,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     // the members' four waves had nothing to do for the first 8 us of the launch.  The leader sends nothing; its XCD goes into the gate word at ENTRY (the members look at
     // it when their partials leave, microseconds later; not there yet counts as "elsewhere": write-through).
     double *ctl = sm + L.ctl, *ev = sm + L.ev;
+    const lds_vuptr verdict = (lds_vuptr)(unsigned *)sm;                              // (leader) a wait for the penalty partials ended without them: EvalTail.  Zeroed in front of the forward map's barriers
     ResidentOps ro;
     ro.xs = sm + L.xs; ro.vs = sm + L.vs; ro.dsv = sm + L.xs; ro.pw = sm + L.pw; ro.gs = nullptr; ro.vskew = 0; ro.wq = sm + L.wq; ro.gpub = nullptr; ro.gwt = true;
     ro.quiet = wg != 0;
@@ -138,7 +147,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
                 for (int u = 0; u < 4; u++) { const int i = lane + 64 * u; hv[u] = h2[i < nh2 ? i : nh2 - 1]; }
             }
             unsigned *w = (unsigned *)(ev + 24 * 64);               // forward_knot_body's progress words (its rowbuf is ev)
-            if (t == 0) { w[0] = 0u; w[2] = 0u; w[3] = 0u; w[4] = 0u; w[5] = st0; }
+            if (t == 0) { w[0] = 0u; w[2] = 0u; w[3] = 0u; w[4] = 0u; w[5] = st0; *verdict = 0u; }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             bad = *(volatile unsigned *)(w + 5) != 0u;
             if (!bad && wg == 0 && t == 0) __hip_atomic_store(flag, (tag << 4) | (my_xcc ? my_xcc : 15u), FRX_RLX_AGENT);
@@ -165,7 +174,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
             }
         }
     } else {
-    if (wg == 0) { if (t == 0) __hip_atomic_store(flag, (tag << 4) | (my_xcc ? my_xcc : 15u), FRX_RLX_AGENT); }
+    if (wg == 0) { if (t == 0) { *verdict = 0u; __hip_atomic_store(flag, (tag << 4) | (my_xcc ? my_xcc : 15u), FRX_RLX_AGENT); } }
     else if (has_task) {   // corridor blocks of the wave's task: constant, in flight under the forward map
         if (k == 0 && wg == 1 && wave == 0 && lane == 0 && a.dp.stamps) a.dp.stamps[44] = (long long)wall_clock64();
         for (int i0 = lane; i0 < nh2; i0 += 4 * 64) {
@@ -197,17 +206,24 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     if (a.dp.stamps && k == 0 && t == 0) a.dp.stamps[41] = (long long)wall_clock64();
     ro.o20ll = a.out20ll; ro.o20tag = tag; ro.status = a.status; ro.spin_ticks = call.timeout_ticks;
     const LineSearchTap tap{nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr};
-    backward_knot_body<true, 64>(a.dp, call.x, a.T, a.C, nullptr, call.f, call.g, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, a.nsteps, tap, c, ev, ctl, &ro);
+    // the tail (EvalTail): f and `done` leave from inside the adjoint; the diagnostic's stamps 64.. of cluster 0 go with it
+    const EvalTail tl{verdict, call.f, done, tag, call.status_host, k == 0 ? a.dp.stamps : nullptr, TAIL};
+    backward_knot_body<true, 64, 0, EvalTail>(a.dp, call.x, a.T, a.C, nullptr, call.f, call.g, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, a.nsteps, tap, c, ev, ctl, &ro, &tl);
     if (a.dp.stamps && k == 0 && t == 0) a.dp.stamps[42] = (long long)wall_clock64();
+    if constexpr (TAIL) {
+        if (a.dp.stamps && k == 0 && t == 0) a.dp.stamps[43] = (long long)wall_clock64();
+    } else {
     __syncthreads();
     if (t == 0) {
         const double fv = ev[36 * 64 + 9 * 65 + 2 * 64 + a.maxCN];  // `red[0]` of backward_knot_wsp64: the objective value (a resident caller's f does not go to global memory there)
         const unsigned code = __hip_atomic_load(a.status, FRX_RLX_AGENT);
         const bool bad = code != 0u;
+        if (tl.st) { asm volatile("" :: "v"(code)); tl.st[67] = (long long)wall_clock64(); }
         call.f[c] = bad ? __builtin_nan("") : fv;
         if (bad && call.status_host) __hip_atomic_store(call.status_host, code, FRX_RLX_SYS);
         __hip_atomic_store(done, tag, FRX_RLX_AGENT);
-        if (a.dp.stamps && k == 0) a.dp.stamps[43] = (long long)wall_clock64();
+        if (tl.st) { const long long e = (long long)wall_clock64(); tl.st[68] = e; tl.st[43] = e; }
+    }
     }
 }
 

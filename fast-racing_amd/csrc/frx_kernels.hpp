@@ -18,6 +18,7 @@
 //   x, g   packed per candidate (tau[dimT], xi[...]);  f [B]
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #include "frx_device.hpp"
 #include "frx_minco.hpp"
@@ -106,6 +107,13 @@ struct KnotPre { int p0, N, c0, cN, x0, cv0, pc, piv, wnv, wvb, wxb; double bs[6
 // consumers published gate_val if they run on the leader's XCD - when all did, the granules leave as plain stores (that XCD's L2 is the meeting point) instead of
 // write-through ones; null: always write-through.
 struct GranuleOut { ll_u64 *ll; unsigned tag; unsigned *gate; unsigned gate_val; const unsigned *mxw; int nmx; };
+// The one-launch evaluation's way out of the adjoint (backward_knot_wsp64<.., TL>: frx_eval_kernel.hpp).  `verdict` is a word of the workgroup's LDS, zero at entry: a
+// polling lane whose wait for the penalty partials ends without them sets it (next to its CAS on the global status word), and thread 0 reads it behind the barrier that
+// follows the knot adjoint, where every such write is ordered before it - no trip to the global word on the good path.  inl: thread 0 stores f (NaN when the verdict is
+// set; the code then goes to status_host, optional) and done = tag right behind the objective's sum, in front of wave 0's time-gradient stores with no wait in between;
+// otherwise the caller does.  (An LDS pointer by type: through a plain pointer in a struct the read is a flat load, which counts on vmcnt.)  st (optional): 100 MHz stamps - [64] wave 0 behind the barrier, [65] wave 0's last gradient store issued, [66] axis wave 1's last store
+// issued, inl: [67] verdict known, [68] done issued.  A struct of its own behind a template flag, as GranuleOut: fields of ResidentOps move k_round's register allocation.
+struct EvalTail { volatile __attribute__((address_space(3))) unsigned *verdict; double *f; unsigned *done; unsigned tag; unsigned *status_host; long long *st; bool inl; };
 
 // Coalesced staging global -> LDS with every load of a trip in flight before the first LDS store.  The plain loop
 // `for (i = k; i < n; i += nthr) dst[i] = src[i]` compiles to load / s_waitcnt vmcnt(0) / ds_write per element even under
@@ -2063,11 +2071,12 @@ __device__ __forceinline__ void backward_knot_wsp64_stage(const DevProblem &dp, 
     FRX_STAMP(24);
 }
 
-template <bool SH>
+template <bool SH, class TL = void>
 __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const double *__restrict__ x, const double *__restrict__ Tin,
                                 const double *__restrict__ Cin, const double *__restrict__ out20, double *__restrict__ f,
                                 double *__restrict__ g, int maxCN, int maxXb, int maxVb, const double *__restrict__ pcrw, int nsteps,
-                                const LineSearchTap &tap, int b, double *sm, const double *ct_lds, const ResidentOps *ro) {
+                                const LineSearchTap &tap, int b, double *sm, const double *ct_lds, const ResidentOps *ro, const TL *tl = nullptr) {
+    constexpr bool TAIL = !std::is_void<TL>::value;     // the one-launch evaluation's tail (EvalTail); nothing of it is compiled into the other callers
     const int nrow = 64, nthr = 256;
     const int k = threadIdx.x, kk = k & 63, t2 = k - 64;
     const int wave = __builtin_amdgcn_readfirstlane(k >> 6);
@@ -2253,6 +2262,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
             if ((spins & 31u) == 31u && (__hip_atomic_load(ro->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || (ll_u64)wall_clock64() > t_end)) {
                 unsigned expect = 0u;
                 __hip_atomic_compare_exchange_strong(ro->status, &expect, 4u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (TAIL) *tl->verdict = 1u;   // (the only way out of this loop without the partials)
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
@@ -2373,6 +2383,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
     }
     __syncthreads();
     FRX_STAMP(22);
+    if constexpr (TAIL) { if (tl->st && k == 0) tl->st[64] = (long long)wall_clock64(); }
     if (wave == 0) {
         // ---- duration gradient, mergeToCoarseGradT (CPU.hpp:946-959), cost (CPU.hpp:988), addLayerTGrad (CPU.hpp:816-894): all within wave 0 ----
         if (piece) gT[kk] = gTl + ((KN(KV, 0, kk) + KN(KV, 1, kk)) + KN(KV, 2, kk)) + dp.rho;     // + rho: CPU.hpp:989
@@ -2388,6 +2399,23 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         const double wc = wave_sum_dpp(costAcc), wtt = wave_sum_dpp(sumTc);
         const double fval = wc + dp.rho * wtt;
         if (kk == 0) { if (!ro) f[b] = fval; red[0] = fval; }             // resident caller: the value travels through the mailbox, nothing to drain
+        if constexpr (TAIL) {
+            // The one-launch evaluation ends HERE for thread 0: f and `done` leave in front of the time gradient, every store of the wave in flight together - vmcnt
+            // retires in order, so a load of the global status word at this point would return only behind the acknowledgements of the stores around it, and f and
+            // `done` behind it would be a third trip.  The verdict comes out of LDS; the global word is read on the failure path alone, for the code.
+            if (tl->inl && k == 0) {
+                const unsigned bad = *tl->verdict;
+                if (__builtin_expect(bad != 0u, 0)) {
+                    unsigned code = __hip_atomic_load(ro->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (code == 0u) code = 4u;                              // (RK_ERR_ARRIVE: what the lane that set the verdict records)
+                    if (tl->status_host) __hip_atomic_store(tl->status_host, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+                if (tl->st) { asm volatile("" :: "v"(bad)); tl->st[67] = (long long)wall_clock64(); }
+                tl->f[b] = bad ? __builtin_nan("") : fval;
+                __hip_atomic_store(tl->done, tl->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tl->st) tl->st[68] = (long long)wall_clock64();
+            }
+        }
         if (dp.soft) {
             if (kk < cN) {
                 const double gi = gCo[kk] * dtt;
@@ -2499,6 +2527,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
     }
     FRX_STAMP_AX(29);
     FRX_STAMP(23);
+    if constexpr (TAIL) { if (tl->st && (k == 0 || k == 64)) tl->st[65 + (k >> 6)] = (long long)wall_clock64(); }
     // ---- line-search tap: what lbfgs.hpp:830 (g.d) and :1296-1297 (|x|, |g|) need, reduced here instead of in a separate launch ----
     if (tap.d != nullptr) {                                           // uniform over the grid
         const double w0 = wave_sum_dpp(t_dg), w1 = wave_sum_dpp(t_xx), w2 = wave_sum_dpp(t_gg);
@@ -2522,15 +2551,15 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
     FRX_STAMP(24);
 }
 
-// SH: out20 (and T, C) were written by workgroups of the same launch.
-template <bool SH, int NR = 0, int RB = 0>
+// SH: out20 (and T, C) were written by workgroups of the same launch.  TL (EvalTail, the one-launch evaluation only): see backward_knot_wsp64.
+template <bool SH, int NR = 0, int RB = 0, class TL = void>
 __device__ __forceinline__ void backward_knot_body(const DevProblem &dp, const double *__restrict__ x, const double *__restrict__ Tin,
                                 const double *__restrict__ Cin, const double *__restrict__ out20, double *__restrict__ f,
                                 double *__restrict__ g, int maxCN, int maxXb, int maxVb, int nrow_rt, const double *__restrict__ pcrw, int nsteps,
-                                const LineSearchTap &tap, int b, double *sm, const double *ct_lds = nullptr, const ResidentOps *ro = nullptr) {
+                                const LineSearchTap &tap, int b, double *sm, const double *ct_lds = nullptr, const ResidentOps *ro = nullptr, const TL *tl = nullptr) {
     const int nrow = NR > 0 ? NR : nrow_rt;
     if (NR == 64 || (NR == 0 && nrow == 64 && blockDim.x == 256)) {              // <= 64 pieces: one wave per axis
-        if (SH) backward_knot_wsp64<SH>(dp, x, Tin, Cin, out20, f, g, maxCN, maxXb, maxVb, pcrw, nsteps, tap, b, sm, ct_lds, ro);       // resident caller: the order built around the poll
+        if (SH) backward_knot_wsp64<SH, TL>(dp, x, Tin, Cin, out20, f, g, maxCN, maxXb, maxVb, pcrw, nsteps, tap, b, sm, ct_lds, ro, tl);       // resident caller: the order built around the poll
         else backward_knot_wsp64_stage<SH, RB>(dp, x, Tin, Cin, out20, f, g, maxCN, maxXb, maxVb, pcrw, nsteps, tap, b, sm, ct_lds, ro);
         return;
     }

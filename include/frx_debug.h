@@ -71,6 +71,9 @@ int frx_eval_launch_time(frx_problem *p, const double *x, int reps, double *out_
  * frx_profile_phases, [40..43] the leader's entry / end of the forward map / end of the adjoint / end, [44..48] wave 0 of the first member: entry, gate seen,
  * granules staged, samples done, partials out. */
 int frx_debug_profile_eval_cluster(frx_problem *p, const double *x, long long *out64);
+/* The same with the stamps of the evaluation's tail behind the first 64 (100 MHz counter, as 40..48): out80[64] wave 0 of the leader behind the barrier that follows
+ * the knot adjoint, [65] its last gradient store issued, [66] axis wave 1's last store issued, [67] thread 0 has the verdict, [68] thread 0 has issued `done`. */
+int frx_debug_profile_eval_tail(frx_problem *p, const double *x, long long *out80);
 
 /* Diagnostic: runs one evaluation at x and returns shader-clock stamps taken at the phase boundaries of candidate 0's
  * k_forward_knot (out32[0..6]) and k_backward_knot (out32[16..24]). */

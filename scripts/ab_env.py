@@ -1,7 +1,9 @@
 """A/B of run-time SWITCHES of one build on one box (boxes differ by 3-5 %, their hosts by more): alternating subprocesses, each with one of the given environments.
 Per process: the headline plan (32 candidates) and the one-candidate plan - us per round, rounds, a checksum of the optimised x (bit-identity between variants) - the
 evaluation in the form frx_objective_eval_device takes (HIP events around 300 back-to-back launches, best of three) with a checksum of (f, grad), the three stage kernels.
-   python scripts/ab_env.py "VAR=a VAR2=b" "VAR=c" ... [reps]       ("-" = the default environment)     -> one JSON line per (variant, repetition), then medians"""
+   python scripts/ab_env.py "VAR=a VAR2=b" "VAR=c" ... [reps]       ("-" = the default environment)     -> one JSON line per (variant, repetition), then medians
+AB_ROOT=<dir> in a variant loads the package (frx_import.py, fast-racing_amd/ with its libfrx.so) from that root instead of this tree: another BUILD in the same alternation
+(scripts/r04/make_variant.sh makes such a root from a git ref)."""
 import hashlib, json, os, subprocess, sys
 child = r'''
 import os, sys, json, hashlib
@@ -52,7 +54,7 @@ for i in range(reps):
         if v != "-":
             for kv in v.split(): k, _, val = kv.partition("="); env[k] = val
         try:
-            p = subprocess.run([sys.executable, "-c", child, ROOT], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, env=env)
+            p = subprocess.run([sys.executable, "-c", child, os.path.abspath(env.pop("AB_ROOT", ROOT))], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, env=env)
             d = json.loads(p.stdout.strip().splitlines()[-1])
         except Exception as e:
             d = {"error": repr(e), "stderr": (p.stderr[-400:] if "p" in dir() else "")}
