@@ -75,7 +75,7 @@ DEBUG_SYMBOLS = [
     "frx_debug_trace", "frx_resident_profile", "frx_debug_direction_log", "frx_debug_direction_log_read", "frx_debug_set_resident_retry",
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
     "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
-    "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device",
+    "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device", "frx_debug_dv_layout", "frx_debug_dv_round",
 ]
 
 # frx_trajectory_check (include/frx.h): fields of a row and flag bits
@@ -115,6 +115,8 @@ def lib():
         L.frx_traj_to_msg.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _up]
         L.frx_msg_sample.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _up, C.c_double, _dp, _dp, _dp, _dp]
         L.frx_dv_selftest.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.frx_debug_dv_layout.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.frx_debug_dv_round.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 17
         L.frx_line_segment_dilate.argtypes = [_dp, _dp, _dp, C.c_int, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_corridor_generate.argtypes = [C.c_int, _dp, C.c_int, C.c_void_p, _dp, C.c_double, C.c_double, BLOCKED_FN, C.c_void_p, C.c_int, C.c_int,
                                             C.POINTER(C.c_int), _ip, _dp]
@@ -423,6 +425,48 @@ def dv_selftest(n, B=4, m=128, iters=140, geom=None, seed=0, device=0):
     gp = (C.c_int * 4)(*geom) if geom else None
     _check(lib().frx_dv_selftest(device, n, B, m, iters, gp, seed, C.byref(err), C.byref(us)))
     return err.value, us.value
+
+
+# struct DvCommand / DvResult and the command bits of the device-vector L-BFGS (csrc/frx_lbfgs.hpp)
+DV_COMMAND = np.dtype([("flags", np.int32), ("slot", np.int32), ("bound", np.int32), ("newest", np.int32), ("step", np.float64)])
+DV_RESULT = np.dtype([("f", np.float64), ("dg", np.float64), ("xx", np.float64), ("gg", np.float64), ("dginit", np.float64), ("pad", np.float64, 3)])
+DV_EVAL, DV_INIT, DV_ADVANCE, DV_TRIAL, DV_RESTORE = 1, 2, 4, 8, 16
+
+
+def dv_layout(n_max, geom=None, tight=True):
+    """frx_debug_dv_layout: ((E, W, PF, BLK), row stride hs) of k_lbfgs_pre for a batch whose longest vector has n_max elements."""
+    out = np.zeros(5, np.int32)
+    gp = np.ascontiguousarray(geom, dtype=np.int32) if geom is not None else None
+    _check(lib().frx_debug_dv_layout(int(n_max), gp.ctypes.data if gp is not None else None, int(bool(tight)), out.ctypes.data))
+    return tuple(int(v) for v in out[:4]), int(out[4])
+
+
+def dv_round(st, cmd, f=None, device=0):
+    """frx_debug_dv_round: one launch of k_lbfgs_pre (and of k_lbfgs_post when f is given) on the state `st`, IN PLACE.  st: geom (E, W, PF, BLK), hs, m,
+    xoff int32 [B+1]; x, g, xp, gp, d float64 of one length; S, Y of one length (>= B m hs); ys; gt; res (DV_RESULT records); optionally poff int32 [B+1] with
+    dflags and pflags int32.  Arrays may be longer than the batch needs: their whole length goes to the device and comes back.  cmd: DV_COMMAND [B]."""
+    B = len(st["xoff"]) - 1
+    geom = np.ascontiguousarray(st["geom"], dtype=np.int32)
+    for k in ("x", "g", "xp", "gp", "d", "S", "Y", "ys", "gt"):
+        a = st[k]
+        assert a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable, k
+    assert len({st[k].size for k in ("x", "g", "xp", "gp", "d")}) == 1 and st["S"].size == st["Y"].size
+    assert st["xoff"].dtype == np.int32 and cmd.dtype == DV_COMMAND and len(cmd) == B and st["res"].dtype == DV_RESULT and cmd.flags.c_contiguous
+    with_p = st.get("poff") is not None
+    if with_p:
+        assert st["poff"].dtype == np.int32 and st["pflags"].dtype == np.int32 and len(st["poff"]) == B + 1
+    with_d = st.get("dflags") is not None
+    if with_d:
+        assert st["dflags"].dtype == np.int32
+    lens = np.array([st["x"].size, st["S"].size, st["ys"].size, st["gt"].size, st["dflags"].size if with_d else 0, st["pflags"].size if with_p else 0,
+                     len(st["res"])], dtype=np.int64)
+    fa = None if f is None else np.ascontiguousarray(f, dtype=np.float64)
+    assert fa is None or fa.size == B
+    ptr = lambda a: a.ctypes.data
+    _check(lib().frx_debug_dv_round(device, B, int(st["m"]), ptr(geom), int(st["hs"]), ptr(lens), ptr(st["xoff"]), ptr(st["x"]), ptr(st["g"]), ptr(st["xp"]),
+                                    ptr(st["gp"]), ptr(st["d"]), ptr(st["S"]), ptr(st["Y"]), ptr(st["ys"]), ptr(st["gt"]), ptr(cmd), ptr(st["res"]),
+                                    ptr(st["poff"]) if with_p else None, ptr(st["dflags"]) if with_d else None, ptr(st["pflags"]) if with_p else None,
+                                    ptr(fa) if fa is not None else None))
 
 
 def traj_max_rates(T, Cf):

@@ -793,6 +793,83 @@ int frx_dv_selftest(int device, int n, int B, int m, int iters, const int *geom4
     return FRX_OK;
 }
 
+// Diagnostic (tests): the geometry and the row stride a plan whose longest vector has n_max elements runs k_lbfgs_pre with - dv_geometry and
+// dv_row_stride themselves.  No device needed.
+int frx_debug_dv_layout(int n_max, const int *geom4, int tight, int *out5) {
+    if (n_max < 1 || !out5) return fail(FRX_ERR_INVALID_ARG, "bad layout argument");
+    int E = 0, W = 0, PF = 0, BLK = 4;
+    frx::dv_geometry(n_max, &E, &W, &PF);
+    if (geom4) { E = geom4[0]; W = geom4[1]; PF = geom4[2]; BLK = geom4[3]; }
+    if (E < 2 || E > 8 || (E & 1) || W < 1 || W > 8 || PF < 1 || PF > 16 || BLK < 1 || BLK > 4 || n_max > 64 * W * E)
+        return fail(FRX_ERR_CAPACITY, "vector too long for k_lbfgs_pre (or no such geometry)");
+    out5[0] = E; out5[1] = W; out5[2] = PF; out5[3] = BLK; out5[4] = (int)frx::dv_row_stride(n_max, E, W, tight != 0);
+    return FRX_OK;
+}
+
+// Diagnostic (tests): ONE round of the device-vector L-BFGS on state the caller owns - upload, k_lbfgs_pre through launch_lbfgs_pre, k_lbfgs_post when f is
+// given, synchronise, copy everything back.  Every array travels in its whole given length (lens7), so what lies behind the part the kernels own comes back
+// as it went.  Nothing is computed here; the checks below only keep a launch inside the arrays.
+int frx_debug_dv_round(int device, int B, int m, const int *geom4, int hs, const long long *lens7, const int *xoff, double *x, double *g, double *xp, double *gp,
+                       double *d, double *S, double *Y, double *ys, double *gt, const void *cmd, void *res, const int *poff, int *dflags, int *pflags,
+                       const double *f) {
+    if (B < 1 || m < 1 || m > 512 || !geom4 || !lens7 || !xoff || !x || !g || !xp || !gp || !d || !S || !Y || !ys || !gt || !cmd || !res)
+        return fail(FRX_ERR_INVALID_ARG, "bad dv round argument");
+    const int E = geom4[0], W = geom4[1], PF = geom4[2], BLK = geom4[3];
+    // (the same range as frx_debug_dv_layout; whether (E, W, PF, BLK) is instantiated is launch_lbfgs_pre's to say, before anything is launched.  m <= 512 and PF <= 16
+    // keep the kernel's tables of 512 + 2 * 16 ages; hs below is one of the two EVEN strides the library itself takes for this batch)
+    if (E < 2 || E > 8 || (E & 1) || W < 1 || W > 8 || PF < 1 || PF > 16 || BLK < 1 || BLK > 4) return fail(FRX_ERR_INVALID_ARG, "no such k_lbfgs_pre geometry");
+    const long long n_vec = lens7[0], n_hist = lens7[1], n_ys = lens7[2], n_gt = lens7[3], n_df = lens7[4], n_pf = lens7[5], n_res = lens7[6];
+    int n_max = 0;
+    if (xoff[0] < 0) return fail(FRX_ERR_INVALID_ARG, "xoff[0] < 0");
+    for (int b = 0; b < B; b++) {
+        if (xoff[b + 1] <= xoff[b]) return fail(FRX_ERR_INVALID_ARG, "every candidate needs at least one variable");
+        n_max = std::max(n_max, xoff[b + 1] - xoff[b]);
+    }
+    if (n_max > 64 * W * E) return fail(FRX_ERR_CAPACITY, "vector too long for the geometry");
+    if ((size_t)hs != frx::dv_row_stride(n_max, E, W, true) && hs != 64 * W * E) return fail(FRX_ERR_INVALID_ARG, "hs is neither the tight nor the full row of this batch");
+    if (xoff[B] > n_vec || (long long)B * m * hs > n_hist || (long long)B * m > n_ys || (long long)B * m * 4 > n_gt || n_res < B)
+        return fail(FRX_ERR_INVALID_ARG, "an array is shorter than the batch needs");
+    const frx::DvCommand *hc = (const frx::DvCommand *)cmd;
+    for (int b = 0; b < B; b++)
+        if ((hc[b].flags & frx::DV_ADVANCE) && (hc[b].slot < 0 || hc[b].slot >= m || hc[b].bound < 1 || hc[b].bound > m))
+            return fail(FRX_ERR_INVALID_ARG, "ADVANCE command with slot or bound outside the history");
+    if (dflags && n_df < B) return fail(FRX_ERR_INVALID_ARG, "dflags shorter than the batch");
+    if ((pflags != nullptr) != (poff != nullptr)) return fail(FRX_ERR_INVALID_ARG, "pflags and poff come together");
+    if (pflags) {
+        if (poff[0] < 0 || poff[B] > n_pf) return fail(FRX_ERR_INVALID_ARG, "pflags shorter than poff asks for");
+        for (int b = 0; b < B; b++) if (poff[b + 1] < poff[b]) return fail(FRX_ERR_INVALID_ARG, "poff not ascending");
+    }
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> dx, dg, dxp, dgp, dd, dS, dY, dys, dgt, df; DevBuf<int> dxoff, dpoff, ddf, dpf;
+    PinBuf<frx::DvCommand> pc; PinBuf<frx::DvResult> pr;
+    hipError_t e;
+    if ((e = dx.alloc(n_vec)) || (e = dg.alloc(n_vec)) || (e = dxp.alloc(n_vec)) || (e = dgp.alloc(n_vec)) || (e = dd.alloc(n_vec)) || (e = dS.alloc(n_hist)) ||
+        (e = dY.alloc(n_hist)) || (e = dys.alloc(n_ys)) || (e = dgt.alloc(n_gt)) || (e = dxoff.alloc(B + 1)) || (e = pc.alloc(B)) || (e = pr.alloc(n_res)) ||
+        (dflags && (e = ddf.alloc(n_df))) || (pflags && ((e = dpf.alloc(n_pf)) || (e = dpoff.alloc(B + 1)))) || (f && (e = df.alloc(B))))
+        return fail(FRX_ERR_ALLOC, hipGetErrorString(e));
+    auto up = [](auto &buf, const void *h, long long count) { return count > 0 ? hipMemcpy(buf.p, h, sizeof(*buf.p) * count, hipMemcpyHostToDevice) : hipSuccess; };
+    auto down = [](void *h, auto &buf, long long count) { return count > 0 ? hipMemcpy(h, buf.p, sizeof(*buf.p) * count, hipMemcpyDeviceToHost) : hipSuccess; };
+    HIP_TRY(up(dx, x, n_vec)); HIP_TRY(up(dg, g, n_vec)); HIP_TRY(up(dxp, xp, n_vec)); HIP_TRY(up(dgp, gp, n_vec)); HIP_TRY(up(dd, d, n_vec));
+    HIP_TRY(up(dS, S, n_hist)); HIP_TRY(up(dY, Y, n_hist)); HIP_TRY(up(dys, ys, n_ys)); HIP_TRY(up(dgt, gt, n_gt)); HIP_TRY(up(dxoff, xoff, B + 1));
+    if (dflags) HIP_TRY(up(ddf, dflags, n_df));
+    if (pflags) { HIP_TRY(up(dpf, pflags, n_pf)); HIP_TRY(up(dpoff, poff, B + 1)); }
+    if (f) HIP_TRY(up(df, f, B));
+    std::memcpy(pc.p, cmd, sizeof(frx::DvCommand) * B); std::memcpy(pr.p, res, sizeof(frx::DvResult) * n_res);
+    frx::DvLaunch dv;
+    dv.xoff = dxoff.p; dv.x = dx.p; dv.g = dg.p; dv.xp = dxp.p; dv.gp = dgp.p; dv.d = dd.p; dv.S = dS.p; dv.Y = dY.p; dv.ys = dys.p; dv.gt = dgt.p;
+    dv.dflags = dflags ? ddf.p : nullptr; dv.pflags = pflags ? dpf.p : nullptr; dv.poff = pflags ? dpoff.p : nullptr;
+    dv.ld = (size_t)n_vec; dv.hs = (size_t)hs; dv.m = m; dv.B = B; dv.E = E; dv.W = W; dv.PF = PF; dv.BLK = BLK;
+    if (frx::launch_lbfgs_pre(dv, pc.p, pr.p, nullptr)) return fail(FRX_ERR_HIP, "k_lbfgs_pre launch (geometry not instantiated?)");
+    if (f && frx::launch_lbfgs_post(dv, df.p, pc.p, pr.p, nullptr)) return fail(FRX_ERR_HIP, "k_lbfgs_post launch");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(down(x, dx, n_vec)); HIP_TRY(down(g, dg, n_vec)); HIP_TRY(down(xp, dxp, n_vec)); HIP_TRY(down(gp, dgp, n_vec)); HIP_TRY(down(d, dd, n_vec));
+    HIP_TRY(down(S, dS, n_hist)); HIP_TRY(down(Y, dY, n_hist)); HIP_TRY(down(ys, dys, n_ys)); HIP_TRY(down(gt, dgt, n_gt));
+    if (dflags) HIP_TRY(down(dflags, ddf, n_df));
+    if (pflags) HIP_TRY(down(pflags, dpf, n_pf));
+    std::memcpy(res, pr.p, sizeof(frx::DvResult) * n_res);
+    return FRX_OK;
+}
+
 // Diagnostic (bench): average duration of each stage kernel of an evaluation at x, HIP events on the handle's stream around `reps`
 // back-to-back launches of ONE kernel at a time (the other stages run once before, so every kernel sees valid inputs).
 int frx_eval_stage_times(frx_problem *p, const double *x, int reps, double *out3_us) {

@@ -84,6 +84,21 @@ int frx_profile_phases(frx_problem *p, const double *x, long long *out32);
 int frx_dv_selftest(int device, int n, int B, int m, int iters, const int *geom4, unsigned seed, double *max_rel_err,
                     double *avg_us);
 
+/* Diagnostic (tests): the layout the device-vector L-BFGS runs with when the longest vector of a batch has n_max elements (csrc/frx_device.hpp, dv_geometry and
+ * dv_row_stride themselves): out5 = {doubles/thread E, waves W, look-ahead rows PF, pairs per reduction BLK, row stride hs of the history in doubles}.
+ * geom4 = {E, W, PF, BLK} to ask for the row of that geometry, NULL for the library's choice; tight = 0 gives the full row 64 W E.  Needs no device. */
+int frx_debug_dv_layout(int n_max, const int *geom4, int tight, int *out5);
+/* Diagnostic (tests): ONE round of the device-vector L-BFGS on state the caller owns (host arrays): they are uploaded, k_lbfgs_pre runs the commands
+ * cmd[B] (struct DvCommand of csrc/frx_lbfgs.hpp: int flags, slot, bound, newest; double step), k_lbfgs_post follows when f[B] is given, and everything is
+ * copied back.  xoff[B+1] delimits the packed vectors x, g, xp, gp, d; S, Y are [B][m][hs], ys [B][m], gt [B][m][4]; res[B] (struct DvResult: 8 doubles f, dg,
+ * xx, gg, dginit, 3 unused) goes in and comes out; poff[B+1] with dflags[B] and pflags[poff[B]] are optional (NULL).  lens7 = the lengths, in elements, of
+ * {each packed vector, S and Y each, ys, gt, dflags, pflags, res}: an array may be longer than the batch needs, its whole length makes the trip, so a
+ * sentinel behind the used part shows a store that went astray.  geom4 and hs as frx_debug_dv_layout gives them for the batch's longest vector (hs tight
+ * or full).  Allocates per call; adds no arithmetic. */
+int frx_debug_dv_round(int device, int B, int m, const int *geom4, int hs, const long long *lens7, const int *xoff, double *x, double *g, double *xp, double *gp,
+                       double *d, double *S, double *Y, double *ys, double *gt, const void *cmd, void *res, const int *poff, int *dflags, int *pflags,
+                       const double *f);
+
 /* The jump-point neighbour tables in the reference's storage order (JPS3DNeib ns[27][3][26], f1/f2[27][3][12]; JPS2DNeib
  * ns[9][2][8], f1/f2[9][2][2]; graph_search.h:72-127), generated from rules instead of spelled out; for the parity test. */
 int frx_jps_tables(int *ns3, int *f13, int *f23, int *ns2, int *f12, int *f22);
