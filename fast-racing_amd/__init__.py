@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "frx_trajectory_check", "frx_trajectory_check_device", "frx_trajectory_sample", "frx_trajectory_sample_device",
     "frx_trajectory_clearance", "frx_trajectory_clearance_workspace", "frx_trajectory_clearance_device",
     "frx_corridor_generate_batch", "frx_corridor_generate_batch_device",
+    "frx_enumerate_vertices_batch", "frx_enumerate_vertices_batch_device", "frx_corridor_slots_to_tasks_device",
 ]
 # diagnostics, include/frx_debug.h: not part of the drop-in boundary
 DEBUG_SYMBOLS = [
@@ -176,6 +177,9 @@ def lib():
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_corridor_generate_batch_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_enumerate_vertices_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.frx_enumerate_vertices_batch_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_corridor_slots_to_tasks_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_debug_map_blocked_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_optimize.argtypes = [C.c_void_p, C.POINTER(LbfgsParams), _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
         L.frx_optimize_stats.argtypes = [C.c_void_p, _dp]
@@ -340,6 +344,45 @@ def corridor_generate_batch_device(n_paths, path_off_dev, path_dev, n_obs, obs_d
     _check(lib().frx_corridor_generate_batch_device(n_paths, path_off_dev, path_dev, n_obs, obs_dev, bbox.ctypes.data, map_height, max_seg,
                                                     C.cast(C.pointer(map_struct), C.c_void_p) if map_struct is not None else None, cap_polys, cap_planes,
                                                     h_slot_dev, cell_planes_dev, n_polys_dev, status_dev, stream))
+
+
+# frx_enumerate_vertices_batch (include/frx.h): a task's status, the most planes of a task, the range of cap_v
+HV_OK, HV_UNBOUNDED, HV_FLAT, HV_PLANES, HV_VERTICES, HV_NONFINITE, HV_SKIPPED = 0, 1, 2, 3, 4, 5, 6
+HV_MAX_PLANES, HV_MIN_CAP_V, HV_MAX_CAP_V = 256, 4, 512
+
+
+def enumerate_vertices_batch(coarse_n, h_off, h_rec, cap_v: int = 64, device: int = 0):
+    """V-polytopes of a batch of corridors on the device (frx_enumerate_vertices_batch): coarse_n, h_off, h_rec as frx_problem_create_from_h takes them (the
+    raw output of corridor_generate_batch, or pack_batch(cands)[0, 3, 4]).  Returns (v_off, v_rec, status): the CSR frx_problem_create takes over the
+    2 coarse_n[b] - 1 polytopes of every candidate in the order [cell 0, overlap 0|1, cell 1, ...], and HV_* per polytope (the vertices of an unbounded or
+    flat polytope are included as the host computes them; a polytope with another non-zero status has none)."""
+    coarse_n = np.ascontiguousarray(coarse_n, dtype=np.int32); h_off = np.ascontiguousarray(h_off, dtype=np.int32)
+    h_rec = np.ascontiguousarray(h_rec, dtype=np.float64).reshape(-1)
+    B = len(coarse_n)
+    n_tasks = max(int(2 * coarse_n.sum() - B), 1) if B else 1
+    status = np.zeros(n_tasks, np.int32); v_off = np.zeros(n_tasks + 1, np.int32); need = C.c_int()
+    cap_vert = 24 * n_tasks                                               # a first guess; the library reports the need when it is too small
+    for _ in range(2):
+        v_rec = np.zeros(3 * cap_vert)
+        rc = lib().frx_enumerate_vertices_batch(device, B, coarse_n.ctypes.data, h_off.ctypes.data, h_rec.ctypes.data, cap_v, status.ctypes.data, v_off.ctypes.data,
+                                                cap_vert, C.byref(need), v_rec.ctypes.data)
+        if rc != -5 or need.value <= cap_vert:                            # FRX_ERR_CAPACITY with a larger need: once more with that room
+            break
+        cap_vert = need.value
+    _check(rc)
+    return v_off, v_rec[:3 * need.value].copy(), status
+
+
+def enumerate_vertices_batch_device(n_tasks, tasks_dev, h_rec_dev, cap_v, v_slot_dev, nv_dev, status_dev, stream=0):
+    """frx_enumerate_vertices_batch_device: one launch on `stream`; device addresses as integers.  tasks [n_tasks][4] int (begin0, count0, begin1, count1 in
+    records of h_rec); outputs v_slot [n_tasks][cap_v][3], nv [n_tasks], status [n_tasks]."""
+    _check(lib().frx_enumerate_vertices_batch_device(n_tasks, tasks_dev, h_rec_dev, cap_v, v_slot_dev, nv_dev, status_dev, stream))
+
+
+def corridor_slots_to_tasks_device(n_paths, cap_polys, cap_planes, cell_planes_dev, n_polys_dev, tasks_dev, stream=0):
+    """frx_corridor_slots_to_tasks_device: one launch on `stream` that fills tasks [n_paths][2 cap_polys - 1][4] from the slotted outputs of
+    corridor_generate_batch_device (record indices into its h_slot)."""
+    _check(lib().frx_corridor_slots_to_tasks_device(n_paths, cap_polys, cap_planes, cell_planes_dev, n_polys_dev, tasks_dev, stream))
 
 
 class VoxelMapStruct(C.Structure):

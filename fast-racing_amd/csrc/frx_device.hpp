@@ -209,4 +209,15 @@ size_t chain_lds_bytes(int pcap, int cap_planes);
 int launch_chain(const ChainLaunch &c, void *stream);
 int launch_map_blocked_pairs(const ChainLaunch &map_of, int n, const double *a, const double *b, int *out, void *stream);   // tests: only the map fields are read
 
+// ---- H -> V vertex enumeration on the device, one workgroup per polytope (frx_enumerate_kernel.hpp) ----
+struct EnumLaunch {
+    const int *tasks; const double *h_rec;                         // device pointers: [n_tasks][4] (begin0, count0, begin1, count1 in records), records of 6 doubles
+    int n_tasks, cap_v;
+    double *v_slot; int *nv, *status;                              // [n_tasks][cap_v][3], [n_tasks], [n_tasks]
+};
+enum { ENUM_MAX_PLANES = 256, ENUM_MIN_CAP_V = 4, ENUM_MAX_CAP_V = 512 };
+size_t enumerate_lds_bytes(int cap_v);                              // dynamic LDS of one workgroup
+int launch_enumerate(const EnumLaunch &e, void *stream);
+int launch_slots_to_tasks(int n_paths, int cap_polys, int cap_planes, const int *cell_planes, const int *n_polys, int *tasks, void *stream);
+
 } // namespace frx

@@ -468,6 +468,99 @@ int frx_corridor_generate_batch(int device, int n_paths, const int *path_off, co
     return FRX_OK;
 }
 
+// ---- H -> V vertex enumeration for a batch of polytopes (frx_enumerate_kernel.hpp): the device form is one launch, the blocking form is that launch between
+// an upload of the CSR frx_problem_create_from_h takes and a host compaction of the vertex slots into the CSR frx_problem_create takes ----
+int frx_enumerate_vertices_batch_device(int n_tasks, const int *tasks_dev, const double *h_rec_dev, int cap_v, double *v_slot_dev, int *nv_dev, int *status_dev,
+                                        void *hip_stream) {
+    const char *who = "frx_enumerate_vertices_batch_device";
+    if (n_tasks < 1 || !tasks_dev || !h_rec_dev || !v_slot_dev || !nv_dev || !status_dev) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null argument or n_tasks < 1");
+    if (cap_v < frx::ENUM_MIN_CAP_V || cap_v > frx::ENUM_MAX_CAP_V) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": cap_v outside [4, 512] (the accepted vertices stay in LDS)");
+    if (frx_device_count() < 1) return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    frx::EnumLaunch L;
+    L.tasks = tasks_dev; L.h_rec = h_rec_dev; L.n_tasks = n_tasks; L.cap_v = cap_v; L.v_slot = v_slot_dev; L.nv = nv_dev; L.status = status_dev;
+    const hipError_t e = (hipError_t)frx::launch_enumerate(L, hip_stream);
+    if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return FRX_OK;
+}
+
+int frx_corridor_slots_to_tasks_device(int n_paths, int cap_polys, int cap_planes, const int *cell_planes_dev, const int *n_polys_dev, int *tasks_dev, void *hip_stream) {
+    const char *who = "frx_corridor_slots_to_tasks_device";
+    if (n_paths < 1 || cap_polys < 1 || cap_planes < 1 || !cell_planes_dev || !n_polys_dev || !tasks_dev) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null or out-of-range argument");
+    if ((double)n_paths * cap_polys * cap_planes > 2.0e9) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": n_paths x cap_polys x cap_planes exceeds 2e9 (record indices are int)");
+    if (frx_device_count() < 1) return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    const hipError_t e = (hipError_t)frx::launch_slots_to_tasks(n_paths, cap_polys, cap_planes, cell_planes_dev, n_polys_dev, tasks_dev, hip_stream);
+    if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return FRX_OK;
+}
+
+int frx_enumerate_vertices_batch(int device, int B, const int *coarse_n, const int *h_off, const double *h_rec, int cap_v, int *status, int *v_off, int cap_vert,
+                                 int *n_vert, double *v_rec) {
+    const char *who = "frx_enumerate_vertices_batch";
+    if (B < 1 || !coarse_n || !h_off || !h_rec || !status || !v_off || !n_vert || !v_rec || cap_vert < 0) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null or out-of-range argument");
+    if (cap_v < frx::ENUM_MIN_CAP_V || cap_v > frx::ENUM_MAX_CAP_V) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": cap_v outside [4, 512] (the accepted vertices stay in LDS)");
+    long long n_poly = 0;
+    for (int b = 0; b < B; b++) {
+        if (coarse_n[b] < 1) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": coarse_n[" + std::to_string(b) + "] < 1");
+        n_poly += coarse_n[b];
+    }
+    if (2 * n_poly - B > 0x7fffffffLL / 4) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": too many polytopes");
+    if (h_off[0] < 0) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": h_off[0] < 0");
+    for (long long m = 0; m < n_poly; m++)
+        if (h_off[m + 1] < h_off[m]) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": h_off is not monotone at polytope " + std::to_string(m));
+    if (frx_device_count() < 1) return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    DeviceGuard restore_device;
+    if (hipSetDevice(device) != hipSuccess) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": device ordinal out of range");
+    // the tasks in the order [cell 0, overlap 0|1, cell 1, ...] per candidate; an overlap's two ranges are contiguous in this CSR and named apart all the same
+    std::vector<int> tasks;
+    tasks.reserve((size_t)4 * (2 * n_poly - B));
+    int poly = 0;
+    for (int b = 0; b < B; b++) {
+        for (int i = 0; i < coarse_n[b]; i++) {
+            const int hb = h_off[poly + i], K = h_off[poly + i + 1] - hb;
+            tasks.insert(tasks.end(), {hb, K, 0, 0});
+            if (i + 1 < coarse_n[b]) tasks.insert(tasks.end(), {hb, K, h_off[poly + i + 1], h_off[poly + i + 2] - h_off[poly + i + 1]});
+        }
+        poly += coarse_n[b];
+    }
+    const int NT = (int)(tasks.size() / 4);
+    // (an empty cell would read as "no task": report it as the plane count it is)
+    for (int t = 0; t < NT; t++) if (tasks[4 * t + 1] == 0) { tasks[4 * t + 1] = tasks[4 * t + 3]; tasks[4 * t + 2] = 0; tasks[4 * t + 3] = 0; if (tasks[4 * t + 1] == 0) tasks[4 * t + 1] = -1; }
+    const size_t n_rec = (size_t)h_off[n_poly], slot_bytes = sizeof(double) * 3 * (size_t)cap_v;
+    int *d_tasks = nullptr, *d_nv = nullptr, *d_st = nullptr; double *d_rec = nullptr, *d_slot = nullptr;
+    auto cleanup = [&]() { for (void *q : {(void *)d_tasks, (void *)d_nv, (void *)d_st, (void *)d_rec, (void *)d_slot}) if (q) (void)hipFree(q); };
+    if (hipMalloc((void **)&d_tasks, 16 * (size_t)NT) != hipSuccess || hipMalloc((void **)&d_nv, 4 * (size_t)NT) != hipSuccess || hipMalloc((void **)&d_st, 4 * (size_t)NT) != hipSuccess ||
+        hipMalloc((void **)&d_rec, 48 * std::max<size_t>(n_rec, 1)) != hipSuccess || hipMalloc((void **)&d_slot, slot_bytes * NT) != hipSuccess) {
+        cleanup();
+        return frx::set_error(FRX_ERR_ALLOC, std::string(who) + ": device buffers (" + std::to_string(slot_bytes * NT) + " bytes of vertex slots)");
+    }
+    hipError_t e = hipMemcpy(d_tasks, tasks.data(), 16 * (size_t)NT, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_rec) e = hipMemcpy(d_rec, h_rec, 48 * n_rec, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cleanup(); return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+    const int rc = frx_enumerate_vertices_batch_device(NT, d_tasks, d_rec, cap_v, d_slot, d_nv, d_st, nullptr);
+    if (rc != FRX_OK) { cleanup(); return rc; }
+    std::vector<int> nv(NT);
+    e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipMemcpy(nv.data(), d_nv, 4 * (size_t)NT, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(status, d_st, 4 * (size_t)NT, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { cleanup(); return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+    // compaction: of every slot only the widest polytope's share is fetched
+    long long need = 0;
+    int widest = 0;
+    v_off[0] = 0;
+    for (int t = 0; t < NT; t++) { need += nv[t]; widest = std::max(widest, nv[t]); v_off[t + 1] = (int)std::min<long long>(need, 0x7fffffffLL); }
+    *n_vert = (int)std::min<long long>(need, 0x7fffffffLL);
+    if (need > cap_vert) { cleanup(); return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": " + std::to_string(need) + " vertices, cap_vert is " + std::to_string(cap_vert)); }
+    if (widest > 0) {
+        const size_t row = sizeof(double) * 3 * (size_t)widest;
+        std::vector<double> stage((size_t)3 * widest * NT);
+        e = hipMemcpy2D(stage.data(), row, d_slot, slot_bytes, row, (size_t)NT, hipMemcpyDeviceToHost);
+        for (int t = 0; t < NT && e == hipSuccess; t++) std::memcpy(v_rec + 3 * (size_t)v_off[t], stage.data() + (size_t)3 * widest * t, sizeof(double) * 3 * (size_t)nv[t]);
+    }
+    cleanup();
+    if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return FRX_OK;
+}
+
 // Tests: the device's sight line (map_blocked, frx_chain_kernel.hpp) on n_pairs pairs of points, host buffers in and out; out[i] = 0 / 1 as frx_map_is_blocked.
 int frx_debug_map_blocked_device(int device, const frx_voxel_map *map, int n_pairs, const double *a, const double *b, int *out) {
     if (!map || !map->cells || !(map->res > 0) || map->dim[0] <= 0 || map->dim[1] <= 0 || map->dim[2] <= 0 || n_pairs < 1 || !a || !b || !out)

@@ -131,6 +131,36 @@ int frx_problem_create_from_h(const frx_config *cfg, int device, int B, const in
 /* Vertices (3 doubles each, lexicographic order) of one H-polytope given as K records (outer normal, point). */
 int frx_enumerate_vertices(int K, const double *h_rec, double *v_out, int cap, int *nv);
 
+/* The same enumeration on the DEVICE for a batch of polytopes (csrc/frx_enumerate_kernel.hpp): one 256-thread workgroup per task walks the plane triples in
+ * the host's order in windows of 256, keeps the first triple of every 1e-7 grid key, sorts by key and judges the polytope - vertices, counts and verdicts are
+ * those of frx_enumerate_vertices / frx_problem_create_from_h bit for bit (every operation is the host's, in its order, none fused).
+ * A task = {begin0, count0, begin1, count1}, four int in records of 6 doubles: the polytope's planes are records begin0 .. begin0+count0-1 followed by
+ * begin1 .. begin1+count1-1 (a cell: count1 = 0; an overlap: the two cells' ranges, which need not be contiguous); count0 = 0: no task.
+ * status per task (FRX_HV_*): 0 = ok; 1 = unbounded and 2 = flat, the host's two refusals (FRX_ERR_EMPTY_POLYTOPE there) - nv and the vertices are written as
+ * the host computes them; 3 = fewer than 4 or more than 256 planes; 4 = more distinct vertices than cap_v; 5 = a record is not finite; 6 = no task.  For 3 - 6
+ * nv = 0 and the task's vertices are left untouched.  A task does not disturb another; the call returns FRX_OK whatever the statuses are.
+ *   frx_enumerate_vertices_batch          blocking, host pointers; takes what frx_problem_create_from_h takes, builds the 2 coarse_n[b] - 1 tasks of every
+ *                                         candidate in the order [cell 0, overlap 0|1, cell 1, ...], and compacts the result into the CSR frx_problem_create
+ *                                         takes: status[n_tasks], v_off[n_tasks + 1], v_rec[3 cap_vert].  *n_vert = vertices needed; FRX_ERR_CAPACITY only when
+ *                                         that exceeds cap_vert (status and v_off are valid then).
+ *   frx_enumerate_vertices_batch_device   ONE launch on hip_stream of the current device: no copy, no synchronisation, no allocation (capturable).  Device
+ *                                         pointers; outputs v_slot[n_tasks][cap_v][3], nv[n_tasks], status[n_tasks].  The caller vouches for the tasks' ranges.
+ *   frx_corridor_slots_to_tasks_device    ONE launch of index arithmetic: tasks[n_paths][2 cap_polys - 1] from the outputs of
+ *                                         frx_corridor_generate_batch_device, record indices into h_slot viewed as one record array (cell c of path p starts at
+ *                                         (p cap_polys + c) cap_planes); positions beyond a path's 2 n_polys - 1 get count0 = 0.  So corridors -> tasks ->
+ *                                         vertices runs on one stream without the host.
+ * FRX_ERR_INVALID_ARG (reported before a device is looked for): NULL arguments, B / n_tasks / n_paths < 1, a coarse_n[b] < 1, non-monotone h_off, cap_v outside
+ * [4, 512] (the accepted vertices stay in LDS), cap_polys or cap_planes < 1.  FRX_ERR_NO_DEVICE without a device.  Not built: an O(K^3) edge-clipping
+ * enumeration - it would meet other duplicates in another order and lose the bit-for-bit referee. */
+enum { FRX_HV_OK = 0, FRX_HV_UNBOUNDED = 1, FRX_HV_FLAT = 2, FRX_HV_PLANES = 3, FRX_HV_VERTICES = 4, FRX_HV_NONFINITE = 5, FRX_HV_SKIPPED = 6 };
+#define FRX_HV_MAX_PLANES 256
+int frx_enumerate_vertices_batch(int device, int B, const int *coarse_n, const int *h_off, const double *h_rec, int cap_v, int *status, int *v_off,
+                                 int cap_vert, int *n_vert, double *v_rec);
+int frx_enumerate_vertices_batch_device(int n_tasks, const int *tasks_dev, const double *h_rec_dev, int cap_v, double *v_slot_dev, int *nv_dev,
+                                        int *status_dev, void *hip_stream);
+int frx_corridor_slots_to_tasks_device(int n_paths, int cap_polys, int cap_planes, const int *cell_planes_dev, const int *n_polys_dev, int *tasks_dev,
+                                       void *hip_stream);
+
 /* Safe-flight-corridor generation, the step upstream of frx_problem_create_from_h.
  * frx_line_segment_dilate = LineSegment3D::dilate(offset) (decomp_util/line_segment.h:31-35 with find_ellipsoid :136-214,
  * DecompBase::find_polyhedron decomp_base.h:63-83, add_local_bbox line_segment.h:47-85, obstacle filter decomp_base.h:35-40):
