@@ -844,7 +844,8 @@ class Problem:
         return out
 
     def profile_eval_tail(self, x):
-        """The same with the stamps of the evaluation's tail in [64..68] (frx_debug.h: frx_debug_profile_eval_tail); 100 MHz ticks from [40] on."""
+        """The same with the stamps of the evaluation's tail in [64..68] and of the hand-off of the penalty partials in [69..74] (frx_debug.h: frx_debug_profile_eval_tail);
+        100 MHz ticks from [40] on, except [75] and [76], which are spin counts and no times."""
         out = np.zeros(80, np.int64)
         _check(lib().frx_debug_profile_eval_tail(self.h, np.ascontiguousarray(x, dtype=np.float64), out.ctypes.data))
         return out

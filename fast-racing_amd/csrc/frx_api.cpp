@@ -704,6 +704,7 @@ static int profile_eval_cluster(frx_problem *p, const double *x, long long *out,
 int frx_debug_profile_eval_cluster(frx_problem *p, const double *x, long long *out64) { return profile_eval_cluster(p, x, out64, 0, 64); }
 // The same evaluation with the stamps of its tail behind the first 64: out80[64..68] = wave 0 behind the barrier that follows the knot adjoint, wave 0's last gradient
 // store issued, axis wave 1's last store issued, thread 0 has the verdict, thread 0 has issued `done` (100 MHz counter, as 40..48).
+// out80[69..76]: the hand-off of the penalty partials (frx_debug.h; EvalHandoff, frx_kernels.hpp).
 int frx_debug_profile_eval_tail(frx_problem *p, const double *x, long long *out80) { return profile_eval_cluster(p, x, out80, 0, FRX_STAMP_SLOTS); }
 
 // Diagnostic (tests, tuning): drives k_lbfgs_pre alone.  `iters` successive accepted steps on random (x, g) sequences of

@@ -2,6 +2,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -14,8 +16,12 @@ namespace frx {
 static bool eval_argp() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_ARGPTR"); return !(e && e[0] == '0'); }(); return on; }   // FRX_EVAL_ARGPTR=0: the by-value form (A/B)
 static bool eval_early_t() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_EARLY_T"); return !(e && e[0] == '0'); }(); return on; }   // FRX_EVAL_EARLY_T=0: the staged-durations form (A/B)
 static bool eval_tail() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_TAIL"); return !(e && e[0] == '0'); }(); return on; }   // FRX_EVAL_TAIL=0: f and `done` behind a barrier and a status trip at the kernel's end (A/B; with the two switches above at their defaults only)
+// FRX_EVAL_HANDOFF=0: the penalty partials piece-major, polled with 8-byte loads, the adjoint's multipliers requested behind the poll (A/B).  Read once per process, before the first handle
+// exists (eval_cluster_geometry): the two forms put a granule at different addresses of one buffer, and a tag is only good for the address it was written to.
+static bool eval_handoff() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_HANDOFF"); return !(e && e[0] == '0'); }(); return on && eval_argp() && eval_tail(); }
 // the instantiation the launcher takes: argument pointer (or not) x early durations (or not)
 static const void *eval_fn() {
+    if (eval_handoff()) return eval_early_t() ? (const void *)k_eval_cluster<true, true, true, true> : (const void *)k_eval_cluster<true, false, true, true>;
     if (!eval_tail() && eval_argp() && eval_early_t()) return (const void *)k_eval_cluster<true, true, false>;
     return eval_argp() ? (eval_early_t() ? (const void *)k_eval_cluster<true, true> : (const void *)k_eval_cluster<true, false>)
                        : (eval_early_t() ? (const void *)k_eval_cluster<false, true> : (const void *)k_eval_cluster<false, false>);
@@ -36,6 +42,7 @@ int eval_cluster_raise_limit(size_t bytes) {
 static int eval_pen_lds(const LaunchGeom &g) { return g.ppw * 19 + g.ppw * (g.Kmax + 1) * 4 + 64 * 21; }   // doubles per wave (penalty_body with a 64-lane group)
 int eval_cluster_geometry(LaunchGeom &g) {
     g.ev_G = 0; g.lds_ev = 0;
+    (void)eval_handoff();
     if (g.solver != SOLVER_KNOT_PCR || g.knot_threads != 64 || g.ppw < 1) return 0;
     const int ntasks = (g.maxN + g.ppw - 1) / g.ppw;
     const size_t lds = sizeof(double) * (size_t)eval_cluster_lds(g.maxN * 19, g.maxXb, g.maxVb, g.maxCN, g.pcr_steps, eval_pen_lds(g)).total;
@@ -56,6 +63,7 @@ size_t eval_cluster_args_bytes() { return sizeof(EvalClusterArgs); }
 void eval_cluster_args(const DevProblem &dp, const LaunchGeom &g, double *T, double *C, unsigned long long *ll, unsigned *words, void *out) {
     EvalClusterArgs a;
     std::memset(&a, 0, sizeof(a));
+    assert(!eval_handoff() || (reinterpret_cast<uintptr_t>(ll) & 15u) == 0);   // value-major granules travel as 16-byte stores and loads (the buffer is a device allocation of its own: 256-byte aligned)
     a.dp = dp; a.T = T; a.C = C; a.out20ll = ll; a.words = words; a.status = words + (size_t)64 * dp.B;
     a.G = g.ev_G; a.maxCN = g.maxCN; a.maxXb = g.maxXb; a.maxVb = g.maxVb; a.nsteps = g.pcr_steps; a.lpp = g.lpp; a.ppw = g.ppw; a.Kmax = g.Kmax; a.pen_lds = eval_pen_lds(g); a.maxN19 = g.maxN * 19;
     std::memcpy(out, &a, sizeof(a));
@@ -70,7 +78,10 @@ int launch_eval_cluster(const LaunchGeom &g, int B, const void *args_host, const
     if (c.test_drop_members) c.timeout_ticks = 5000ull;
     const dim3 grid(8 * g.ev_G * ((B + 7) / 8));
     const bool et = eval_early_t();
-    if (eval_argp() && args_dev) {
+    if (eval_handoff() && args_dev) {
+        if (et) hipLaunchKernelGGL((k_eval_cluster<true, true, true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+        else hipLaunchKernelGGL((k_eval_cluster<true, false, true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+    } else if (eval_argp() && args_dev) {
         if (et && !eval_tail()) hipLaunchKernelGGL((k_eval_cluster<true, true, false>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
         else if (et) hipLaunchKernelGGL((k_eval_cluster<true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
         else hipLaunchKernelGGL((k_eval_cluster<true, false>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);

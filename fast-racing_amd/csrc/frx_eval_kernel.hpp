@@ -41,7 +41,9 @@ namespace frx {
 struct EvalClusterArgs {                      // constant for the life of a handle (a copy lives in device memory: ARGP below)
     DevProblem dp;
     double *T, *C;
-    ll_u64 *out20ll;                         // [P][20] granules: the penalty partials, members -> leader (its own buffer: the round kernel's carries tags of its own)
+    ll_u64 *out20ll;                         // 20 granules per piece: the penalty partials, members -> leader (its own buffer: the round kernel's carries tags of its own).  Candidate c owns the 40 N words
+                                             // behind 40 poff[c]; in them granule (value v, piece k) lies at word 2 (v N + k) - value-major, the order the leader's lanes poll in (HO below) - or, in the
+                                             // piece-major form, at 2 (20 k + v).  One form for the life of a handle: a tag validates a word only at the address it was written for
     unsigned *words;                         // [B][64]: cluster k's 256-byte block: word 0 = gate (tag << 4 | the leader's XCD + 1: (C, T) are out), words 8 .. 8 + G - 2 = tag << 4 | XCD + 1 of
                                              // members 1 .. G-1 (written at their entry), word 32 = tag of the last completed evaluation
     unsigned *status;                        // [1] sticky error word
@@ -86,7 +88,10 @@ template <class F> struct EvalEarlySync {
 };
 // TAIL (the default; FRX_EVAL_TAIL=0 takes the other form, A/B): thread 0 of the leader stores f and `done` inside the adjoint, right behind the objective's sum
 // (EvalTail, frx_kernels.hpp); otherwise behind a workgroup barrier and a load of the global status word at the kernel's end, as until now.
-template <bool ARGP, bool ET, bool TAIL = true>
+// HO (the default; FRX_EVAL_HANDOFF=0 takes the other form, A/B; with the tail above and the argument pointer only): the hand-off of the partials laid out for its reader
+// (EvalHandoff, frx_kernels.hpp) - the members store a granule with one 16-byte store at its value-major place; the leader's waves poll with one coalesced 16-byte load
+// per granule, wave 0 two and an axis wave six, and the axis waves request the 52 multipliers of their knot in front of the poll instead of behind it.
+template <bool ARGP, bool ET, bool TAIL = true, bool HO = false>
 __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::conditional<ARGP, const EvalClusterArgs *__restrict__, EvalClusterArgs>::type arg, EvalCallArgs call) {
     const EvalClusterArgs &a = [&]() -> const EvalClusterArgs & { if constexpr (ARGP) return *arg; else return arg; }();
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -95,7 +100,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     if (k >= a.dp.B) return;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int c = k;
-    // (diagnostic, frx_debug_profile_eval_cluster: cycle stamps of cluster 0 - 40..43 the leader: entry, forward map done, adjoint done, end; 64..68 its tail, see EvalTail; 44..48 wave 0 of member 1, see penalty_wave_ll - these in ticks of the 100 MHz counter all workgroups share; 49: the leader's shader clock at entry, the origin of the bodies' own stamps 0..31)
+    // (diagnostic, frx_debug_profile_eval_cluster: cycle stamps of cluster 0 - 40..43 the leader: entry, forward map done, adjoint done, end; 64..68 its tail, see EvalTail; 70..76 its poll for the partials, see EvalHandoff; 44..48 wave 0 of member 1, see penalty_wave_ll, and 69: the gate word's value has arrived - these in ticks of the 100 MHz counter all workgroups share; 49: the leader's shader clock at entry, the origin of the bodies' own stamps 0..31)
     if (a.dp.stamps && k == 0 && wg == 0 && t == 0) { a.dp.stamps[40] = (long long)wall_clock64(); a.dp.stamps[49] = (long long)__builtin_readcyclecounter(); }
     unsigned *flag = a.words + (size_t)k * 64, *done = flag + 32;
     const int p0 = a.dp.poff[c], N = a.dp.poff[c + 1] - p0;
@@ -196,9 +201,11 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
         if (pl < npieces) penalty_lane_samples<true>(a.dp, ctl + (size_t)(task * a.ppw + pl) * 19, hS + (size_t)pl * hstride, ctl[(task * a.ppw + pl) * 19 + 18], jl, a.lpp, a.Kmax, red + lane * 21);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (mst) mst[47] = (long long)wall_clock64();
-        const unsigned gv = __hip_atomic_load(flag, FRX_RLX_AGENT);           // the leader's XCD, if it has arrived under this evaluation's tag
+        const unsigned gv = __hip_atomic_load(flag, FRX_RLX_AGENT);           // the leader's XCD, if it has arrived under this evaluation's tag (requested in front of the samples instead, the trip is worth 0.07 us: profiles/NOTES.md)
+        if (mst) { asm volatile("" :: "v"(gv)); mst[69] = (long long)wall_clock64(); }   // (the word's value is in its register)
         const bool wt = my_xcc == 0u || (gv >> 4) != tag || (gv & 15u) != my_xcc;   // plain stores when the leader runs on this XCD (its L2 is the meeting point), write-through otherwise
-        penalty_reduce<true>(red, npieces, a.lpp, nullptr, lane, 64, wt, a.out20ll + (size_t)gp0 * 40, tag);
+        if constexpr (HO) penalty_reduce<true, true>(red, npieces, a.lpp, nullptr, lane, 64, wt, a.out20ll + (size_t)p0 * 40, tag, N, task * a.ppw);
+        else penalty_reduce<true>(red, npieces, a.lpp, nullptr, lane, 64, wt, a.out20ll + (size_t)gp0 * 40, tag);
         if (mst) mst[48] = (long long)wall_clock64();
         return;
     }
@@ -208,7 +215,8 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     const LineSearchTap tap{nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr};
     // the tail (EvalTail): f and `done` leave from inside the adjoint; the diagnostic's stamps 64.. of cluster 0 go with it
     const EvalTail tl{verdict, call.f, done, tag, call.status_host, k == 0 ? a.dp.stamps : nullptr, TAIL};
-    backward_knot_body<true, 64, 0, EvalTail>(a.dp, call.x, a.T, a.C, nullptr, call.f, call.g, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, a.nsteps, tap, c, ev, ctl, &ro, &tl);
+    const EvalHandoff<HO> ho{k == 0 ? a.dp.stamps : nullptr};
+    backward_knot_body<true, 64, 0, EvalTail, EvalHandoff<HO>>(a.dp, call.x, a.T, a.C, nullptr, call.f, call.g, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, a.nsteps, tap, c, ev, ctl, &ro, &tl, &ho);
     if (a.dp.stamps && k == 0 && t == 0) a.dp.stamps[42] = (long long)wall_clock64();
     if constexpr (TAIL) {
         if (a.dp.stamps && k == 0 && t == 0) a.dp.stamps[43] = (long long)wall_clock64();

@@ -114,6 +114,18 @@ struct GranuleOut { ll_u64 *ll; unsigned tag; unsigned *gate; unsigned gate_val;
 // otherwise the caller does.  (An LDS pointer by type: through a plain pointer in a struct the read is a flat load, which counts on vmcnt.)  st (optional): 100 MHz stamps - [64] wave 0 behind the barrier, [65] wave 0's last gradient store issued, [66] axis wave 1's last store
 // issued, inl: [67] verdict known, [68] done issued.  A struct of its own behind a template flag, as GranuleOut: fields of ResidentOps move k_round's register allocation.
 struct EvalTail { volatile __attribute__((address_space(3))) unsigned *verdict; double *f; unsigned *done; unsigned tag; unsigned *status_host; long long *st; bool inl; };
+// The one-launch evaluation's hand-off of the penalty partials (penalty_reduce<.., TR>, backward_knot_wsp64<.., HO>: frx_eval_kernel.hpp), a struct of its own behind a
+// template flag for the same reason.  TR: the granules of a candidate lie TRANSPOSED, granule (value v, piece k) at word 2 (v N + k) behind the candidate's 40 poff words
+// (N its piece count) instead of 2 (20 k + v): lane k of a polling wave reads piece k, so a wave's load of one value is 64 consecutive granules - 1 KB, eight cache
+// lines - where the piece-major form touches 64 lines per load instruction, and both words of a granule come in ONE 16-byte load (each word still carries its own tag:
+// a torn load is caught as before).  Wave 0 polls its two granules, an axis wave its six, and an axis lane requests the 52 multipliers of its knot IN FRONT of the poll
+// (the leader of this kernel idles there with one wave per SIMD and the whole register file: 232 VGPRs, nothing spilled - the resident kernel's leader paid 190 spilled
+// registers for the same move, which is why it stays behind this flag).  st (optional): 100 MHz stamps - [70] wave 0 enters the poll, [71] has left
+// it, [72] / [73] the same for axis wave 1, [74] axis wave 1's Hermite adjoint is done (the twin of the shader-clock stamp 26); [75] / [76] spins of lane 0 of wave 0 /
+// of axis wave 1.
+template <bool TR> struct EvalHandoff { static constexpr bool tr = TR; long long *st; };
+template <class HO> struct ho_transposed { static constexpr bool value = HO::tr; };
+template <> struct ho_transposed<void> { static constexpr bool value = false; };
 
 // Coalesced staging global -> LDS with every load of a trip in flight before the first LDS store.  The plain loop
 // `for (i = k; i < n; i += nthr) dst[i] = src[i]` compiles to load / s_waitcnt vmcnt(0) / ds_write per element even under
@@ -358,8 +370,11 @@ __device__ __forceinline__ void penalty_lane_samples(const DevProblem &dp, const
     }
 }
 // fixed-order reduction over the samples of each piece (lane slots red[lane * 21 ..]): thread = (piece of the group, value)
-template <bool SH>
-__device__ __forceinline__ void penalty_reduce(const double *red, int npieces, int lpp, double *__restrict__ out, int lane, int nthr, bool wt, ll_u64 *out_ll = nullptr, unsigned ll_tag = 0) {
+// TR (the one-launch evaluation, EvalHandoff): out_ll is the CANDIDATE's first granule word, the group's pieces are its pieces tr_k0 .. of tr_N, and the granule of
+// (value v, piece k) goes to word 2 (v tr_N + k) as one 16-byte store (write-through: two 8-byte ones, each word validates itself).
+template <bool SH, bool TR = false>
+__device__ __forceinline__ void penalty_reduce(const double *red, int npieces, int lpp, double *__restrict__ out, int lane, int nthr, bool wt, ll_u64 *out_ll = nullptr, unsigned ll_tag = 0,
+                                               int tr_N = 0, int tr_k0 = 0) {
     for (int idx = lane; idx < npieces * 20; idx += nthr) {
         const int p2 = idx / 20, v = idx - p2 * 20;
         const double *src = red + (p2 * lpp) * 21 + v;
@@ -378,6 +393,16 @@ __device__ __forceinline__ void penalty_reduce(const double *red, int npieces, i
         }
 #pragma unroll 4
         for (; l < lpp; l++) s += src[l * 21];
+        if constexpr (TR) {
+            ll_u64 *slot = out_ll + 2 * ((size_t)v * tr_N + (tr_k0 + p2));
+            if (wt) rk_ll_put(slot, s, ll_tag, true);
+            else {
+                const ll_u64 bits = (ll_u64)__double_as_longlong(s), tg = (ll_u64)ll_tag << 32;
+                typedef ll_u64 ll_v2 __attribute__((ext_vector_type(2)));
+                ll_v2 w; w.x = (bits & 0xFFFFFFFFull) | tg; w.y = (bits >> 32) | tg;
+                *(ll_v2 *)slot = w;                                             // (16-byte aligned: frx_device_eval.hip checks the base; 40 poff words and 2 (v N + k) words are multiples of 16 bytes)
+            }
+        } else
         if (SH && out_ll) rk_ll_put(out_ll + 2 * idx, s, ll_tag, wt);      // resident caller: the partials travel as granules that the adjoint polls (no drain, no arrival count in front of it)
         else stg<SH>(out + idx, s, wt);
     }
@@ -2071,12 +2096,13 @@ __device__ __forceinline__ void backward_knot_wsp64_stage(const DevProblem &dp, 
     FRX_STAMP(24);
 }
 
-template <bool SH, class TL = void>
+template <bool SH, class TL = void, class HO = void>
 __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const double *__restrict__ x, const double *__restrict__ Tin,
                                 const double *__restrict__ Cin, const double *__restrict__ out20, double *__restrict__ f,
                                 double *__restrict__ g, int maxCN, int maxXb, int maxVb, const double *__restrict__ pcrw, int nsteps,
-                                const LineSearchTap &tap, int b, double *sm, const double *ct_lds, const ResidentOps *ro, const TL *tl = nullptr) {
+                                const LineSearchTap &tap, int b, double *sm, const double *ct_lds, const ResidentOps *ro, const TL *tl = nullptr, const HO *ho = nullptr) {
     constexpr bool TAIL = !std::is_void<TL>::value;     // the one-launch evaluation's tail (EvalTail); nothing of it is compiled into the other callers
+    constexpr bool HOST = !std::is_void<HO>::value, HOTR = ho_transposed<HO>::value;   // its hand-off of the partials (EvalHandoff): the stamps; the transposed granules
     const int nrow = 64, nthr = 256;
     const int k = threadIdx.x, kk = k & 63, t2 = k - 64;
     const int wave = __builtin_amdgcn_readfirstlane(k >> 6);
@@ -2239,6 +2265,17 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
             ka_ih3 = ih3; ka_ih4 = ih4;
         }
     }
+    if constexpr (HOTR) {
+        // (EvalHandoff) the 52 multipliers of this knot requested IN FRONT of the poll: their LDS trips run under the wait instead of under the Hermite adjoint
+        if (wave != 0 && nst <= 6) {
+#pragma unroll
+            for (int st = 0; st < 6; st++)
+#pragma unroll
+                for (int i = 0; i < 8; i++) ab[st][i] = pw[kc * pws + (st < nst ? st : 0) * 8 + i];
+#pragma unroll
+            for (int i = 0; i < 4; i++) Di[i] = pw[kc * pws + nsteps * 8 + i];
+        }
+    }
     if (SH && ro && ro->o20ll) {
         // Resident caller: the 20 partials of piece kp arrive as granules tagged with the number of this evaluation; lane kk of wave 0 polls {cost, d/dT},
         // lane kk of an axis wave its six d/dc - the workgroups that integrate the penalty neither drain nor count in front of this read, and the leader
@@ -2249,12 +2286,38 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         constexpr int NG = 6;
         ll_u64 w[NG][2];
         const int ng = wave == 0 ? 2 : 6, gbase = wave == 0 ? 0 : 2 + (wave - 1), gstep = wave == 0 ? 1 : 3;
+        unsigned nspin = 0;                                                  // (EvalHandoff's stamps: the spins of this lane)
+        if constexpr (HOST) { if (ho->st && kk == 0 && wave <= 1) ho->st[70 + 2 * wave] = (long long)wall_clock64(); }
         for (unsigned spins = 0;; spins++) {
+            if constexpr (HOTR) {
+                // EvalHandoff, transposed: granule (v, kp) at word 2 (v N + kp) of the candidate - lane by lane consecutive; one 16-byte L1-bypassing load per granule, wave 0 two
+                // of them.  The loads are unconditional: EVERY lane's address has to lie inside the candidate's own 40 N words - a lane without a piece has kp = 0 (clamped above)
+                // and reads piece 0's granules, whose values it does not use.
+                typedef unsigned ll_v4u __attribute__((ext_vector_type(4)));
+                const ll_u64 *ogt = ro->o20ll + 40 * (size_t)p0 + 2 * ((size_t)gbase * N + kp);
+                const size_t ogs = 2 * (size_t)gstep * N;
+                ll_v4u r[NG];
+                if (wave == 0) {
+                    asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %3, off sc1\n\ts_waitcnt vmcnt(0)"
+                                 : "=&v"(r[0]), "=&v"(r[1]) : "v"(ogt), "v"(ogt + ogs) : "memory");
+#pragma unroll
+                    for (int q = 2; q < NG; q++) r[q] = r[1];
+                } else {
+                    asm volatile("global_load_dwordx4 %0, %6, off sc1\n\tglobal_load_dwordx4 %1, %7, off sc1\n\tglobal_load_dwordx4 %2, %8, off sc1\n\t"
+                                 "global_load_dwordx4 %3, %9, off sc1\n\tglobal_load_dwordx4 %4, %10, off sc1\n\tglobal_load_dwordx4 %5, %11, off sc1\n\ts_waitcnt vmcnt(0)"
+                                 : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4]), "=&v"(r[5])
+                                 : "v"(ogt), "v"(ogt + ogs), "v"(ogt + 2 * ogs), "v"(ogt + 3 * ogs), "v"(ogt + 4 * ogs), "v"(ogt + 5 * ogs) : "memory");
+                }
+#pragma unroll
+                for (int q = 0; q < NG; q++) { w[q][0] = (ll_u64)r[q].x | ((ll_u64)r[q].y << 32); w[q][1] = (ll_u64)r[q].z | ((ll_u64)r[q].w << 32); }
+            } else {
 #pragma unroll
             for (int q = 0; q < NG; q++) {
                 const ll_u64 *g2 = og + 2 * (gbase + gstep * (q < ng ? q : ng - 1));
                 w[q][0] = __hip_atomic_load(g2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); w[q][1] = __hip_atomic_load(g2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            }
+            if constexpr (HOST) nspin = spins + 1u;
             bool all = true;
 #pragma unroll
             for (int q = 0; q < NG; q++) all = all && rk_ll_ok(w[q][0], w[q][1], tg);
@@ -2272,6 +2335,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
 #pragma unroll
             for (int q = 0; q < 6; q++) cbq[q] = rk_ll_value(w[q][0], w[q][1]);
         }
+        if constexpr (HOST) { if (ho->st && kk == 0 && wave <= 1) { asm volatile("" :: "v"(w[1][1])); ho->st[71 + 2 * wave] = (long long)wall_clock64(); ho->st[75 + wave] = (long long)nspin; } }
     }
     if (wave == 0) {
         if (piece) { costAcc = o0 + jerkE; gTl = o1 + jerkT; }
@@ -2283,9 +2347,9 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         if (kk < cN) gCo[kk] = (double)(r_iv + (r_fb << 10));
         if (tap.early_cmd && k == 0) { early_word = __hip_atomic_load(tap.early_cmd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); early_step = __hip_atomic_load(tap.early_cmd + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }   // behind the wave's first loads (see LineSearchTap)
     } else {
-        if (nst <= 6) {
+        if (!HOTR && nst <= 6) {
             // every multiplier of this knot (they were all saved by the forward pass), requested first: a step of the solve below is then one lane exchange,
-            // not two LDS round trips, and these trips run under the Hermite adjoint.  (In front of the poll they would be 104 more live registers there.)
+            // not two LDS round trips, and these trips run under the Hermite adjoint.  (In front of the poll they would be 104 more live registers there: EvalHandoff does that, for the one-launch evaluation alone.)
 #pragma unroll
             for (int st = 0; st < 6; st++)
 #pragma unroll
@@ -2312,6 +2376,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         double r0 = 0.0, r1 = 0.0, pbk = 0.0;
         if (act) { r0 = db[1] + eVu; r1 = db[2] + eAu; pbk = db[0] + ePu; }      // right-hand side of K mu = wbar; direct d f / d p_k (both adjacent pieces)
         FRX_STAMP_AX(26);
+        if constexpr (HOST) { if (ho->st && k == 64) { asm volatile("" :: "v"(r0), "v"(r1), "v"(pbk)); ho->st[74] = (long long)wall_clock64(); } }
         // ---- mu = K^-1 wbar with the multipliers of the forward reduction (K is symmetric), neighbours by lane shifts ----
         double muv = 0.0, mua = 0.0;                                   // zero at the fixed end knots
         if (nst <= 6) {
@@ -2551,15 +2616,15 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
     FRX_STAMP(24);
 }
 
-// SH: out20 (and T, C) were written by workgroups of the same launch.  TL (EvalTail, the one-launch evaluation only): see backward_knot_wsp64.
-template <bool SH, int NR = 0, int RB = 0, class TL = void>
+// SH: out20 (and T, C) were written by workgroups of the same launch.  TL, HO (EvalTail, EvalHandoff: the one-launch evaluation only): see backward_knot_wsp64.
+template <bool SH, int NR = 0, int RB = 0, class TL = void, class HO = void>
 __device__ __forceinline__ void backward_knot_body(const DevProblem &dp, const double *__restrict__ x, const double *__restrict__ Tin,
                                 const double *__restrict__ Cin, const double *__restrict__ out20, double *__restrict__ f,
                                 double *__restrict__ g, int maxCN, int maxXb, int maxVb, int nrow_rt, const double *__restrict__ pcrw, int nsteps,
-                                const LineSearchTap &tap, int b, double *sm, const double *ct_lds = nullptr, const ResidentOps *ro = nullptr, const TL *tl = nullptr) {
+                                const LineSearchTap &tap, int b, double *sm, const double *ct_lds = nullptr, const ResidentOps *ro = nullptr, const TL *tl = nullptr, const HO *ho = nullptr) {
     const int nrow = NR > 0 ? NR : nrow_rt;
     if (NR == 64 || (NR == 0 && nrow == 64 && blockDim.x == 256)) {              // <= 64 pieces: one wave per axis
-        if (SH) backward_knot_wsp64<SH, TL>(dp, x, Tin, Cin, out20, f, g, maxCN, maxXb, maxVb, pcrw, nsteps, tap, b, sm, ct_lds, ro, tl);       // resident caller: the order built around the poll
+        if (SH) backward_knot_wsp64<SH, TL, HO>(dp, x, Tin, Cin, out20, f, g, maxCN, maxXb, maxVb, pcrw, nsteps, tap, b, sm, ct_lds, ro, tl, ho);       // resident caller: the order built around the poll
         else backward_knot_wsp64_stage<SH, RB>(dp, x, Tin, Cin, out20, f, g, maxCN, maxXb, maxVb, pcrw, nsteps, tap, b, sm, ct_lds, ro);
         return;
     }

@@ -72,7 +72,9 @@ int frx_eval_launch_time(frx_problem *p, const double *x, int reps, double *out_
  * granules staged, samples done, partials out. */
 int frx_debug_profile_eval_cluster(frx_problem *p, const double *x, long long *out64);
 /* The same with the stamps of the evaluation's tail behind the first 64 (100 MHz counter, as 40..48): out80[64] wave 0 of the leader behind the barrier that follows
- * the knot adjoint, [65] its last gradient store issued, [66] axis wave 1's last store issued, [67] thread 0 has the verdict, [68] thread 0 has issued `done`. */
+ * the knot adjoint, [65] its last gradient store issued, [66] axis wave 1's last store issued, [67] thread 0 has the verdict, [68] thread 0 has issued `done`;
+ * the hand-off of the penalty partials: [69] wave 0 of the first member has the gate word's value, [70] / [71] wave 0 of the leader enters / has left its poll for the
+ * partials, [72] / [73] the same for axis wave 1, [74] axis wave 1's Hermite adjoint is done, [75] / [76] NOT times: the spins of lane 0 of wave 0 / of axis wave 1. */
 int frx_debug_profile_eval_tail(frx_problem *p, const double *x, long long *out80);
 
 /* Diagnostic: runs one evaluation at x and returns shader-clock stamps taken at the phase boundaries of candidate 0's
