@@ -67,6 +67,7 @@ ABI_SYMBOLS = [
     "frx_dilate_batch", "frx_multi_create", "frx_multi_destroy", "frx_multi_info", "frx_multi_layout", "frx_multi_initial_guess", "frx_multi_optimize", "frx_multi_last_exchange",
     "frx_map_mark_cloud", "frx_map_is_blocked", "frx_grid_search", "frx_jps_plan", "frx_route_plan",
     "frx_trajectory_check", "frx_trajectory_check_device", "frx_trajectory_sample", "frx_trajectory_sample_device",
+    "frx_trajectory_extrema", "frx_trajectory_extrema_device",
     "frx_trajectory_clearance", "frx_trajectory_clearance_workspace", "frx_trajectory_clearance_device",
     "frx_corridor_generate_batch", "frx_corridor_generate_batch_device",
     "frx_enumerate_vertices_batch", "frx_enumerate_vertices_batch_device", "frx_corridor_slots_to_tasks_device",
@@ -83,6 +84,8 @@ DEBUG_SYMBOLS = [
 CHECK_FIELDS = ("corridor", "speed", "thrust_min", "thrust_max", "body_rate", "acc", "worst_t", "worst_k")
 CHECK_MAX_INTERVALS = 16384
 CHECK_FLAG_CORRIDOR, CHECK_FLAG_SPEED, CHECK_FLAG_THRUST_MIN, CHECK_FLAG_THRUST_MAX, CHECK_FLAG_BODY_RATE, CHECK_FLAG_NONFINITE = 1, 2, 4, 8, 16, 32
+# frx_trajectory_extrema (include/frx.h): fields of a row; its flags are the CHECK_FLAG_* bits (no CORRIDOR bit)
+EXTREMA_FIELDS = ("speed", "acc", "thrust_min", "thrust_max", "body_rate", "t_speed", "t_acc", "t_thrust_min", "t_thrust_max", "t_body_rate")
 # frx_trajectory_clearance (include/frx.h): fields of a row, flag bits, the largest cloud; CLEAR_TILE sample states and CLEAR_PASS cloud points are what a
 # workgroup of the kernel holds at a time (fast-racing_amd/csrc/frx_device.hpp), the sizes at which it takes another turn of a loop
 CLEAR_FIELDS = ("ell", "dist", "worst_t", "worst_i")
@@ -167,6 +170,8 @@ def lib():
         L.frx_forward.argtypes = [C.c_void_p, _dp, _dp, _dp]
         L.frx_trajectory_check.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_trajectory_check_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_extrema.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_extrema_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_trajectory_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         L.frx_trajectory_sample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_trajectory_clearance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -747,6 +752,23 @@ class Problem:
     def trajectory_check_device(self, T_ptr: int, C_ptr: int, out_ptr: int, intervals: int = 256, stream: int = 0):
         """frx_trajectory_check_device: the piece rows (P x 8 doubles at out_ptr) as one launch on `stream`, device pointers, no synchronisation."""
         _check(lib().frx_trajectory_check_device(self.h, T_ptr, C_ptr, int(intervals), out_ptr, stream))
+
+    def trajectory_extrema(self, T, Cf):
+        """Exact per-piece extrema of speed, acceleration, thrust and body rate of the batch (T, C) with the times they are attained at
+        (frx_trajectory_extrema; nothing is sampled, the corridor is not covered): dict(piece (P, 10), cand (B, 10), flags (B,) uint32 of
+        CHECK_FLAG_* bits) plus the candidate rows' fields by name (EXTREMA_FIELDS)."""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1); Cf = np.ascontiguousarray(Cf, dtype=np.float64).reshape(-1)
+        if T.size != self.P or Cf.size != 18 * self.P:
+            raise ValueError(f"trajectory_extrema: expected {self.P} durations and {18 * self.P} coefficients, got {T.size} and {Cf.size}")
+        piece = np.zeros((self.P, 10)); cand = np.zeros((self.B, 10)); flags = np.zeros(self.B, np.uint32)
+        _check(lib().frx_trajectory_extrema(self.h, T.ctypes.data, Cf.ctypes.data, piece.ctypes.data, cand.ctypes.data, flags.ctypes.data))
+        out = dict(piece=piece, cand=cand, flags=flags)
+        out.update({name: cand[:, i] for i, name in enumerate(EXTREMA_FIELDS)})
+        return out
+
+    def trajectory_extrema_device(self, T_ptr: int, C_ptr: int, out_ptr: int, stream: int = 0):
+        """frx_trajectory_extrema_device: the piece rows (P x 10 doubles at out_ptr) as one launch on `stream`, device pointers, no synchronisation."""
+        _check(lib().frx_trajectory_extrema_device(self.h, T_ptr, C_ptr, out_ptr, stream))
 
     def trajectory_sample(self, T, Cf, n_samples: int, dt: float = 0.0, t0: float = 0.0, times=None):
         """Every candidate of the batch (T, C) at n_samples times with its SE(3) outputs (frx_trajectory_sample): times (B, n_samples) from each

@@ -231,6 +231,7 @@ struct frx_problem {
     // pinned staging
     PinBuf<double> h_x, h_f, h_g, h_T, h_C, h_out20;
     DevBuf<double> d_check;                                 // [P][8] rows of frx_trajectory_check, allocated on its first call
+    DevBuf<double> d_extrema;                               // [P][10] rows of frx_trajectory_extrema, allocated on its first call
     DevBuf<double> d_sample;                                // frx_trajectory_sample: [B][S][20] rows, then [B][S] times; grown as needed
     DevBuf<double> d_clear;                                 // frx_trajectory_clearance: [P][4] rows, the cloud [n_obs][3], then the partials [P][chunks][4]; grown as needed
     int clear_chunk = 0;                                    // tests (frx_debug_set_clear_chunk): > 0 = cloud points per chunk, 0 = the library's own split
@@ -1127,6 +1128,58 @@ int frx_trajectory_check(frx_problem *p, const double *T, const double *C, int i
             if (o[FRX_CHECK_THRUST_MAX] > p->cfg.thr_acc_max) fl |= FRX_CHECK_FLAG_THRUST_MAX;
             if (o[FRX_CHECK_BODY_RATE] > p->cfg.body_rate_max) fl |= FRX_CHECK_FLAG_BODY_RATE;
             for (int f = 0; f < FRX_CHECK_FIELDS; f++)
+                if (!std::isfinite(o[f])) fl |= FRX_CHECK_FLAG_NONFINITE;
+            flags[b] = fl;
+        }
+    }
+    return FRX_OK;
+}
+
+int frx_trajectory_extrema_device(frx_problem *p, const double *T_dev, const double *C_dev, double *piece_out_dev, void *hip_stream) {
+    if (!p || !T_dev || !C_dev || !piece_out_dev) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    HIP_TRY((hipError_t)frx::launch_extrema(p->P, p->dp.pc.gAcc, T_dev, C_dev, piece_out_dev, hip_stream));
+    return FRX_OK;
+}
+
+int frx_trajectory_extrema(frx_problem *p, const double *T, const double *C, double *piece_out, double *cand_out, unsigned *flags) {
+    static_assert(FRX_EXTREMA_FIELDS == (int)frx::EXTREMA_FIELDS && FRX_EXTREMA_FIELDS <= 20, "the rows fit the P x 20 staging");
+    if (!p || !T || !C || !cand_out) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n_rows = (size_t)FRX_EXTREMA_FIELDS * p->P;
+    if (!p->d_extrema.p) HIP_TRY(p->d_extrema.alloc(n_rows));
+    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
+    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
+    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+    const int rc = frx_trajectory_extrema_device(p, p->d_T.p, p->d_C.p, p->d_extrema.p, p->stream);
+    if (rc != FRX_OK) return rc;
+    double *rows = p->h_out20.p;                                            // (P x 20 doubles of staging: the P x 10 rows fit)
+    HIP_TRY(hipMemcpyAsync(rows, p->d_extrema.p, sizeof(double) * n_rows, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (piece_out) std::memcpy(piece_out, rows, sizeof(double) * n_rows);
+    // per candidate, in piece order: a later piece replaces on strict > (< for THRUST_MIN) or when it is not a number, and a field that is not a number
+    // stays; the time goes with the value, counted from the candidate's start on the prefix of durations summed left to right as frx_trajectory_check sums it
+    for (int b = 0; b < p->B; b++) {
+        double *o = cand_out + (size_t)FRX_EXTREMA_FIELDS * b;
+        double t0 = 0.0;
+        for (int gp = p->poff[b]; gp < p->poff[b + 1]; gp++) {
+            const double *r = rows + (size_t)FRX_EXTREMA_FIELDS * gp;
+            for (int f = 0; f < 5; f++) {
+                const double a = o[f], c = r[f];
+                const bool better = f == FRX_EXTREMA_THRUST_MIN ? c < a : c > a;
+                if (gp == p->poff[b] || (a == a && (better || c != c))) { o[f] = c; o[5 + f] = t0 + r[5 + f]; }
+            }
+            t0 += T[gp];
+        }
+        if (flags) {
+            unsigned fl = 0u;
+            if (o[FRX_EXTREMA_SPEED] > p->cfg.vel_max) fl |= FRX_CHECK_FLAG_SPEED;
+            if (o[FRX_EXTREMA_THRUST_MIN] < p->cfg.thr_acc_min) fl |= FRX_CHECK_FLAG_THRUST_MIN;
+            if (o[FRX_EXTREMA_THRUST_MAX] > p->cfg.thr_acc_max) fl |= FRX_CHECK_FLAG_THRUST_MAX;
+            if (o[FRX_EXTREMA_BODY_RATE] > p->cfg.body_rate_max) fl |= FRX_CHECK_FLAG_BODY_RATE;
+            for (int f = 0; f < FRX_EXTREMA_FIELDS; f++)
                 if (!std::isfinite(o[f])) fl |= FRX_CHECK_FLAG_NONFINITE;
             flags[b] = fl;
         }

@@ -95,6 +95,11 @@ int check_geometry(int intervals, int Kmax, int *lpp, int *ppw);
 // out: [P][8] (frx.h FRX_CHECK_*) of the pieces (T, C) against the handle's corridor blocks and limits; T / C / out are device pointers
 int launch_check(const DevProblem &dp, int Kmax, const double *T, const double *C, int intervals, double *out, void *stream);
 
+// ---- exact per-piece extrema of speed, acceleration, thrust and body rate (frx_extrema_kernel.hpp) ----
+enum { EXTREMA_FIELDS = 10 };
+// out: [P][10] (frx.h FRX_EXTREMA_*) of the pieces (T, C) under gravity g_acc; T / C / out are device pointers.  One launch, no dynamic LDS.
+int launch_extrema(int P, double g_acc, const double *T, const double *C, double *out, void *stream);
+
 // ---- batched sampling with SE(3) outputs (frx_sample_kernel.hpp) ----
 // 1 when candidates of up to maxN fine pieces fit the kernel's LDS
 int sample_fits(int maxN);

@@ -315,6 +315,44 @@ int frx_traj_max_rates(int n_pieces, const double *T, const double *C, double *m
 int frx_trajectory_check(frx_problem *p, const double *T, const double *C, int intervals, double *piece_out, double *cand_out, unsigned *flags);
 int frx_trajectory_check_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, double *piece_out_dev, void *hip_stream);
 
+/* Exact extrema of the four dynamic quantities of a batch of results, on the device.  frx_trajectory_check samples, so a limit broken between two of
+ * its samples is reported as kept; these entries do not sample.  Under the flatness map of CPU.hpp:260-299 |v|^2, |a|^2 and |h|^2 = |a + g e3|^2
+ * are polynomials in t and omega_xy^2 = |h x j|^2 / |h|^4 (j = dh/dt) is a rational function of t, so a piece's extrema are values at the roots of
+ * a known polynomial - the derivative of the squared norm; N'Q - 2NQ' (degree 13) for omega_xy^2 = N / Q^2 - and at the piece's two ends.  The
+ * roots are found as frx_traj_max_rates finds them (every sign change on the piece, bracketed by the derivative's roots and bisected down to
+ * adjacent doubles).  Fields of a row (FRX_EXTREMA_FIELDS doubles):
+ *   FRX_EXTREMA_SPEED       max |v|        FRX_EXTREMA_ACC         max |a|
+ *   FRX_EXTREMA_THRUST_MIN  min |h|        FRX_EXTREMA_THRUST_MAX  max |h|
+ *   FRX_EXTREMA_BODY_RATE   max |omega_xy| (the quantity the body-rate penalty and FRX_CHECK_BODY_RATE limit)
+ *   FRX_EXTREMA_T_SPEED .. FRX_EXTREMA_T_BODY_RATE   the local time in [0, T] at which each of the five is attained, in the same order: the
+ *                           first one in the order (roots ascending, then 0, then T) on ties
+ * SPEED and ACC are frx_traj_max_rates' numbers bit for bit wherever that function does not take its early-out.  It returns 0 for a piece whose
+ * |v|^2 (|a|^2) has a numerically zero derivative - the reference's rule, trajectory.hpp:192-195 - so a piece of constant velocity (3, -4, 0)
+ * reports speed 0 there; a certificate must not, so here the two ends are always candidates and that piece reports 5 at time 0.  A piece whose T
+ * is not finite or <= 0, or that has a coefficient that is not finite, has all ten fields NaN (frx_traj_max_rates drops a NaN in its max and
+ * reports 0); a value that is not a number - the body rate where h = 0 - makes its field NaN.
+ * A candidate's row reduces its pieces in piece order (max; min for THRUST_MIN; the first piece wins a tie, NaN propagates); its times count
+ * from the candidate's start.  Flags per candidate: FRX_CHECK_FLAG_SPEED / THRUST_MIN / THRUST_MAX / BODY_RATE / NONFINITE against the handle's
+ * own limits with no slack (ACC is not limited).  The corridor is NOT covered: the body's reach past a face is not polynomial in t; judge it
+ * with frx_trajectory_check and frx_trajectory_clearance.  Rows are bit-identical run to run and independent of the rest of the batch.
+ *   frx_trajectory_extrema        blocking: T[total fine pieces], C[total fine pieces x 18] on the host as frx_optimize returns them;
+ *                                 piece_out (P x 10) and flags (B) may be NULL, cand_out (B x 10) may not.
+ *   frx_trajectory_extrema_device a pure launch on the caller's stream (no copy, no synchronisation, no allocation): piece rows only, device pointers.
+ * Serves both kinds of handle.  FRX_ERR_INVALID_ARG for a NULL argument, reported before a device is looked for; FRX_ERR_NO_DEVICE without one. */
+#define FRX_EXTREMA_FIELDS 10
+#define FRX_EXTREMA_SPEED 0
+#define FRX_EXTREMA_ACC 1
+#define FRX_EXTREMA_THRUST_MIN 2
+#define FRX_EXTREMA_THRUST_MAX 3
+#define FRX_EXTREMA_BODY_RATE 4
+#define FRX_EXTREMA_T_SPEED 5
+#define FRX_EXTREMA_T_ACC 6
+#define FRX_EXTREMA_T_THRUST_MIN 7
+#define FRX_EXTREMA_T_THRUST_MAX 8
+#define FRX_EXTREMA_T_BODY_RATE 9
+int frx_trajectory_extrema(frx_problem *p, const double *T, const double *C, double *piece_out, double *cand_out, unsigned *flags);
+int frx_trajectory_extrema_device(frx_problem *p, const double *T_dev, const double *C_dev, double *piece_out_dev, void *hip_stream);
+
 /* Batched sampling of results with their SE(3) outputs, on the device.  The reference's traj_server evaluates one PolynomialTrajectory message at
  * control rate (traj_server.cpp:397-456: position, velocity, acceleration, jerk) and its controller derives attitude and thrust from the
  * acceleration; frx_msg_sample is that call for one time.  These entries sample every candidate of the handle's batch at S = n_samples times
