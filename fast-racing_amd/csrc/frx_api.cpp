@@ -275,8 +275,8 @@ struct frx_problem {
     DevBuf<unsigned long long> d_ev_ll; unsigned *d_ev_words = nullptr;   // one allocation: [40 P] granule words, then the [64 B + 1] control words
     int eval_fused = 0, eval_fused_G = 0, eval_fused_stamps = 0;
     unsigned long long eval_fused_ticks = 25000000ull;      // bound of every wait inside the launch, ticks of the 100 MHz counter: 250 ms (a healthy evaluation takes ~20 us; FRX_EVAL_TIMEOUT_MS)
-    std::vector<unsigned char> ev_args, ev_args_up;         // the one-launch evaluation's constant arguments (frx::eval_cluster_args): as they should be / as the device copy holds them
-    DevBuf<unsigned char> d_ev_args;
+    std::vector<unsigned char> ev_args, ev_args_st;         // the one-launch evaluation's constant arguments (frx::eval_cluster_args), host copies: without / with the stamps pointer
+    DevBuf<unsigned char> d_ev_args, d_ev_args_st;          // their device copies: uploaded at create / by the diagnostic that sets the pointer (profile_eval_cluster) - never by an evaluation
     PinBuf<unsigned> h_ev_status;                           // mapped host word: the code of an expired wait, written by the leader that saw it - launch_eval reads it without a synchronisation
     unsigned eval_fused_code = 0;                           // the code that retired the one-launch form on this handle (0: none)
     // one launch per evaluation for LARGE batches (frx_solo_kernel.hpp: one workgroup per candidate): 0 = never, 1 = from eval_solo_min_B candidates on (default), 2 = always
@@ -301,14 +301,12 @@ int launch_eval(frx_problem *p, const double *x_dev, double *f_dev, double *g_de
     auto solo = [&]() { return frx::launch_eval_solo(p->dp, p->geo, x_dev, p->d_T.p, p->d_C.p, p->d_out20.p, f_dev, g_dev, st, p->tap_d, p->tap_flags, p->tap_res, p->tap_arrive, p->tap_flag, p->tap_round); };
     if (solo_ok && p->eval_solo == 2) return solo();                          // (forced: tests and measurements at batch sizes the other forms would take)
     if (backward && p->eval_fused && p->geo.solver == frx::SOLVER_KNOT_PCR && !p->tap_d && !p->dp.cand_active && (!p->dp.stamps || p->eval_fused_stamps)) {
-        // the handle's constant arguments live in device memory (uploaded at create); they only change when a diagnostic switches the cycle stamps on or off -
-        // a synchronous copy then (never inside somebody's capture: the diagnostics are blocking calls of their own)
-        frx::eval_cluster_args(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_ev_ll.p, p->d_ev_words, p->ev_args.data());
-        if (p->ev_args != p->ev_args_up) {
-            if (hipMemcpy(p->d_ev_args.p, p->ev_args.data(), p->ev_args.size(), hipMemcpyHostToDevice) != hipSuccess) return (int)hipErrorUnknown;
-            p->ev_args_up = p->ev_args;
-        }
-        return frx::launch_eval_cluster(p->geo, p->B, p->ev_args.data(), p->d_ev_args.p, x_dev, f_dev, g_dev, p->eval_fused_ticks, st, p->h_ev_status.p);
+        // the handle's constant arguments live in device memory, in TWO copies: the one uploaded at create (no stamps pointer) and the one a diagnostic uploads
+        // before it switches the cycle stamps on.  A launch picks the copy with the kernel's instantiation (launch_eval_cluster) and never copies anything itself:
+        // the caller may be capturing, and a graph captured before a diagnostic still points at arguments nobody has touched since.
+        const bool stamped = p->dp.stamps != nullptr;
+        if (stamped && !p->d_ev_args_st.p) return (int)hipErrorInvalidValue;
+        return frx::launch_eval_cluster(p->geo, p->B, stamped ? p->ev_args_st.data() : p->ev_args.data(), stamped ? p->d_ev_args_st.p : p->d_ev_args.p, x_dev, f_dev, g_dev, p->eval_fused_ticks, st, p->h_ev_status.p);
     }
     // batches beyond the clusters' reach: one workgroup per candidate runs the three stage bodies back to back - plain evaluations AND the optimiser's rounds (same
     // stage buffers, tap and skipped candidates as the three launches; bit-identical results)
@@ -599,7 +597,6 @@ int frx_problem_create(const frx_config *cfg, int device, int B, const int *coar
         frx::eval_cluster_args(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_ev_ll.p, p->d_ev_words, p->ev_args.data());
         const hipError_t e_ = hipMemcpy(p->d_ev_args.p, p->ev_args.data(), p->ev_args.size(), hipMemcpyHostToDevice);
         if (e_ != hipSuccess) { const std::string m_ = std::string("upload of the evaluation arguments: ") + hipGetErrorString(e_); (void)hipStreamDestroy(p->stream); delete p; return fail(FRX_ERR_HIP, m_); }
-        p->ev_args_up = p->ev_args;
     }
     if (std::getenv("FRX_SETUP_TIMING")) fprintf(stderr, "[frx setup] frx_problem_create: B = %d, host descriptors %.3f ms, device allocations + uploads %.3f ms\n", B, ms_host_build, ms_since(t_create0) - ms_host_build);
     *out = p;
@@ -696,6 +693,13 @@ static int profile_eval_cluster(frx_problem *p, const double *x, long long *out,
     int rc = frx_objective_eval(p, x, f.data(), g.data());          // warm
     if (rc != FRX_OK) return rc;
     p->dp.stamps = p->d_stamps.p; p->eval_fused_stamps = 1;
+    {   // the argument block with the stamps pointer: a device copy of its own, uploaded here (a blocking call), so that no evaluation ever has to
+        p->ev_args_st.assign(frx::eval_cluster_args_bytes(), 0);
+        frx::eval_cluster_args(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_ev_ll.p, p->d_ev_words, p->ev_args_st.data());
+        hipError_t e_ = p->d_ev_args_st.p ? hipSuccess : p->d_ev_args_st.alloc(p->ev_args_st.size());
+        if (e_ == hipSuccess) e_ = hipMemcpy(p->d_ev_args_st.p, p->ev_args_st.data(), p->ev_args_st.size(), hipMemcpyHostToDevice);
+        if (e_ != hipSuccess) { p->dp.stamps = nullptr; p->eval_fused_stamps = 0; return fail(FRX_ERR_HIP, hipGetErrorString(e_)); }
+    }
     rc = frx_objective_eval(p, x, f.data(), g.data());
     p->dp.stamps = nullptr; p->eval_fused_stamps = 0;
     if (rc != FRX_OK) return rc;

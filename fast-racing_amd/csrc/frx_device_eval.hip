@@ -19,8 +19,14 @@ static bool eval_tail() { static const bool on = [] { const char *e = std::geten
 // FRX_EVAL_HANDOFF=0: the penalty partials piece-major, polled with 8-byte loads, the adjoint's multipliers requested behind the poll (A/B).  Read once per process, before the first handle
 // exists (eval_cluster_geometry): the two forms put a granule at different addresses of one buffer, and a tag is only good for the address it was written to.
 static bool eval_handoff() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_HANDOFF"); return !(e && e[0] == '0'); }(); return on && eval_argp() && eval_tail(); }
+// FRX_EVAL_CHAIN=0: the form with the cycle stamps compiled in and every argument field loaded at its use - the one the diagnostics launch in any case (A/B; with the four
+// switches above at their defaults only)
+static bool eval_chain() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_CHAIN"); return !(e && e[0] == '0'); }(); return on && eval_handoff(); }
+// the instantiation of the hand-off form that carries the stamps: the diagnostics' launches, and every launch under FRX_EVAL_CHAIN=0
+static const void *eval_fn_stamps() { return eval_early_t() ? (const void *)k_eval_cluster<true, true, true, true> : (const void *)k_eval_cluster<true, false, true, true>; }
 // the instantiation the launcher takes: argument pointer (or not) x early durations (or not)
 static const void *eval_fn() {
+    if (eval_chain()) return eval_early_t() ? (const void *)k_eval_cluster<true, true, true, true, true> : (const void *)k_eval_cluster<true, false, true, true, true>;
     if (eval_handoff()) return eval_early_t() ? (const void *)k_eval_cluster<true, true, true, true> : (const void *)k_eval_cluster<true, false, true, true>;
     if (!eval_tail() && eval_argp() && eval_early_t()) return (const void *)k_eval_cluster<true, true, false>;
     return eval_argp() ? (eval_early_t() ? (const void *)k_eval_cluster<true, true> : (const void *)k_eval_cluster<true, false>)
@@ -35,7 +41,8 @@ int eval_cluster_raise_limit(size_t bytes) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
     if (bytes <= held[dev]) return 0;
-    const hipError_t e = hipFuncSetAttribute(eval_fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    hipError_t e = hipFuncSetAttribute(eval_fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess && eval_chain()) e = hipFuncSetAttribute(eval_fn_stamps(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);   // (the diagnostics' instantiation)
     if (e == hipSuccess) held[dev] = bytes;
     return (int)e;
 }
@@ -58,8 +65,8 @@ int eval_cluster_blocks_per_cu(size_t lds_bytes) {
     return n;
 }
 size_t eval_cluster_args_bytes() { return sizeof(EvalClusterArgs); }
-// The handle's constant arguments (frx_api.cpp keeps a host copy next to a device copy and uploads it when it changes - at create, and when a diagnostic switches the
-// cycle stamps on): everything launch_eval_cluster used to pack per call.
+// The handle's constant arguments (frx_api.cpp keeps a host copy next to a device copy, uploaded at create, and a second pair with the stamps pointer set that the
+// diagnostics upload before their evaluation): everything launch_eval_cluster used to pack per call.
 void eval_cluster_args(const DevProblem &dp, const LaunchGeom &g, double *T, double *C, unsigned long long *ll, unsigned *words, void *out) {
     EvalClusterArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -78,7 +85,11 @@ int launch_eval_cluster(const LaunchGeom &g, int B, const void *args_host, const
     if (c.test_drop_members) c.timeout_ticks = 5000ull;
     const dim3 grid(8 * g.ev_G * ((B + 7) / 8));
     const bool et = eval_early_t();
-    if (eval_handoff() && args_dev) {
+    // the production instantiation has no stamp code: a handle whose stamps pointer is set (a diagnostic's evaluation) takes the one that has, with the argument block that carries the pointer
+    if (eval_chain() && args_dev && !((const EvalClusterArgs *)args_host)->dp.stamps) {
+        if (et) hipLaunchKernelGGL((k_eval_cluster<true, true, true, true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+        else hipLaunchKernelGGL((k_eval_cluster<true, false, true, true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+    } else if (eval_handoff() && args_dev) {
         if (et) hipLaunchKernelGGL((k_eval_cluster<true, true, true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
         else hipLaunchKernelGGL((k_eval_cluster<true, false, true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
     } else if (eval_argp() && args_dev) {

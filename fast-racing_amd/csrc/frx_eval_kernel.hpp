@@ -82,7 +82,8 @@ struct EvalCallArgs {                         // what changes per call
 };
 // The early barrier of the early-duration form (forward_knot_body<.., ET>): the caller's loads behind the body's, then one barrier that zeroes the counters and makes the
 // status early-out workgroup-uniform.
-template <class F> struct EvalEarlySync {
+template <class F, bool NS = false> struct EvalEarlySync {
+    static constexpr bool nostamps = NS;          // (CH below: no cycle stamps compiled into the forward map)
     const F &f; long long *st; bool steps;
     __device__ __forceinline__ bool sync() const { return f(); }
 };
@@ -91,9 +92,20 @@ template <class F> struct EvalEarlySync {
 // HO (the default; FRX_EVAL_HANDOFF=0 takes the other form, A/B; with the tail above and the argument pointer only): the hand-off of the partials laid out for its reader
 // (EvalHandoff, frx_kernels.hpp) - the members store a granule with one 16-byte store at its value-major place; the leader's waves poll with one coalesced 16-byte load
 // per granule, wave 0 two and an axis wave six, and the axis waves request the 52 multipliers of their knot in front of the poll instead of behind it.
-template <bool ARGP, bool ET, bool TAIL = true, bool HO = false>
+// CH (the default; FRX_EVAL_CHAIN=0 takes the other form, A/B; with the three above only): the PRODUCTION instantiation.  The cycle stamps are a compile-time property - no
+// read of a clock, no load of the stamps pointer, no branch on it in this kernel or in the bodies it calls (the diagnostics, frx_debug_profile_eval_cluster and the
+// timeline scripts, launch the CH = false instantiation with an argument block of their own that carries the pointer: launch_eval_cluster picks both by the handle's
+// stamps pointer).  And no argument load behind a wait of the chain: behind the argument pointer every field is a scalar load at its use, and the wait for it (lgkmcnt)
+// drains the LDS reads of the lone wave around it.  What the stretches behind the forward map read is loaded ONCE and pinned in scalar registers (as_uniform, frx_kernels.hpp) -
+//   leader, in front of the adjoint's set-up (so in front of the poll, where it idles): rho, the fixed-time layer's soft / c2 / sumT, the gradient's and f's base, `done`, status_host (EvalChain, EvalTail);
+//   members, in front of the samples: lpp, N, the task's first piece, the candidate's granule base;
+//   members too: the four penalty weights, each of which is otherwise read inside the branch of its violated constraint, in the middle of a lane's samples;
+//   every workgroup, in front of the forward map: nsteps (the axis waves read it behind the last reduction step).
+template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false>
 __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::conditional<ARGP, const EvalClusterArgs *__restrict__, EvalClusterArgs>::type arg, EvalCallArgs call) {
+    static_assert(!CH || (ARGP && TAIL && HO), "the production form: argument pointer, inline tail, value-major hand-off");
     const EvalClusterArgs &a = [&]() -> const EvalClusterArgs & { if constexpr (ARGP) return *arg; else return arg; }();
+    const auto stp = [&]() -> long long * { if constexpr (CH) return nullptr; else return a.dp.stamps; };   // (CH: a constant - every stamp below folds away)
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int lane8 = blockIdx.x & 7, rest = blockIdx.x >> 3;
     const int wg = rest % a.G, k = lane8 + 8 * (rest / a.G);       // (k_round's mapping: a cluster's blocks share blockIdx % 8 - one XCD, as observed)
@@ -101,7 +113,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int c = k;
     // (diagnostic, frx_debug_profile_eval_cluster: cycle stamps of cluster 0 - 40..43 the leader: entry, forward map done, adjoint done, end; 64..68 its tail, see EvalTail; 70..76 its poll for the partials, see EvalHandoff; 44..48 wave 0 of member 1, see penalty_wave_ll, and 69: the gate word's value has arrived - these in ticks of the 100 MHz counter all workgroups share; 49: the leader's shader clock at entry, the origin of the bodies' own stamps 0..31)
-    if (a.dp.stamps && k == 0 && wg == 0 && t == 0) { a.dp.stamps[40] = (long long)wall_clock64(); a.dp.stamps[49] = (long long)__builtin_readcyclecounter(); }
+    if (stp() && k == 0 && wg == 0 && t == 0) { stp()[40] = (long long)wall_clock64(); stp()[49] = (long long)__builtin_readcyclecounter(); }
     unsigned *flag = a.words + (size_t)k * 64, *done = flag + 32;
     const int p0 = a.dp.poff[c], N = a.dp.poff[c + 1] - p0;
     const int ntasks = (N + a.ppw - 1) / a.ppw;                     // wave-tasks of this candidate: ppw pieces each; members 1 .. G-1 hold 4 (G - 1) >= ntasks waves
@@ -125,7 +137,9 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     unsigned my_xcc = 0;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
     my_xcc = call.force_wt ? 0u : (my_xcc & 7u) + 1u;                  // 0: "nowhere" - never equal to a partner's
-    const EvalClusterLds L = eval_cluster_lds(a.maxN19, a.maxXb, a.maxVb, a.maxCN, a.nsteps, a.pen_lds);
+    int nsteps = a.nsteps;
+    if constexpr (CH) asm volatile("" : "+s"(nsteps));
+    const EvalClusterLds L = eval_cluster_lds(a.maxN19, a.maxXb, a.maxVb, a.maxCN, nsteps, a.pen_lds);
     // Round 6: the MEMBERS run the forward map too - the same body on the same x, so their (C, T) are the leader's bit for bit - instead of waiting for the leader's
     // coefficients: until now (C, T) travelled as granules behind a gate word (sweep 0.7 us, gate seen 0.15, granules polled and staged 0.7 us on the members' side) while
     // the members' four waves had nothing to do for the first 8 us of the launch.  The leader sends nothing; its XCD goes into the gate word at ENTRY (the members look at
@@ -145,7 +159,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     const int nh2 = (npieces * hstride) >> 1;
     bool bad = false;
     if constexpr (ET) {
-        if (k == 0 && wg == 1 && wave == 0 && lane == 0 && a.dp.stamps) a.dp.stamps[44] = (long long)wall_clock64();
+        if (k == 0 && wg == 1 && wave == 0 && lane == 0 && stp()) stp()[44] = (long long)wall_clock64();
         const auto early = [&]() -> bool {
             if (has_task) {
 #pragma unroll
@@ -160,9 +174,9 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
         };
         const int wg_last = min(a.G - 1, (ntasks - 1) / 4 + 1);           // the last-dispatched member with a task
         long long *est = nullptr;
-        if (a.dp.stamps && k == 0 && (wg == 0 || wg == wg_last)) est = a.dp.stamps + (wg == 0 ? 50 : 60);
-        const EvalEarlySync<decltype(early)> es{early, est, wg == 0};
-        forward_knot_body<false, 64, 5, 0, true>(a.dp, call.x, a.T, a.C, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, a.nsteps, c, ev, ctl, true, &ro, nullptr, nullptr, &es);
+        if (stp() && k == 0 && (wg == 0 || wg == wg_last)) est = stp() + (wg == 0 ? 50 : 60);
+        const EvalEarlySync<decltype(early), CH> es{early, est, wg == 0};
+        forward_knot_body<false, 64, 5, 0, true>(a.dp, call.x, a.T, a.C, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, nsteps, c, ev, ctl, true, &ro, nullptr, nullptr, &es);
         if (bad) {                                                   // an earlier launch's wait expired (see above): uniform over the workgroup
             if (wg == 0 && t == 0) call.f[k] = __builtin_nan("");
             return;
@@ -181,7 +195,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     } else {
     if (wg == 0) { if (t == 0) { *verdict = 0u; __hip_atomic_store(flag, (tag << 4) | (my_xcc ? my_xcc : 15u), FRX_RLX_AGENT); } }
     else if (has_task) {   // corridor blocks of the wave's task: constant, in flight under the forward map
-        if (k == 0 && wg == 1 && wave == 0 && lane == 0 && a.dp.stamps) a.dp.stamps[44] = (long long)wall_clock64();
+        if (k == 0 && wg == 1 && wave == 0 && lane == 0 && stp()) stp()[44] = (long long)wall_clock64();
         for (int i0 = lane; i0 < nh2; i0 += 4 * 64) {
             double2 v[4];
 #pragma unroll
@@ -190,36 +204,61 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
             for (int u = 0; u < 4; u++) { const int i = i0 + 64 * u; if (i < nh2) { hS[2 * i] = v[u].x; hS[2 * i + 1] = v[u].y; } }
         }
     }
-    forward_knot_body<false, 64, 5>(a.dp, call.x, a.T, a.C, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, a.nsteps, c, ev, ctl, true, &ro);   // MODE 1 | 4: stages x and the polytopes itself, (C, T) into ctl only
+    forward_knot_body<false, 64, 5>(a.dp, call.x, a.T, a.C, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, nsteps, c, ev, ctl, true, &ro);   // MODE 1 | 4: stages x and the polytopes itself, (C, T) into ctl only
     }
     if (wg != 0) {
         // every WAVE of a member is on its own from here (no workgroup barrier below): its samples out of the workgroup's (C, T) copy, its partials as granules
         if (!has_task) return;
-        long long *const mst = (k == 0 && wg == 1 && wave == 0 && lane == 0) ? a.dp.stamps : nullptr;
+        long long *const mst = (k == 0 && wg == 1 && wave == 0 && lane == 0) ? stp() : nullptr;
         if (mst) mst[46] = (long long)wall_clock64();
-        const int pl = lane / a.lpp, jl = lane - pl * a.lpp;
-        if (pl < npieces) penalty_lane_samples<true>(a.dp, ctl + (size_t)(task * a.ppw + pl) * 19, hS + (size_t)pl * hstride, ctl[(task * a.ppw + pl) * 19 + 18], jl, a.lpp, a.Kmax, red + lane * 21);
+        // (CH) what the reduction and the granule stores read from the argument block, once, in front of the samples
+        int m_lpp = a.lpp, m_t0 = task * a.ppw, m_N = N;
+        ll_u64 *m_ll = a.out20ll + (size_t)p0 * 40;
+        if constexpr (CH) {
+            m_N = as_uniform(m_N);
+            gptr<ll_u64> q_ll = (gptr<ll_u64>)as_uniform(m_ll);
+            asm volatile("" : "+s"(m_lpp), "+s"(m_t0), "+s"(m_N), "+s"(q_ll));
+            m_ll = (ll_u64 *)q_ll;
+        }
+        const int pl = lane / m_lpp, jl = lane - pl * m_lpp;
+        if constexpr (CH) {
+            // the penalty weights too: each is read inside the branch of its violated constraint, a scalar trip in the middle of a lane's samples
+            DevProblem mdp = a.dp;
+            asm volatile("" : "+s"(mdp.pc.chi[0]), "+s"(mdp.pc.chi[1]), "+s"(mdp.pc.chi[2]), "+s"(mdp.pc.chi[3]));
+            if (pl < npieces) penalty_lane_samples<true>(mdp, ctl + (size_t)(m_t0 + pl) * 19, hS + (size_t)pl * hstride, ctl[(m_t0 + pl) * 19 + 18], jl, m_lpp, a.Kmax, red + lane * 21);
+        } else
+        if (pl < npieces) penalty_lane_samples<true>(a.dp, ctl + (size_t)(m_t0 + pl) * 19, hS + (size_t)pl * hstride, ctl[(m_t0 + pl) * 19 + 18], jl, m_lpp, a.Kmax, red + lane * 21);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (mst) mst[47] = (long long)wall_clock64();
         const unsigned gv = __hip_atomic_load(flag, FRX_RLX_AGENT);           // the leader's XCD, if it has arrived under this evaluation's tag (requested in front of the samples instead, the trip is worth 0.07 us: profiles/NOTES.md)
         if (mst) { asm volatile("" :: "v"(gv)); mst[69] = (long long)wall_clock64(); }   // (the word's value is in its register)
         const bool wt = my_xcc == 0u || (gv >> 4) != tag || (gv & 15u) != my_xcc;   // plain stores when the leader runs on this XCD (its L2 is the meeting point), write-through otherwise
-        if constexpr (HO) penalty_reduce<true, true>(red, npieces, a.lpp, nullptr, lane, 64, wt, a.out20ll + (size_t)p0 * 40, tag, N, task * a.ppw);
-        else penalty_reduce<true>(red, npieces, a.lpp, nullptr, lane, 64, wt, a.out20ll + (size_t)gp0 * 40, tag);
+        if constexpr (HO) penalty_reduce<true, true>(red, npieces, m_lpp, nullptr, lane, 64, wt, m_ll, tag, m_N, m_t0);
+        else penalty_reduce<true>(red, npieces, m_lpp, nullptr, lane, 64, wt, a.out20ll + (size_t)gp0 * 40, tag);
         if (mst) mst[48] = (long long)wall_clock64();
         return;
     }
     // ---- leader ----
-    if (a.dp.stamps && k == 0 && t == 0) a.dp.stamps[41] = (long long)wall_clock64();
+    if (stp() && k == 0 && t == 0) stp()[41] = (long long)wall_clock64();
     ro.o20ll = a.out20ll; ro.o20tag = tag; ro.status = a.status; ro.spin_ticks = call.timeout_ticks;
     const LineSearchTap tap{nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr};
     // the tail (EvalTail): f and `done` leave from inside the adjoint; the diagnostic's stamps 64.. of cluster 0 go with it
-    const EvalTail tl{verdict, call.f, done, tag, call.status_host, k == 0 ? a.dp.stamps : nullptr, TAIL};
-    const EvalHandoff<HO> ho{k == 0 ? a.dp.stamps : nullptr};
-    backward_knot_body<true, 64, 0, EvalTail, EvalHandoff<HO>>(a.dp, call.x, a.T, a.C, nullptr, call.f, call.g, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, a.nsteps, tap, c, ev, ctl, &ro, &tl, &ho);
-    if (a.dp.stamps && k == 0 && t == 0) a.dp.stamps[42] = (long long)wall_clock64();
+    // (CH) what the adjoint reads behind its poll, loaded here - the leader idles at the poll - and held in scalar registers: EvalChain, and the tail's addresses
+    EvalChain ch{0.0, 0.0, 0, 0, nullptr};
+    double *t_f = call.f; unsigned *t_done = done, *t_sh = call.status_host;
+    if constexpr (CH) {
+        ch = EvalChain{a.dp.rho, a.dp.sumT, a.dp.soft, a.dp.c2, nullptr};
+        gptr<double> q_g = (gptr<double>)call.g, q_f = (gptr<double>)t_f;
+        gptr<unsigned> q_done = (gptr<unsigned>)t_done, q_sh = (gptr<unsigned>)t_sh;
+        asm volatile("" : "+s"(ch.rho), "+s"(ch.sumT), "+s"(ch.soft), "+s"(ch.c2), "+s"(q_g), "+s"(q_f), "+s"(q_done), "+s"(q_sh));
+        ch.g = (double *)q_g; t_f = (double *)q_f; t_done = (unsigned *)q_done; t_sh = (unsigned *)q_sh;
+    }
+    const EvalTail tl{verdict, t_f, t_done, tag, t_sh, k == 0 ? stp() : nullptr, TAIL};
+    const EvalHandoff<HO, CH> ho{k == 0 ? stp() : nullptr, ch};
+    backward_knot_body<true, 64, 0, EvalTail, EvalHandoff<HO, CH>>(a.dp, call.x, a.T, a.C, nullptr, call.f, call.g, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, nsteps, tap, c, ev, ctl, &ro, &tl, &ho);
+    if (stp() && k == 0 && t == 0) stp()[42] = (long long)wall_clock64();
     if constexpr (TAIL) {
-        if (a.dp.stamps && k == 0 && t == 0) a.dp.stamps[43] = (long long)wall_clock64();
+        if (stp() && k == 0 && t == 0) stp()[43] = (long long)wall_clock64();
     } else {
     __syncthreads();
     if (t == 0) {

@@ -123,9 +123,30 @@ struct EvalTail { volatile __attribute__((address_space(3))) unsigned *verdict; 
 // registers for the same move, which is why it stays behind this flag).  st (optional): 100 MHz stamps - [70] wave 0 enters the poll, [71] has left
 // it, [72] / [73] the same for axis wave 1, [74] axis wave 1's Hermite adjoint is done (the twin of the shader-clock stamp 26); [75] / [76] spins of lane 0 of wave 0 /
 // of axis wave 1.
-template <bool TR> struct EvalHandoff { static constexpr bool tr = TR; long long *st; };
+// CH (EvalChain; FRX_EVAL_CHAIN=0 takes the other form, A/B): the production form of the one-launch evaluation.  No cycle stamp of any kind is compiled into the body (the
+// stamps are a property of the INSTANTIATION: the diagnostics launch the CH = false one), and what the stretch behind the poll reads from the argument block - rho, the
+// fixed-time layer's switches and total, the gradient's base - comes in `ch`, loaded once in front of the poll and held in scalar registers: behind a pointer every such
+// field is a scalar load at its use, whose wait (lgkmcnt) also drains the LDS reads the wave has in flight around it.
+struct EvalChain { double rho, sumT; int soft, c2; double *g; };
+template <bool TR, bool CH = false> struct EvalHandoff { static constexpr bool tr = TR, chain = CH; long long *st; EvalChain ch; };
 template <class HO> struct ho_transposed { static constexpr bool value = HO::tr; };
 template <> struct ho_transposed<void> { static constexpr bool value = false; };
+template <class HO> struct ho_chain { static constexpr bool value = HO::chain; };
+template <> struct ho_chain<void> { static constexpr bool value = false; };
+// (the early-duration form's sync object, EvalEarlySync: ES::nostamps - no cycle stamps compiled into forward_knot_body)
+template <class ES> struct es_nostamps { static constexpr bool value = ES::nostamps; };
+template <> struct es_nostamps<void> { static constexpr bool value = false; };
+// Pinning a wave-uniform value in scalar registers: `asm volatile("" : "+s"(v), ...)` defines it anew, so the compiler may not re-load it at its uses, and ONE statement for a
+// group of values lets their loads go out together in front of it.  as_uniform: a uniform value that came through a vector load moves to a scalar register first (a no-op otherwise).
+// gptr: a pointer goes through such a statement as a pointer to GLOBAL memory by type - as a plain one it would come out with its address space unknown, and its stores as flat stores.
+template <class T> using gptr = __attribute__((address_space(1))) T *;
+template <class V> __device__ __forceinline__ V as_uniform(V v) {
+    static_assert(sizeof(V) == 4 || sizeof(V) == 8, "a 4- or 8-byte value");
+    int w[sizeof(V) / 4]; __builtin_memcpy(w, &v, sizeof(V));
+    for (unsigned i = 0; i < sizeof(V) / 4; i++) w[i] = __builtin_amdgcn_readfirstlane(w[i]);
+    __builtin_memcpy(&v, w, sizeof(V));
+    return v;
+}
 
 // Coalesced staging global -> LDS with every load of a trip in flight before the first LDS store.  The plain loop
 // `for (i = k; i < n; i += nthr) dst[i] = src[i]` compiles to load / s_waitcnt vmcnt(0) / ds_write per element even under
@@ -1340,8 +1361,8 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
     double *pwf = vs + maxVb;                          // [nrow][nsteps*8+5] reduction multipliers (wave-specialised path)
     if (ro) { xs = ro->xs; vs = ro->vs; if (nrow == 64 && nthr == 256) pwf = ro->pw; }
 #define KN(arr, axis, idx) arr[(axis) * (nrow + 1) + (idx)]
-#define FWD_STAMP(slot) do { if (!(ro && ro->quiet)) FRX_STAMP(slot); } while (0)
-#define FWD_STAMP_AX(slot) do { if (!(ro && ro->quiet)) FRX_STAMP_AX(slot); } while (0)
+#define FWD_STAMP(slot) do { if constexpr (!es_nostamps<ES>::value) { if (!(ro && ro->quiet)) FRX_STAMP(slot); } } while (0)
+#define FWD_STAMP_AX(slot) do { if constexpr (!es_nostamps<ES>::value) { if (!(ro && ro->quiet)) FRX_STAMP_AX(slot); } } while (0)
     FWD_STAMP(0);
     // Every global read of the kernel is issued here, before the first barrier, so the whole kernel pays ONE memory
     // latency (loads placed in later phases cannot be hoisted over the barriers by the compiler: measured +4 us).
@@ -2103,6 +2124,14 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
                                 const LineSearchTap &tap, int b, double *sm, const double *ct_lds, const ResidentOps *ro, const TL *tl = nullptr, const HO *ho = nullptr) {
     constexpr bool TAIL = !std::is_void<TL>::value;     // the one-launch evaluation's tail (EvalTail); nothing of it is compiled into the other callers
     constexpr bool HOST = !std::is_void<HO>::value, HOTR = ho_transposed<HO>::value;   // its hand-off of the partials (EvalHandoff): the stamps; the transposed granules
+    constexpr bool CHN = ho_chain<HO>::value;           // (EvalChain) no stamps in this instantiation, the argument block's scalars from ho->ch
+#define BK_STAMP(slot) do { if constexpr (!CHN) FRX_STAMP(slot); } while (0)
+#define BK_STAMP_AX(slot) do { if constexpr (!CHN) FRX_STAMP_AX(slot); } while (0)
+    const auto a_rho = [&]() -> double { if constexpr (CHN) return ho->ch.rho; else return dp.rho; };       // (each read at its use, as ever, where they do not come in `ch`)
+    const auto a_sumT = [&]() -> double { if constexpr (CHN) return ho->ch.sumT; else return dp.sumT; };
+    const auto a_soft = [&]() -> int { if constexpr (CHN) return ho->ch.soft; else return dp.soft; };
+    const auto a_c2 = [&]() -> int { if constexpr (CHN) return ho->ch.c2; else return dp.c2; };
+    if constexpr (CHN) g = ho->ch.g;
     const int nrow = 64, nthr = 256;
     const int k = threadIdx.x, kk = k & 63, t2 = k - 64;
     const int wave = __builtin_amdgcn_readfirstlane(k >> 6);
@@ -2134,7 +2163,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
     const bool tapped = tap.d != nullptr;
     const int tap_flags = (tapped && tap.flags) ? tap.flags[b] : 0;   // consumed by thread 0 at the very end
     double t_dg = 0.0, t_xx = 0.0, t_gg = 0.0;          // g.d, x.x, g.g over the elements this thread writes
-    FRX_STAMP(16);
+    BK_STAMP(16);
     // ---- all global reads up front ----
     const bool piece = kk < N;
     const int kp = piece ? kk : 0;                      // clamped piece index: loads are unconditional, results of lanes without a piece unused
@@ -2190,7 +2219,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         }
         __syncthreads();
     }
-    FRX_STAMP(17);
+    BK_STAMP(17);
     // ================================================================================================================================================
     // Round 5: everything that does NOT depend on the penalty partials runs here, IN FRONT of the poll for them.  In the resident kernel the leader has
     // ~4.5 us between the end of its forward map and the arrival of the partials (hand-off, the members' penalty share) with nothing to do; until
@@ -2235,7 +2264,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         }
         if (dp.soft && kk < cN) { x_tau = xs[kk]; dtt = dT_dtau(x_tau, dp.c2 != 0); if (tapped) d_tau = dsv[kk]; }
     } else {
-        FRX_STAMP_AX(25);
+        BK_STAMP_AX(25);
         {   // jerk-energy part of cbar = d f / d c of this axis (CPU.hpp:84-92)
             const double t1 = h, t2_ = t1 * t1, t3 = t2_ * t1, t4 = t2_ * t2_, t5 = t4 * t1;
             cj3 = 72.0 * cq[3] * t1 + 144.0 * cq[4] * t2_ + 240.0 * cq[5] * t3;
@@ -2375,7 +2404,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         const double ePu = lane_up1(db[3]), eVu = lane_up1(db[4]), eAu = lane_up1(db[5]);
         double r0 = 0.0, r1 = 0.0, pbk = 0.0;
         if (act) { r0 = db[1] + eVu; r1 = db[2] + eAu; pbk = db[0] + ePu; }      // right-hand side of K mu = wbar; direct d f / d p_k (both adjacent pieces)
-        FRX_STAMP_AX(26);
+        BK_STAMP_AX(26);
         if constexpr (HOST) { if (ho->st && k == 64) { asm volatile("" :: "v"(r0), "v"(r1), "v"(pbk)); ho->st[74] = (long long)wall_clock64(); } }
         // ---- mu = K^-1 wbar with the multipliers of the forward reduction (K is symmetric), neighbours by lane shifts ----
         double muv = 0.0, mua = 0.0;                                   // zero at the fixed end knots
@@ -2410,7 +2439,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
                 muv = Dq[0] * r0 + Dq[1] * r1; mua = Dq[2] * r0 + Dq[3] * r1;
             }
         }
-        FRX_STAMP_AX(27);
+        BK_STAMP_AX(27);
         // The waypoint layer's operands - this lane's vertices, variables and direction elements, the forward map's two sums - are requested HERE, where the
         // solve's 52 multipliers are dead: their LDS round trips run under the knot adjoint and the barrier instead of behind it (in front of the
         // poll, next to the multipliers, they cost the resident kernel's leader 190 spilled registers).
@@ -2444,14 +2473,14 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         const double dlu = lane_up1(dlb);                    // + dl of the piece ending at this knot
         if (piece) KN(KV, ax, kk) = hb;
         if (act) KN(KP, ax, kk) = pbk + dlu - dlb;                   // d f / d q_k for the pair that owns the waypoint
-        FRX_STAMP_AX(28);
+        BK_STAMP_AX(28);
     }
     __syncthreads();
-    FRX_STAMP(22);
+    BK_STAMP(22);
     if constexpr (TAIL) { if (tl->st && k == 0) tl->st[64] = (long long)wall_clock64(); }
     if (wave == 0) {
         // ---- duration gradient, mergeToCoarseGradT (CPU.hpp:946-959), cost (CPU.hpp:988), addLayerTGrad (CPU.hpp:816-894): all within wave 0 ----
-        if (piece) gT[kk] = gTl + ((KN(KV, 0, kk) + KN(KV, 1, kk)) + KN(KV, 2, kk)) + dp.rho;     // + rho: CPU.hpp:989
+        if (piece) gT[kk] = gTl + ((KN(KV, 0, kk) + KN(KV, 1, kk)) + KN(KV, 2, kk)) + a_rho();     // + rho: CPU.hpp:989
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         double sumTc = 0.0;
         if (kk < cN) {
@@ -2462,7 +2491,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
             sumTc = tt;
         }
         const double wc = wave_sum_dpp(costAcc), wtt = wave_sum_dpp(sumTc);
-        const double fval = wc + dp.rho * wtt;
+        const double fval = wc + a_rho() * wtt;
         if (kk == 0) { if (!ro) f[b] = fval; red[0] = fval; }             // resident caller: the value travels through the mailbox, nothing to drain
         if constexpr (TAIL) {
             // The one-launch evaluation ends HERE for thread 0: f and `done` leave in front of the time gradient, every store of the wave in flight together - vmcnt
@@ -2481,7 +2510,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
                 if (tl->st) tl->st[68] = (long long)wall_clock64();
             }
         }
-        if (dp.soft) {
+        if (a_soft()) {
             if (kk < cN) {
                 const double gi = gCo[kk] * dtt;
                 if (gs) gs[kk] = gi; else g[x0 + kk] = gi;
@@ -2492,17 +2521,17 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (kk == 0) {
                 const int Ms1 = cN - 1;
-                const double gTail = dp.sumT * gCo[Ms1];
+                const double gTail = a_sumT() * gCo[Ms1];
                 double expTauSum = 0.0, gFreeDotExpTau = 0.0;
                 for (int i = 0; i < Ms1; i++) {
-                    const double e = tau_to_T(xs[i], dp.c2 != 0);
+                    const double e = tau_to_T(xs[i], a_c2() != 0);
                     expTauSum += e;
-                    gFreeDotExpTau += e * (dp.sumT * gCo[i]);
+                    gFreeDotExpTau += e * (a_sumT() * gCo[i]);
                 }
                 const double den = expTauSum + 1.0;
                 for (int i = 0; i < Ms1; i++) {
-                    const double de = dT_dtau(xs[i], dp.c2 != 0);
-                    const double gi = (dp.sumT * gCo[i] - gTail) * de / den - (gFreeDotExpTau - gTail * expTauSum) * de / (den * den);
+                    const double de = dT_dtau(xs[i], a_c2() != 0);
+                    const double gi = (a_sumT() * gCo[i] - gTail) * de / den - (gFreeDotExpTau - gTail * expTauSum) * de / (den * den);
                     if (gs) gs[i] = gi; else g[x0 + i] = gi;
                     if (gpub && !defer_time_gpub) stg<SH>(gpub + i, gi, gwt);
                     if (tapped) { t_dg += gi * dsv[i]; t_xx += xs[i] * xs[i]; t_gg += gi * gi; }
@@ -2520,9 +2549,9 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         if (wact) { g0 = KN(KP, 0, w + 1); g1 = KN(KP, 1, w + 1); g2 = KN(KP, 2, w + 1); }
         if (cached0) {
             const double s2 = wq1 * g0 + wq2 * g1 + wq3 * g2;
-            FRX_STAMP_AX(30);
+            BK_STAMP_AX(30);
             const double gdq = w_c2sc * s2, kq = 4.0 * gdq * w_iq2, sc22 = w_sc22;
-            FRX_STAMP_AX(31);
+            BK_STAMP_AX(31);
             if (wact) {
 #pragma unroll
                 for (int j = 0; j < WPF; j++)                              // the vertices fetched in front of the poll
@@ -2565,11 +2594,11 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
                     for (int j = 0; j < 4; j++)
                         if (a0 + 2 * j < nv1) { const double x2 = xv[j] * xv[j]; qn += x2; s2 += dgv[j] * x2; }
                 }
-            FRX_STAMP_AX(30);
+            BK_STAMP_AX(30);
             qn += dpp_mov<0xB1>(qn); s2 += dpp_mov<0xB1>(s2);   // pair sums
             const double qp1 = qn + 1.0, iq = 1.0 / qp1, sc = 2.0 * iq;
             const double gdq = 2.0 * sc * s2, kq = 4.0 * gdq * (iq * iq), sc22 = 2.0 * sc * sc;
-            FRX_STAMP_AX(31);
+            BK_STAMP_AX(31);
             if (wact)
                 for (int a0 = sub; a0 < nv1; a0 += 8) {
                     double xv[4], dgv[4], dd[4];
@@ -2590,8 +2619,8 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
                 }
         }
     }
-    FRX_STAMP_AX(29);
-    FRX_STAMP(23);
+    BK_STAMP_AX(29);
+    BK_STAMP(23);
     if constexpr (TAIL) { if (tl->st && (k == 0 || k == 64)) tl->st[65 + (k >> 6)] = (long long)wall_clock64(); }
     // ---- line-search tap: what lbfgs.hpp:830 (g.d) and :1296-1297 (|x|, |g|) need, reduced here instead of in a separate launch ----
     if (tap.d != nullptr) {                                           // uniform over the grid
@@ -2600,7 +2629,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         double *red3 = rowbuf;                                        // the row buffer is not used by this path
         if ((k & 63) == 0) { red3[w] = w0; red3[nw + w] = w1; red3[2 * nw + w] = w2; }
         __syncthreads();
-        if (defer_time_gpub && wave == 1 && kk < (dp.soft ? cN : cN - 1)) stg<SH>(gpub + kk, gs[kk], gwt);   // (see defer_time_gpub)
+        if (defer_time_gpub && wave == 1 && kk < (a_soft() ? cN : cN - 1)) stg<SH>(gpub + kk, gs[kk], gwt);   // (see defer_time_gpub)
         if (k == 0 && ((tap_flags & DV_EVAL) || tap.lds_out)) {
             const double fval = red[0];
             double a0 = 0.0, a1 = 0.0, a2 = 0.0;
@@ -2613,7 +2642,9 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
             if (atomicAdd(tap.arrive, 1u) + 1u == (unsigned)gridDim.x * tap.round) *tap.flag = tap.round;
         }
     }
-    FRX_STAMP(24);
+    BK_STAMP(24);
+#undef BK_STAMP
+#undef BK_STAMP_AX
 }
 
 // SH: out20 (and T, C) were written by workgroups of the same launch.  TL, HO (EvalTail, EvalHandoff: the one-launch evaluation only): see backward_knot_wsp64.
