@@ -68,6 +68,7 @@ int launch_backward(const DevProblem &dp, const LaunchGeom &g, const double *x, 
 
 // One launch per evaluation (frx_eval_kernel.hpp): clusters of g.ev_G workgroups, one per candidate.  ll: [P][40 + 38] granule words (penalty partials, then (C, T)), words: [64 B + 1] (the last one: status), both
 // zeroed ONCE at allocation.  The caller has checked that dp.B * g.ev_G workgroups are resident at once (eval_cluster_geometry).
+int eval_cluster_class(const LaunchGeom &g);                      // 1: a handle of this geometry launches the compile-time geometry class (EvalGeomK16, frx_eval_kernel.hpp), 0: the run-time form
 int eval_cluster_geometry(LaunchGeom &g);                         // fills ev_G / lds_ev from the other fields; returns ev_G
 // The handle's constant arguments are packed ONCE (eval_cluster_args into eval_cluster_args_bytes() bytes) and live in host AND device memory; a launch passes the
 // device copy by pointer (the by-value form behind FRX_EVAL_ARGPTR=0 reads the host copy) plus what changes per call.

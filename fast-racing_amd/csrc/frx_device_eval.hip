@@ -22,6 +22,13 @@ static bool eval_handoff() { static const bool on = [] { const char *e = std::ge
 // FRX_EVAL_CHAIN=0: the form with the cycle stamps compiled in and every argument field loaded at its use - the one the diagnostics launch in any case (A/B; with the four
 // switches above at their defaults only)
 static bool eval_chain() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_CHAIN"); return !(e && e[0] == '0'); }(); return on && eval_handoff(); }
+// FRX_EVAL_GEOM=0: the run-time instantiation also where the handle's geometry is the class EvalGeomK16 (A/B; with the five switches above at their defaults only)
+static bool eval_geom_on() { static const bool on = [] { const char *e = std::getenv("FRX_EVAL_GEOM"); return !(e && e[0] == '0'); }(); return on && eval_handoff() && eval_early_t(); }
+typedef eval_geom<EvalGeomK16> GeomK16;
+// does a handle of this geometry launch the class instantiation (k_eval_cluster<.., EvalGeomK16>)?  Exactly the class's integers, nothing "close": any other handle takes the run-time form.
+int eval_cluster_class(const LaunchGeom &g) {
+    return (eval_geom_on() && g.ev_G && g.lpp == GeomK16::lpp && g.ppw == GeomK16::ppw && g.Kmax == GeomK16::kmax && g.pcr_steps == GeomK16::nsteps) ? 1 : 0;
+}
 // the instantiation of the hand-off form that carries the stamps: the diagnostics' launches, and every launch under FRX_EVAL_CHAIN=0
 static const void *eval_fn_stamps() { return eval_early_t() ? (const void *)k_eval_cluster<true, true, true, true> : (const void *)k_eval_cluster<true, false, true, true>; }
 // the instantiation the launcher takes: argument pointer (or not) x early durations (or not)
@@ -43,10 +50,15 @@ int eval_cluster_raise_limit(size_t bytes) {
     if (bytes <= held[dev]) return 0;
     hipError_t e = hipFuncSetAttribute(eval_fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess && eval_chain()) e = hipFuncSetAttribute(eval_fn_stamps(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);   // (the diagnostics' instantiation)
+    if (e == hipSuccess && eval_geom_on()) {                             // (the class instantiations: production and diagnostics)
+        e = hipFuncSetAttribute((const void *)k_eval_cluster<true, true, true, true, true, EvalGeomK16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_eval_cluster<true, true, true, true, false, EvalGeomK16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    }
     if (e == hipSuccess) held[dev] = bytes;
     return (int)e;
 }
 static int eval_pen_lds(const LaunchGeom &g) { return g.ppw * 19 + g.ppw * (g.Kmax + 1) * 4 + 64 * 21; }   // doubles per wave (penalty_body with a 64-lane group)
+static_assert(GeomK16::pen_lds == 3 * 19 + 3 * 36 + 64 * 21, "the class's per-wave LDS is eval_pen_lds of its integers");
 int eval_cluster_geometry(LaunchGeom &g) {
     g.ev_G = 0; g.lds_ev = 0;
     (void)eval_handoff();
@@ -86,7 +98,11 @@ int launch_eval_cluster(const LaunchGeom &g, int B, const void *args_host, const
     const dim3 grid(8 * g.ev_G * ((B + 7) / 8));
     const bool et = eval_early_t();
     // the production instantiation has no stamp code: a handle whose stamps pointer is set (a diagnostic's evaluation) takes the one that has, with the argument block that carries the pointer
-    if (eval_chain() && args_dev && !((const EvalClusterArgs *)args_host)->dp.stamps) {
+    if (eval_cluster_class(g) && args_dev) {                           // the geometry class: its production instantiation, or the one with the stamps under the same rule as below
+        assert(((const EvalClusterArgs *)args_host)->pen_lds == GeomK16::pen_lds && ((const EvalClusterArgs *)args_host)->nsteps == GeomK16::nsteps);
+        if (eval_chain() && !((const EvalClusterArgs *)args_host)->dp.stamps) hipLaunchKernelGGL((k_eval_cluster<true, true, true, true, true, EvalGeomK16>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+        else hipLaunchKernelGGL((k_eval_cluster<true, true, true, true, false, EvalGeomK16>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
+    } else if (eval_chain() && args_dev && !((const EvalClusterArgs *)args_host)->dp.stamps) {
         if (et) hipLaunchKernelGGL((k_eval_cluster<true, true, true, true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
         else hipLaunchKernelGGL((k_eval_cluster<true, false, true, true, true>), grid, dim3(256), g.lds_ev, (hipStream_t)stream, (const EvalClusterArgs *)args_dev, c);
     } else if (eval_handoff() && args_dev) {

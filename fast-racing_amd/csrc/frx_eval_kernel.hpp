@@ -101,9 +101,36 @@ template <class F, bool NS = false> struct EvalEarlySync {
 //   members, in front of the samples: lpp, N, the task's first piece, the candidate's granule base;
 //   members too: the four penalty weights, each of which is otherwise read inside the branch of its violated constraint, in the middle of a lane's samples;
 //   every workgroup, in front of the forward map: nsteps (the axis waves read it behind the last reduction step).
-template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false>
+// GEO (EvalGeomK16; FRX_EVAL_GEOM=0 takes the other form, A/B; with the switches above at their defaults only): the GEOMETRY CLASS of the headline handle as integer constants -
+// kappa + 1 = 17 lanes per piece, 3 pieces per wave-task, corridor blocks of Kmax = 8 half-spaces (36 doubles), six reduction steps.  The kernel otherwise takes all of
+// them as run-time integers behind the argument pointer, and on a member's path between the forward map's last barrier and its first sample that is about 230
+// instructions: scalar loads in five groups with a wait each, a division for lane / lpp, a four-way predicated staging scaffold with a second-trip loop, multiplies by
+// strides.  With the class
+//   the lane -> (piece, sample) map, the task's first piece, the block stride and the per-wave LDS are constants, and with lpp and Kmax constant where they are inlined
+//   the sample loop, the half-space chunks and penalty_reduce's block of sixteen reads fold to the trips they take;
+//   a task's corridor blocks (at most 54 double2) are ONE load per lane and one LDS store behind the forward map;
+//   what the samples and the granule stores still read from the argument block (the four weights, kappa, 1 / kappa: run-time VALUES, as before; the candidate's granule
+//   base) is loaded in front of the forward map and kept in VECTOR registers across it (the kernel uses 232 of 512; the forward map and the samples have the scalar
+//   registers to themselves): the samples take the weights and kappa as vector operands, the granule base moves to a scalar pair in front of the samples.
+// N stays per candidate (ragged handles qualify), and so does everything that is not an integer of the geometry: no floating-point expression, operand or order changes,
+// f and the gradient are the run-time form's bits (tests/test_gpu_eval_geometry.py).  launch_eval_cluster picks the class instantiation when the handle's geometry equals
+// it exactly; both CH values have one, so the diagnostics stamp the form that is timed.  The number of reduction steps belongs to the class (it selects the handles) but
+// reaches the bodies as an opaque scalar: folded into forward_knot_body / backward_knot_wsp64, and with the six steps of the matrix and axis waves unrolled on top, the
+// evaluation measured no faster and slower respectively (profiles/NOTES.md), so the bodies of frx_kernels.hpp compile as they do for everybody else.
+struct EvalGeomK16 { static constexpr int LPP = 17, PPW = 3, KMAX = 8, NSTEPS = 6; };
+template <class GEO> struct eval_geom {
+    static constexpr bool fixed = true;
+    static constexpr int lpp = GEO::LPP, ppw = GEO::PPW, kmax = GEO::KMAX, nsteps = GEO::NSTEPS;
+    static constexpr int hstride = (kmax + 1) * 4, pen_lds = ppw * 19 + ppw * hstride + 64 * 21;
+    static_assert(ppw * lpp <= 64 && ppw * hstride <= 2 * 64, "a wave-task: one lane per sample, one double2 of its corridor blocks per lane");
+};
+template <> struct eval_geom<void> { static constexpr bool fixed = false; static constexpr int lpp = 0, ppw = 0, kmax = 0, nsteps = 0, hstride = 0, pen_lds = 0; };
+template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void>
 __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::conditional<ARGP, const EvalClusterArgs *__restrict__, EvalClusterArgs>::type arg, EvalCallArgs call) {
     static_assert(!CH || (ARGP && TAIL && HO), "the production form: argument pointer, inline tail, value-major hand-off");
+    typedef eval_geom<GEO> GC;
+    constexpr bool GF = GC::fixed;
+    static_assert(!GF || (ARGP && ET && TAIL && HO), "the geometry class: the default form of every other switch");
     const EvalClusterArgs &a = [&]() -> const EvalClusterArgs & { if constexpr (ARGP) return *arg; else return arg; }();
     const auto stp = [&]() -> long long * { if constexpr (CH) return nullptr; else return a.dp.stamps; };   // (CH: a constant - every stamp below folds away)
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -116,7 +143,11 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     if (stp() && k == 0 && wg == 0 && t == 0) { stp()[40] = (long long)wall_clock64(); stp()[49] = (long long)__builtin_readcyclecounter(); }
     unsigned *flag = a.words + (size_t)k * 64, *done = flag + 32;
     const int p0 = a.dp.poff[c], N = a.dp.poff[c + 1] - p0;
-    const int ntasks = (N + a.ppw - 1) / a.ppw;                     // wave-tasks of this candidate: ppw pieces each; members 1 .. G-1 hold 4 (G - 1) >= ntasks waves
+    // (the geometry's integers: constants of the class, or the argument block's fields read at each use as before)
+    const auto g_ppw = [&]() -> int { if constexpr (GF) return GC::ppw; else return a.ppw; };
+    const auto g_pen_lds = [&]() -> int { if constexpr (GF) return GC::pen_lds; else return a.pen_lds; };
+    const auto g_kmax = [&]() -> int { if constexpr (GF) return GC::kmax; else return a.Kmax; };
+    const int ntasks = (N + g_ppw() - 1) / g_ppw();                     // wave-tasks of this candidate: ppw pieces each; members 1 .. G-1 hold 4 (G - 1) >= ntasks waves
     if (wg != 0 && ((wg - 1) * 4 >= ntasks || call.test_drop_members)) return;   // a member without a task
     unsigned st0 = 0u;                                              // (ET: thread 0's copy of the status word, the workgroup's first load)
     if constexpr (ET) { if (t == 0) st0 = __hip_atomic_load(a.status, FRX_RLX_AGENT); }
@@ -137,9 +168,10 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     unsigned my_xcc = 0;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
     my_xcc = call.force_wt ? 0u : (my_xcc & 7u) + 1u;                  // 0: "nowhere" - never equal to a partner's
-    int nsteps = a.nsteps;
-    if constexpr (CH) asm volatile("" : "+s"(nsteps));
-    const EvalClusterLds L = eval_cluster_lds(a.maxN19, a.maxXb, a.maxVb, a.maxCN, nsteps, a.pen_lds);
+    int nsteps = GC::nsteps;
+    if constexpr (!GF) nsteps = a.nsteps;
+    if constexpr (CH || GF) asm volatile("" : "+s"(nsteps));            // (GEO: the class's constant, opaque in a scalar register - see above)
+    const EvalClusterLds L = eval_cluster_lds(a.maxN19, a.maxXb, a.maxVb, a.maxCN, nsteps, g_pen_lds());
     // Round 6: the MEMBERS run the forward map too - the same body on the same x, so their (C, T) are the leader's bit for bit - instead of waiting for the leader's
     // coefficients: until now (C, T) travelled as granules behind a gate word (sweep 0.7 us, gate seen 0.15, granules polled and staged 0.7 us on the members' side) while
     // the members' four waves had nothing to do for the first 8 us of the launch.  The leader sends nothing; its XCD goes into the gate word at ENTRY (the members look at
@@ -151,19 +183,32 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     ro.quiet = wg != 0;
     const int task = (wg - 1) * 4 + wave;                                  // (members) this wave's task: ppw pieces
     const bool has_task = wg != 0 && task < ntasks;
-    const int gp0 = p0 + task * a.ppw, npieces = has_task ? min(a.ppw, N - task * a.ppw) : 0;
-    const int hstride = (a.Kmax + 1) * 4;
-    double *wsm = sm + L.mem + (size_t)wave * a.pen_lds, *hS = wsm, *red = wsm + (size_t)a.ppw * hstride;
+    const int gp0 = p0 + task * g_ppw(), npieces = has_task ? min(g_ppw(), N - task * g_ppw()) : 0;
+    const int hstride = (g_kmax() + 1) * 4;
+    double *wsm = sm + L.mem + (size_t)wave * g_pen_lds(), *hS = wsm, *red = wsm + (size_t)g_ppw() * hstride;
     double2 hv[4];                                                  // (ET, members) the first trip of the corridor blocks, loaded behind the forward map's loads
     const double2 *h2 = (const double2 *)(a.dp.hblk + (size_t)gp0 * hstride);
     const int nh2 = (npieces * hstride) >> 1;
     bool bad = false;
+    // (GEO, members) the run-time values the samples read from the argument block: requested here, parked in vector registers across the forward map
+    double m_chi[4] = {0.0, 0.0, 0.0, 0.0}, m_invk = 0.0; int m_kappa = 0;
+    gptr<ll_u64> m_llv = nullptr;
+    if constexpr (GF) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) m_chi[i] = a.dp.pc.chi[i];
+        m_invk = a.dp.inv_kappa; m_kappa = a.dp.kappa;
+        m_llv = (gptr<ll_u64>)(a.out20ll + (size_t)p0 * 40);
+        asm volatile("" : "+v"(m_chi[0]), "+v"(m_chi[1]), "+v"(m_chi[2]), "+v"(m_chi[3]), "+v"(m_invk), "+v"(m_kappa), "+v"(m_llv));
+    }
     if constexpr (ET) {
         if (k == 0 && wg == 1 && wave == 0 && lane == 0 && stp()) stp()[44] = (long long)wall_clock64();
         const auto early = [&]() -> bool {
             if (has_task) {
+                if constexpr (GF) hv[0] = h2[lane < nh2 ? lane : nh2 - 1];          // (nh2 <= 54: the one trip there is)
+                else {
 #pragma unroll
                 for (int u = 0; u < 4; u++) { const int i = lane + 64 * u; hv[u] = h2[i < nh2 ? i : nh2 - 1]; }
+                }
             }
             unsigned *w = (unsigned *)(ev + 24 * 64);               // forward_knot_body's progress words (its rowbuf is ev)
             if (t == 0) { w[0] = 0u; w[2] = 0u; w[3] = 0u; w[4] = 0u; w[5] = st0; *verdict = 0u; }
@@ -181,6 +226,9 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
             if (wg == 0 && t == 0) call.f[k] = __builtin_nan("");
             return;
         }
+        if constexpr (GF) {
+            if (has_task && lane < nh2) { hS[2 * lane] = hv[0].x; hS[2 * lane + 1] = hv[0].y; }   // (two 8-byte halves: a wave's LDS starts at an odd double, pen_lds = 1509)
+        } else
         if (has_task) {
 #pragma unroll
             for (int u = 0; u < 4; u++) { const int i = lane + 64 * u; if (i < nh2) { hS[2 * i] = hv[u].x; hS[2 * i + 1] = hv[u].y; } }
@@ -212,8 +260,17 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
         long long *const mst = (k == 0 && wg == 1 && wave == 0 && lane == 0) ? stp() : nullptr;
         if (mst) mst[46] = (long long)wall_clock64();
         // (CH) what the reduction and the granule stores read from the argument block, once, in front of the samples
-        int m_lpp = a.lpp, m_t0 = task * a.ppw, m_N = N;
-        ll_u64 *m_ll = a.out20ll + (size_t)p0 * 40;
+        int m_lpp = GC::lpp;
+        if constexpr (!GF) m_lpp = a.lpp;
+        int m_t0 = task * g_ppw(), m_N = N;
+        ll_u64 *m_ll = nullptr;
+        if constexpr (!GF) m_ll = a.out20ll + (size_t)p0 * 40;
+        if constexpr (GF) {
+            m_N = as_uniform(m_N);
+            gptr<ll_u64> q_ll = as_uniform(m_llv);
+            asm volatile("" : "+s"(m_N), "+s"(q_ll));
+            m_ll = (ll_u64 *)q_ll;
+        } else
         if constexpr (CH) {
             m_N = as_uniform(m_N);
             gptr<ll_u64> q_ll = (gptr<ll_u64>)as_uniform(m_ll);
@@ -221,6 +278,13 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
             m_ll = (ll_u64 *)q_ll;
         }
         const int pl = lane / m_lpp, jl = lane - pl * m_lpp;
+        if constexpr (GF) {
+            DevProblem mdp = a.dp;
+#pragma unroll
+            for (int i = 0; i < 4; i++) mdp.pc.chi[i] = m_chi[i];
+            mdp.inv_kappa = m_invk; mdp.kappa = m_kappa;
+            if (pl < npieces) penalty_lane_samples<true>(mdp, ctl + (size_t)(m_t0 + pl) * 19, hS + (size_t)pl * hstride, ctl[(m_t0 + pl) * 19 + 18], jl, m_lpp, GC::kmax, red + lane * 21);
+        } else
         if constexpr (CH) {
             // the penalty weights too: each is read inside the branch of its violated constraint, a scalar trip in the middle of a lane's samples
             DevProblem mdp = a.dp;

@@ -57,6 +57,10 @@ int frx_eval_stage_times(frx_problem *p, const double *x, int reps, double *out3
  * 0 = one launch per stage.  The environment variable FRX_EVAL_FUSED=0 turns the form off for every handle created afterwards. */
 int frx_debug_set_eval_fused(frx_problem *p, int enable);
 int frx_debug_eval_fused(const frx_problem *p);
+/* Which instantiation of the one-launch form the handle launches: 1 = the compile-time geometry class (17 samples per piece, 3 pieces per wave-task, corridor blocks of 8
+ * half-spaces, six reduction steps - the handle's geometry equals it exactly), 0 = the run-time form (any other geometry, FRX_EVAL_GEOM=0, or no one-launch form at all).
+ * The two give the same bits. */
+int frx_debug_eval_geometry(const frx_problem *p);
 /* The solo form of an evaluation (one workgroup per candidate runs forward map, penalty integral and adjoint in ONE launch; batches larger than the clusters of the
  * one-launch form reach; the per-stage rounds of frx_optimize take it too).  mode 0 = never, 1 = from the handle's batch-size threshold on (default; FRX_EVAL_SOLO_MIN_B),
  * 2 = at every batch size, also where the cluster form would apply.  Results are bit-identical to the three stage launches (replaces the same objectiveFunc,
