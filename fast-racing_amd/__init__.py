@@ -77,7 +77,7 @@ DEBUG_SYMBOLS = [
     "frx_debug_trace", "frx_resident_profile", "frx_debug_direction_log", "frx_debug_direction_log_read", "frx_debug_set_resident_retry",
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
     "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_eval_geometry", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
-    "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device", "frx_debug_dv_layout", "frx_debug_dv_round",
+    "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device", "frx_debug_dv_layout", "frx_debug_dv_round", "frx_debug_fold_rows",
 ]
 
 # frx_trajectory_check (include/frx.h): fields of a row and flag bits
@@ -179,6 +179,7 @@ def lib():
         L.frx_trajectory_clearance_workspace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.frx_trajectory_clearance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_debug_set_clear_chunk.argtypes = [C.c_void_p, C.c_int]
+        L.frx_debug_fold_rows.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
         L.frx_corridor_generate_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_corridor_generate_batch_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
@@ -738,17 +739,26 @@ class Problem:
     def penalty_device(self, T_ptr: int, C_ptr: int, out_ptr: int, stream: int = 0):
         _check(lib().frx_penalty_eval_device(self.h, T_ptr, C_ptr, out_ptr, stream))
 
+    def _traj_TC(self, who, T, Cf):
+        """(T, Cf) of a trajectory_* call as flat float64 arrays of the handle's sizes"""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1); Cf = np.ascontiguousarray(Cf, dtype=np.float64).reshape(-1)
+        if T.size != self.P or Cf.size != 18 * self.P:
+            raise ValueError(f"{who}: expected {self.P} durations and {18 * self.P} coefficients, got {T.size} and {Cf.size}")
+        return T, Cf
+
+    def _traj_folded(self, fields, cand_key, entry, *args):
+        """dict(piece (P, n), <cand_key> (B, n), flags (B,) uint32) plus the candidate rows' n fields by name, filled by entry(handle, *args, piece, cand, flags)"""
+        piece = np.zeros((self.P, len(fields))); cand = np.zeros((self.B, len(fields))); flags = np.zeros(self.B, np.uint32)
+        _check(entry(self.h, *args, piece.ctypes.data, cand.ctypes.data, flags.ctypes.data))
+        out = {"piece": piece, cand_key: cand, "flags": flags}
+        out.update({name: cand[:, i] for i, name in enumerate(fields)})
+        return out
+
     def trajectory_check(self, T, Cf, intervals: int = 256):
         """Dense feasibility certificate of the batch (T, C) against the handle's corridors and limits (frx_trajectory_check):
         dict(piece (P, 8), candidate (B, 8), flags (B,) uint32) plus the candidate rows' fields by name (CHECK_FIELDS)."""
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1); Cf = np.ascontiguousarray(Cf, dtype=np.float64).reshape(-1)
-        if T.size != self.P or Cf.size != 18 * self.P:
-            raise ValueError(f"trajectory_check: expected {self.P} durations and {18 * self.P} coefficients, got {T.size} and {Cf.size}")
-        piece = np.zeros((self.P, 8)); cand = np.zeros((self.B, 8)); flags = np.zeros(self.B, np.uint32)
-        _check(lib().frx_trajectory_check(self.h, T.ctypes.data, Cf.ctypes.data, int(intervals), piece.ctypes.data, cand.ctypes.data, flags.ctypes.data))
-        out = dict(piece=piece, candidate=cand, flags=flags)
-        out.update({name: cand[:, i] for i, name in enumerate(CHECK_FIELDS)})
-        return out
+        T, Cf = self._traj_TC("trajectory_check", T, Cf)
+        return self._traj_folded(CHECK_FIELDS, "candidate", lib().frx_trajectory_check, T.ctypes.data, Cf.ctypes.data, int(intervals))
 
     def trajectory_check_device(self, T_ptr: int, C_ptr: int, out_ptr: int, intervals: int = 256, stream: int = 0):
         """frx_trajectory_check_device: the piece rows (P x 8 doubles at out_ptr) as one launch on `stream`, device pointers, no synchronisation."""
@@ -758,14 +768,8 @@ class Problem:
         """Exact per-piece extrema of speed, acceleration, thrust and body rate of the batch (T, C) with the times they are attained at
         (frx_trajectory_extrema; nothing is sampled, the corridor is not covered): dict(piece (P, 10), cand (B, 10), flags (B,) uint32 of
         CHECK_FLAG_* bits) plus the candidate rows' fields by name (EXTREMA_FIELDS)."""
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1); Cf = np.ascontiguousarray(Cf, dtype=np.float64).reshape(-1)
-        if T.size != self.P or Cf.size != 18 * self.P:
-            raise ValueError(f"trajectory_extrema: expected {self.P} durations and {18 * self.P} coefficients, got {T.size} and {Cf.size}")
-        piece = np.zeros((self.P, 10)); cand = np.zeros((self.B, 10)); flags = np.zeros(self.B, np.uint32)
-        _check(lib().frx_trajectory_extrema(self.h, T.ctypes.data, Cf.ctypes.data, piece.ctypes.data, cand.ctypes.data, flags.ctypes.data))
-        out = dict(piece=piece, cand=cand, flags=flags)
-        out.update({name: cand[:, i] for i, name in enumerate(EXTREMA_FIELDS)})
-        return out
+        T, Cf = self._traj_TC("trajectory_extrema", T, Cf)
+        return self._traj_folded(EXTREMA_FIELDS, "cand", lib().frx_trajectory_extrema, T.ctypes.data, Cf.ctypes.data)
 
     def trajectory_extrema_device(self, T_ptr: int, C_ptr: int, out_ptr: int, stream: int = 0):
         """frx_trajectory_extrema_device: the piece rows (P x 10 doubles at out_ptr) as one launch on `stream`, device pointers, no synchronisation."""
@@ -775,9 +779,7 @@ class Problem:
         """Every candidate of the batch (T, C) at n_samples times with its SE(3) outputs (frx_trajectory_sample): times (B, n_samples) from each
         candidate's start, else t0 + s dt (dt > 0) or n_samples points over each duration (dt == 0).  dict(rows (B, S, 20)) plus the named
         views of the rows (SAMPLE_VIEWS: pos, vel, acc, jerk (B, S, 3), thrust (B, S), quat (B, S, 4) as w, x, y, z, omega (B, S, 3))."""
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1); Cf = np.ascontiguousarray(Cf, dtype=np.float64).reshape(-1)
-        if T.size != self.P or Cf.size != 18 * self.P:
-            raise ValueError(f"trajectory_sample: expected {self.P} durations and {18 * self.P} coefficients, got {T.size} and {Cf.size}")
+        T, Cf = self._traj_TC("trajectory_sample", T, Cf)
         S = int(n_samples)
         tp = None
         if times is not None:
@@ -800,18 +802,11 @@ class Problem:
     def trajectory_clearance(self, T, Cf, obs, intervals: int = 256):
         """Clearance of the batch (T, C) against the obstacle cloud obs (n_obs, 3) (frx_trajectory_clearance): dict(piece (P, 4), cand (B, 4),
         flags (B,) uint32) plus the candidate rows' fields by name (CLEAR_FIELDS: ell >= 1 means free, dist in metres, worst_t, worst_i)."""
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1); Cf = np.ascontiguousarray(Cf, dtype=np.float64).reshape(-1)
-        if T.size != self.P or Cf.size != 18 * self.P:
-            raise ValueError(f"trajectory_clearance: expected {self.P} durations and {18 * self.P} coefficients, got {T.size} and {Cf.size}")
+        T, Cf = self._traj_TC("trajectory_clearance", T, Cf)
         obs = np.ascontiguousarray(obs, dtype=np.float64)
         if obs.ndim != 2 or obs.shape[1] != 3:
             raise ValueError(f"trajectory_clearance: obs must have shape (n_obs, 3), got {obs.shape}")
-        piece = np.zeros((self.P, 4)); cand = np.zeros((self.B, 4)); flags = np.zeros(self.B, np.uint32)
-        _check(lib().frx_trajectory_clearance(self.h, T.ctypes.data, Cf.ctypes.data, int(intervals), obs.shape[0], obs.ctypes.data, piece.ctypes.data,
-                                              cand.ctypes.data, flags.ctypes.data))
-        out = dict(piece=piece, cand=cand, flags=flags)
-        out.update({name: cand[:, i] for i, name in enumerate(CLEAR_FIELDS)})
-        return out
+        return self._traj_folded(CLEAR_FIELDS, "cand", lib().frx_trajectory_clearance, T.ctypes.data, Cf.ctypes.data, int(intervals), obs.shape[0], obs.ctypes.data)
 
     def trajectory_clearance_workspace(self, n_obs: int, intervals: int = 256) -> int:
         """frx_trajectory_clearance_workspace: bytes of scratch trajectory_clearance_device needs for a cloud of n_obs points (0: none)."""

@@ -34,6 +34,7 @@
 #include "frx_host_pool.hpp"
 #include "frx_host_setup.hpp"
 #include "frx_compact.hpp"
+#include "frx_traj_fold.hpp"
 
 namespace {
 
@@ -1053,17 +1054,38 @@ int frx_penalty_eval_device(frx_problem *p, const double *T_dev, const double *C
     return FRX_OK;
 }
 
-int frx_penalty_eval(frx_problem *p, const double *T, const double *C, double *cost, double *gdT, double *gdC) {
-    if (!p || !T || !C || !cost || !gdT || !gdC) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    HIP_TRY(hipSetDevice(p->device));
+// The blocking entries that take (T, C) from the host - penalty, check, extrema, clearance, sample - run: argument checks, stage_TC ((T, C) -> d_T, d_C through the
+// pinned h_T, h_C), their _device entry on the handle's stream, fetch_rows, then a fold on the host (frx_traj_fold.hpp for the three that have candidate rows).
+static int stage_TC(frx_problem *p, const double *T, const double *C) {
     std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
     std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
     HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
-    int rc = frx_penalty_eval_device(p, p->d_T.p, p->d_C.p, p->d_out20.p, p->stream);
-    if (rc != FRX_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(p->h_out20.p, p->d_out20.p, sizeof(double) * 20 * (size_t)p->P, hipMemcpyDeviceToHost, p->stream));
+    return FRX_OK;
+}
+// n <= 20 P doubles of piece rows -> h_out20, complete on return; piece_out, when given, gets a copy
+static int fetch_rows(frx_problem *p, const double *d_rows, size_t n, double *piece_out) {
+    HIP_TRY(hipMemcpyAsync(p->h_out20.p, d_rows, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
+    if (piece_out) std::memcpy(piece_out, p->h_out20.p, sizeof(double) * n);
+    return FRX_OK;
+}
+// a scratch buffer that grows to `need` doubles
+static int grow(DevBuf<double> &buf, size_t need, const char *entry) {
+    if (buf.n < need && buf.alloc(need) != hipSuccess) {
+        (void)hipGetLastError();                                            // (a failed allocation is no error of a later launch)
+        return fail(FRX_ERR_ALLOC, std::string(entry) + ": cannot allocate " + std::to_string(need * sizeof(double)) + " bytes on the device");
+    }
+    return FRX_OK;
+}
+#define FRX_TRY(expr) do { const int rc_ = (expr); if (rc_ != FRX_OK) return rc_; } while (0)
+
+int frx_penalty_eval(frx_problem *p, const double *T, const double *C, double *cost, double *gdT, double *gdC) {
+    if (!p || !T || !C || !cost || !gdT || !gdC) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    HIP_TRY(hipSetDevice(p->device));
+    FRX_TRY(stage_TC(p, T, C));
+    FRX_TRY(frx_penalty_eval_device(p, p->d_T.p, p->d_C.p, p->d_out20.p, p->stream));
+    FRX_TRY(fetch_rows(p, p->d_out20.p, 20 * (size_t)p->P, nullptr));
     // accumulate, like cuda_computer::compute (cc.cu:549-559)
     for (int b = 0; b < p->B; b++) {
         double s = 0.0;
@@ -1092,51 +1114,11 @@ int frx_trajectory_check(frx_problem *p, const double *T, const double *C, int i
     if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
     HIP_TRY(hipSetDevice(p->device));
     if (!p->d_check.p) HIP_TRY(p->d_check.alloc((size_t)p->P * FRX_CHECK_FIELDS));
-    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
-    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
-    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
-    const int rc = frx_trajectory_check_device(p, p->d_T.p, p->d_C.p, intervals, p->d_check.p, p->stream);
-    if (rc != FRX_OK) return rc;
-    double *rows = p->h_out20.p;                                            // (P x 20 doubles of staging: the P x 8 rows fit)
-    HIP_TRY(hipMemcpyAsync(rows, p->d_check.p, sizeof(double) * FRX_CHECK_FIELDS * (size_t)p->P, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (piece_out) std::memcpy(piece_out, rows, sizeof(double) * FRX_CHECK_FIELDS * (size_t)p->P);
-    // per candidate, in piece order: max (min for THRUST_MIN), NaN propagating; the worst reach keeps the first piece that attains it
-    auto nmax = [](double a, double b) { return (a > b || a != a) ? a : b; };
-    auto nmin = [](double a, double b) { return (a < b || a != a) ? a : b; };
-    for (int b = 0; b < p->B; b++) {
-        double *o = cand_out + (size_t)FRX_CHECK_FIELDS * b;
-        double t0 = 0.0;
-        for (int gp = p->poff[b]; gp < p->poff[b + 1]; gp++) {
-            const double *r = rows + (size_t)FRX_CHECK_FIELDS * gp;
-            if (gp == p->poff[b]) {
-                for (int f = 0; f < 6; f++) o[f] = r[f];
-                o[FRX_CHECK_WORST_T] = r[FRX_CHECK_WORST_T]; o[FRX_CHECK_WORST_K] = 0.0;
-            } else {
-                const double a = o[FRX_CHECK_CORRIDOR], c = r[FRX_CHECK_CORRIDOR];
-                if ((c > a && a == a) || (c != c && a == a)) { o[FRX_CHECK_WORST_T] = t0 + r[FRX_CHECK_WORST_T]; o[FRX_CHECK_WORST_K] = (double)(gp - p->poff[b]); }
-                o[FRX_CHECK_CORRIDOR] = nmax(a, c);
-                o[FRX_CHECK_SPEED] = nmax(o[FRX_CHECK_SPEED], r[FRX_CHECK_SPEED]);
-                o[FRX_CHECK_THRUST_MIN] = nmin(o[FRX_CHECK_THRUST_MIN], r[FRX_CHECK_THRUST_MIN]);
-                o[FRX_CHECK_THRUST_MAX] = nmax(o[FRX_CHECK_THRUST_MAX], r[FRX_CHECK_THRUST_MAX]);
-                o[FRX_CHECK_BODY_RATE] = nmax(o[FRX_CHECK_BODY_RATE], r[FRX_CHECK_BODY_RATE]);
-                o[FRX_CHECK_ACC] = nmax(o[FRX_CHECK_ACC], r[FRX_CHECK_ACC]);
-            }
-            t0 += T[gp];
-        }
-        if (flags) {
-            unsigned fl = 0u;
-            if (o[FRX_CHECK_CORRIDOR] > 0.0) fl |= FRX_CHECK_FLAG_CORRIDOR;
-            if (o[FRX_CHECK_SPEED] > p->cfg.vel_max) fl |= FRX_CHECK_FLAG_SPEED;
-            if (o[FRX_CHECK_THRUST_MIN] < p->cfg.thr_acc_min) fl |= FRX_CHECK_FLAG_THRUST_MIN;
-            if (o[FRX_CHECK_THRUST_MAX] > p->cfg.thr_acc_max) fl |= FRX_CHECK_FLAG_THRUST_MAX;
-            if (o[FRX_CHECK_BODY_RATE] > p->cfg.body_rate_max) fl |= FRX_CHECK_FLAG_BODY_RATE;
-            for (int f = 0; f < FRX_CHECK_FIELDS; f++)
-                if (!std::isfinite(o[f])) fl |= FRX_CHECK_FLAG_NONFINITE;
-            flags[b] = fl;
-        }
-    }
+    FRX_TRY(stage_TC(p, T, C));
+    FRX_TRY(frx_trajectory_check_device(p, p->d_T.p, p->d_C.p, intervals, p->d_check.p, p->stream));
+    FRX_TRY(fetch_rows(p, p->d_check.p, (size_t)FRX_CHECK_FIELDS * p->P, piece_out));
+    const double lim[4] = {p->cfg.vel_max, p->cfg.thr_acc_min, p->cfg.thr_acc_max, p->cfg.body_rate_max};
+    frx::fold_check(p->B, p->poff.data(), T, p->h_out20.p, lim, cand_out, flags);
     return FRX_OK;
 }
 
@@ -1154,41 +1136,11 @@ int frx_trajectory_extrema(frx_problem *p, const double *T, const double *C, dou
     HIP_TRY(hipSetDevice(p->device));
     const size_t n_rows = (size_t)FRX_EXTREMA_FIELDS * p->P;
     if (!p->d_extrema.p) HIP_TRY(p->d_extrema.alloc(n_rows));
-    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
-    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
-    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
-    const int rc = frx_trajectory_extrema_device(p, p->d_T.p, p->d_C.p, p->d_extrema.p, p->stream);
-    if (rc != FRX_OK) return rc;
-    double *rows = p->h_out20.p;                                            // (P x 20 doubles of staging: the P x 10 rows fit)
-    HIP_TRY(hipMemcpyAsync(rows, p->d_extrema.p, sizeof(double) * n_rows, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (piece_out) std::memcpy(piece_out, rows, sizeof(double) * n_rows);
-    // per candidate, in piece order: a later piece replaces on strict > (< for THRUST_MIN) or when it is not a number, and a field that is not a number
-    // stays; the time goes with the value, counted from the candidate's start on the prefix of durations summed left to right as frx_trajectory_check sums it
-    for (int b = 0; b < p->B; b++) {
-        double *o = cand_out + (size_t)FRX_EXTREMA_FIELDS * b;
-        double t0 = 0.0;
-        for (int gp = p->poff[b]; gp < p->poff[b + 1]; gp++) {
-            const double *r = rows + (size_t)FRX_EXTREMA_FIELDS * gp;
-            for (int f = 0; f < 5; f++) {
-                const double a = o[f], c = r[f];
-                const bool better = f == FRX_EXTREMA_THRUST_MIN ? c < a : c > a;
-                if (gp == p->poff[b] || (a == a && (better || c != c))) { o[f] = c; o[5 + f] = t0 + r[5 + f]; }
-            }
-            t0 += T[gp];
-        }
-        if (flags) {
-            unsigned fl = 0u;
-            if (o[FRX_EXTREMA_SPEED] > p->cfg.vel_max) fl |= FRX_CHECK_FLAG_SPEED;
-            if (o[FRX_EXTREMA_THRUST_MIN] < p->cfg.thr_acc_min) fl |= FRX_CHECK_FLAG_THRUST_MIN;
-            if (o[FRX_EXTREMA_THRUST_MAX] > p->cfg.thr_acc_max) fl |= FRX_CHECK_FLAG_THRUST_MAX;
-            if (o[FRX_EXTREMA_BODY_RATE] > p->cfg.body_rate_max) fl |= FRX_CHECK_FLAG_BODY_RATE;
-            for (int f = 0; f < FRX_EXTREMA_FIELDS; f++)
-                if (!std::isfinite(o[f])) fl |= FRX_CHECK_FLAG_NONFINITE;
-            flags[b] = fl;
-        }
-    }
+    FRX_TRY(stage_TC(p, T, C));
+    FRX_TRY(frx_trajectory_extrema_device(p, p->d_T.p, p->d_C.p, p->d_extrema.p, p->stream));
+    FRX_TRY(fetch_rows(p, p->d_extrema.p, n_rows, piece_out));
+    const double lim[4] = {p->cfg.vel_max, p->cfg.thr_acc_min, p->cfg.thr_acc_max, p->cfg.body_rate_max};
+    frx::fold_extrema(p->B, p->poff.data(), T, p->h_out20.p, lim, cand_out, flags);
     return FRX_OK;
 }
 
@@ -1223,54 +1175,16 @@ int frx_trajectory_clearance_device(frx_problem *p, const double *T_dev, const d
 int frx_trajectory_clearance(frx_problem *p, const double *T, const double *C, int intervals, int n_obs, const double *obs, double *piece_out, double *cand_out,
                              unsigned *flags) {
     int chunk = 0, nchunks = 0;
-    const int rc = clear_args(p, T, C, intervals, n_obs, obs, cand_out, &chunk, &nchunks);
-    if (rc != FRX_OK) return rc;
+    FRX_TRY(clear_args(p, T, C, intervals, n_obs, obs, cand_out, &chunk, &nchunks));
     HIP_TRY(hipSetDevice(p->device));
     const size_t n_rows = (size_t)FRX_CLEAR_FIELDS * p->P, n_cloud = 3 * (size_t)n_obs, n_work = nchunks > 1 ? n_rows * (size_t)nchunks : 0;
-    const size_t need = n_rows + n_cloud + n_work;
-    if (p->d_clear.n < need && p->d_clear.alloc(need) != hipSuccess) {
-        (void)hipGetLastError();                                            // (a failed allocation is no error of a later launch)
-        return fail(FRX_ERR_ALLOC, "frx_trajectory_clearance: cannot allocate " + std::to_string(need * sizeof(double)) + " bytes on the device");
-    }
+    FRX_TRY(grow(p->d_clear, n_rows + n_cloud + n_work, "frx_trajectory_clearance"));
     double *d_rows = p->d_clear.p, *d_obs = d_rows + n_rows, *d_work = n_work ? d_obs + n_cloud : nullptr;
-    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
-    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
-    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+    FRX_TRY(stage_TC(p, T, C));
     HIP_TRY(hipMemcpyAsync(d_obs, obs, sizeof(double) * n_cloud, hipMemcpyHostToDevice, p->stream));
-    const int lrc = frx_trajectory_clearance_device(p, p->d_T.p, p->d_C.p, intervals, n_obs, d_obs, d_work, d_rows, p->stream);
-    if (lrc != FRX_OK) return lrc;
-    double *rows = p->h_out20.p;                                            // (P x 20 doubles of staging: the P x 4 rows fit)
-    HIP_TRY(hipMemcpyAsync(rows, d_rows, sizeof(double) * n_rows, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (piece_out) std::memcpy(piece_out, rows, sizeof(double) * n_rows);
-    // per candidate, in piece order, the kernel's order on (ELL, piece): NaN beats any number, then the smaller value, then the earlier piece; DIST is a
-    // NaN-propagating min; the prefix of durations is summed left to right as frx_trajectory_check sums it
-    for (int b = 0; b < p->B; b++) {
-        double *o = cand_out + (size_t)FRX_CLEAR_FIELDS * b;
-        double t0 = 0.0;
-        for (int gp = p->poff[b]; gp < p->poff[b + 1]; gp++) {
-            const double *r = rows + (size_t)FRX_CLEAR_FIELDS * gp;
-            if (gp == p->poff[b]) {
-                for (int f = 0; f < FRX_CLEAR_FIELDS; f++) o[f] = r[f];
-            } else {
-                const double a = o[FRX_CLEAR_ELL], c = r[FRX_CLEAR_ELL];
-                if (a == a && (c < a || c != c)) {
-                    o[FRX_CLEAR_ELL] = c; o[FRX_CLEAR_WORST_T] = t0 + r[FRX_CLEAR_WORST_T]; o[FRX_CLEAR_WORST_I] = r[FRX_CLEAR_WORST_I];
-                }
-                const double d = o[FRX_CLEAR_DIST], e = r[FRX_CLEAR_DIST];
-                o[FRX_CLEAR_DIST] = (d < e || d != d) ? d : e;
-            }
-            t0 += T[gp];
-        }
-        if (flags) {
-            unsigned fl = 0u;
-            if (o[FRX_CLEAR_ELL] < 1.0) fl |= FRX_CLEAR_FLAG_COLLISION;
-            for (int f = 0; f < FRX_CLEAR_FIELDS; f++)
-                if (!std::isfinite(o[f])) fl |= FRX_CLEAR_FLAG_NONFINITE;
-            flags[b] = fl;
-        }
-    }
+    FRX_TRY(frx_trajectory_clearance_device(p, p->d_T.p, p->d_C.p, intervals, n_obs, d_obs, d_work, d_rows, p->stream));
+    FRX_TRY(fetch_rows(p, d_rows, n_rows, piece_out));
+    frx::fold_clearance(p->B, p->poff.data(), T, p->h_out20.p, nullptr, cand_out, flags);
     return FRX_OK;
 }
 
@@ -1279,6 +1193,13 @@ int frx_trajectory_clearance(frx_problem *p, const double *T, const double *C, i
 int frx_debug_set_clear_chunk(frx_problem *p, int points) {
     if (!p || points < 0) return fail(FRX_ERR_INVALID_ARG, "null handle or a negative chunk");
     p->clear_chunk = points;
+    return FRX_OK;
+}
+
+// Tests: the fold of the blocking check (kind 0), extrema (1) and clearance (2) entries on piece rows the caller made up; no handle, no device.
+int frx_debug_fold_rows(int kind, int B, const int *piece_off, const double *T, const double *rows, const double *limits, double *cand_out, unsigned *flags) {
+    if (kind < 0 || kind > 2 || B < 1 || !piece_off || !T || !rows || !limits) return fail(FRX_ERR_INVALID_ARG, "kind must be 0, 1 or 2, B >= 1 and no input NULL");
+    (kind == 0 ? frx::fold_check : kind == 1 ? frx::fold_extrema : frx::fold_clearance)(B, piece_off, T, rows, limits, cand_out, flags);
     return FRX_OK;
 }
 
@@ -1309,24 +1230,16 @@ int frx_trajectory_sample_device(frx_problem *p, const double *T_dev, const doub
 
 int frx_trajectory_sample(frx_problem *p, const double *T, const double *C, int n_samples, double t0, double dt, const double *times, double *out) {
     size_t n_out = 0;
-    const int rc = sample_args(p, T, C, n_samples, t0, dt, times, out, &n_out);
-    if (rc != FRX_OK) return rc;
+    FRX_TRY(sample_args(p, T, C, n_samples, t0, dt, times, out, &n_out));
     HIP_TRY(hipSetDevice(p->device));
     const size_t n_times = times ? n_out / FRX_SAMPLE_FIELDS : 0, need = n_out + n_times;   // (rows first: 16-byte aligned)
     if (need > SIZE_MAX / sizeof(double)) return fail(FRX_ERR_ALLOC, "frx_trajectory_sample: output too large");
-    if (p->d_sample.n < need && p->d_sample.alloc(need) != hipSuccess) {
-        (void)hipGetLastError();                                            // (a failed allocation is no error of a later launch)
-        return fail(FRX_ERR_ALLOC, "frx_trajectory_sample: cannot allocate " + std::to_string(need * sizeof(double)) + " bytes on the device");
-    }
+    FRX_TRY(grow(p->d_sample, need, "frx_trajectory_sample"));
     double *d_out = p->d_sample.p, *d_times = times ? p->d_sample.p + n_out : nullptr;
-    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
-    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
-    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+    FRX_TRY(stage_TC(p, T, C));
     if (times) HIP_TRY(hipMemcpyAsync(d_times, times, sizeof(double) * n_times, hipMemcpyHostToDevice, p->stream));
-    const int lrc = frx_trajectory_sample_device(p, p->d_T.p, p->d_C.p, n_samples, t0, dt, d_times, d_out, p->stream);
-    if (lrc != FRX_OK) return lrc;
-    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, p->stream));
+    FRX_TRY(frx_trajectory_sample_device(p, p->d_T.p, p->d_C.p, n_samples, t0, dt, d_times, d_out, p->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, p->stream));   // (the rows go to the caller as they are: no fold, no staging)
     HIP_TRY(hipStreamSynchronize(p->stream));
     return FRX_OK;
 }

@@ -18,9 +18,6 @@
 
 namespace frx {
 
-// NaN-propagating max / min: the result is NaN when either operand is
-__device__ __forceinline__ double chk_max(double a, double b) { return (a > b || a != a) ? a : b; }
-__device__ __forceinline__ double chk_min(double a, double b) { return (a < b || a != a) ? a : b; }
 // (value, index) of the worst reach: NaN beats any number, then the larger value, then the lower index
 __device__ __forceinline__ bool chk_worse(double a, int ia, double b, int ib) {
     const bool na = a != a, nb = b != b;
@@ -63,21 +60,16 @@ __global__ void __launch_bounds__(256) k_traj_check(DevProblem dp, const double 
             poly_eval<1>(c, s1, vel);
             poly_eval<2>(c, s1, acc);
             poly_eval<3>(c, s1, jer);
-            // attitude (CPU.hpp:266-276): zB = h / |h|, yB = normalise(0, zB.z, -zB.y), xB = yB x zB
-            const double h[3] = {acc[0], acc[1], acc[2] + gAcc};
-            const double F2 = dot3(h, h), invF = rsqrt_fast(F2);
-            const double zB[3] = {h[0] * invF, h[1] * invF, h[2] * invF};
-            const double invM = rsqrt_fast(zB[2] * zB[2] + zB[1] * zB[1]);
-            const double yB1 = zB[2] * invM, yB2 = -zB[1] * invM;
-            const double xB[3] = {yB1 * zB[2] - yB2 * zB[1], yB2 * zB[0], -(yB1 * zB[0])};
+            const FlatFrame fr = flat_frame(acc, gAcc);                       // attitude (CPU.hpp:266-276)
+            const double *xB = fr.xB, *zB = fr.zB, yB1 = fr.yB1, yB2 = fr.yB2;
             // limits (CPU.hpp:281-299, 347-398)
-            const double thr = sqrt(F2);
-            vspd = chk_max(vspd, sqrt(dot3(vel, vel)));
-            vacc = chk_max(vacc, sqrt(dot3(acc, acc)));
-            vthl = chk_min(vthl, thr);
-            vthh = chk_max(vthh, thr);
+            const double thr = sqrt(fr.F2);
+            vspd = nan_max(vspd, sqrt(dot3(vel, vel)));
+            vacc = nan_max(vacc, sqrt(dot3(acc, acc)));
+            vthl = nan_min(vthl, thr);
+            vthh = nan_max(vthh, thr);
             const double r0 = dot3(xB, jer), r1 = yB1 * jer[1] + yB2 * jer[2];
-            vbdr = chk_max(vbdr, sqrt(r0 * r0 + r1 * r1) * invF);
+            vbdr = nan_max(vbdr, sqrt(r0 * r0 + r1 * r1) * fr.invF);
             // corridor (CPU.hpp:322-328): records {n, n.(p_k - org) - safeMargin} after the origin org = hb[0..2]
             const double pl[3] = {pos[0] - hb[0], pos[1] - hb[1], pos[2] - hb[2]};
 #pragma unroll 2
@@ -96,7 +88,7 @@ __global__ void __launch_bounds__(256) k_traj_check(DevProblem dp, const double 
         const double ob = __shfl_xor(vbdr, off), oa = __shfl_xor(vacc, off);
         const int oi = __shfl_xor(icor, off);
         if (chk_worse(oc, oi, vcor, icor)) { vcor = oc; icor = oi; }
-        vspd = chk_max(vspd, os); vthl = chk_min(vthl, ol); vthh = chk_max(vthh, oh); vbdr = chk_max(vbdr, ob); vacc = chk_max(vacc, oa);
+        vspd = nan_max(vspd, os); vthl = nan_min(vthl, ol); vthh = nan_max(vthh, oh); vbdr = nan_max(vbdr, ob); vacc = nan_max(vacc, oa);
     }
     if (mine && jl == 0) {
         const int jw = icor / KS, kw = icor - jw * KS;

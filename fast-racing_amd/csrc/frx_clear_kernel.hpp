@@ -1,5 +1,5 @@
 // Clearance of a batch of trajectories against the obstacle cloud (frx_trajectory_clearance, include/frx.h): per fine piece, M + 1 samples
-// s_j = j (T / M) of the body ellipsoid C = R E - R = [xB yB zB](h), h = a + g e3, the check's arithmetic (frx_check_kernel.hpp) - against every
+// s_j = j (T / M) of the body ellipsoid C = R E - R = [xB yB zB](h), h = a + g e3, the check's frame (flat_frame, frx_math.hpp) - against every
 // cloud point o_i: u = o_i - p, q = (xB.u / e0)^2 + (yB.u / e1)^2 + (zB.u / e2)^2 (decomp_util's Ellipsoid::dist, squared), r = u.u, reduced to
 //   0 sqrt(min q)   1 sqrt(min r)   2 local time s_j of the sample that attains min q   3 index i of the point that attains it
 // under the total order (q, j, i): NaN beats any number, then the smaller q, then the lower j, then the lower i.  min r propagates NaN.  Every
@@ -24,8 +24,6 @@ static constexpr int CLEAR_THREADS = 256;                          // four waves
 static constexpr int CLEAR_R = CLEAR_PASS / CLEAR_THREADS;         // points a lane keeps in registers: 4
 static constexpr int CLEAR_STATE = 12;                             // doubles of a sample state: p, xB / e0, yB / e1, zB / e2
 
-// NaN-propagating min: the result is NaN when either operand is
-__device__ __forceinline__ double clr_min(double a, double b) { return (a < b || a != a) ? a : b; }
 // (q, j, i) a before (q, j, i) b: NaN beats any number, then the smaller q, then the lower j, then the lower i
 __device__ __forceinline__ bool clr_worse(double a, int ja, int ia, double b, int jb, int ib) {
     const bool na = a != a, nb = b != b;
@@ -85,18 +83,12 @@ __global__ void __launch_bounds__(CLEAR_THREADS) k_traj_clear(DevProblem dp, con
                 double pos[3], acc[3];
                 poly_eval<0>(cS, s1, pos);
                 poly_eval<2>(cS, s1, acc);
-                // attitude, the check's arithmetic: zB = h / |h|, yB = normalise(0, zB.z, -zB.y), xB = yB x zB
-                const double h[3] = {acc[0], acc[1], acc[2] + gAcc};
-                const double invF = rsqrt_fast(dot3(h, h));
-                const double zB[3] = {h[0] * invF, h[1] * invF, h[2] * invF};
-                const double invM = rsqrt_fast(zB[2] * zB[2] + zB[1] * zB[1]);
-                const double yB1 = zB[2] * invM, yB2 = -zB[1] * invM;
-                const double xB[3] = {yB1 * zB[2] - yB2 * zB[1], yB2 * zB[0], -(yB1 * zB[0])};
+                const FlatFrame fr = flat_frame(acc, gAcc);               // attitude: the check's frame
                 double *s = sS + tid * CLEAR_STATE;
                 s[0] = pos[0]; s[1] = pos[1]; s[2] = pos[2];
-                s[3] = xB[0] / e0; s[4] = xB[1] / e0; s[5] = xB[2] / e0;
-                s[6] = (0.0 * invM) / e1; s[7] = yB1 / e1; s[8] = yB2 / e1;
-                s[9] = zB[0] / e2; s[10] = zB[1] / e2; s[11] = zB[2] / e2;
+                s[3] = fr.xB[0] / e0; s[4] = fr.xB[1] / e0; s[5] = fr.xB[2] / e0;
+                s[6] = (0.0 * fr.invM) / e1; s[7] = fr.yB1 / e1; s[8] = fr.yB2 / e1;
+                s[9] = fr.zB[0] / e2; s[10] = fr.zB[1] / e2; s[11] = fr.zB[2] / e2;
             }
             __syncthreads();
 #pragma unroll 1
@@ -126,7 +118,7 @@ __global__ void __launch_bounds__(CLEAR_THREADS) k_traj_clear(DevProblem dp, con
             const double qk = qm[k] == -INFINITY ? (double)NAN : qm[k];            // (q >= 0: -inf can only stand for a NaN)
             if (idx < i1 && clr_worse(qk, jm[k], idx, bq, bj, bi)) { bq = qk; bj = jm[k]; bi = idx; }
         }
-        br = clr_min(br, rm == -INFINITY ? (double)NAN : rm);
+        br = nan_min(br, rm == -INFINITY ? (double)NAN : rm);
     }
 
     // across the wave, then across the waves through LDS
@@ -134,14 +126,14 @@ __global__ void __launch_bounds__(CLEAR_THREADS) k_traj_clear(DevProblem dp, con
         const double oq = __shfl_xor(bq, off), orr = __shfl_xor(br, off);
         const int oj = __shfl_xor(bj, off), oi = __shfl_xor(bi, off);
         if (clr_worse(oq, oj, oi, bq, bj, bi)) { bq = oq; bj = oj; bi = oi; }
-        br = clr_min(br, orr);
+        br = nan_min(br, orr);
     }
     if (lane == 0) { redq[wave] = bq; redr[wave] = br; redj[wave] = bj; redi[wave] = bi; }
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < CLEAR_THREADS / 64; w++) {
             if (clr_worse(redq[w], redj[w], redi[w], bq, bj, bi)) { bq = redq[w]; bj = redj[w]; bi = redi[w]; }
-            br = clr_min(br, redr[w]);
+            br = nan_min(br, redr[w]);
         }
         if (nchunks == 1) {
             double *o = rows + (size_t)piece * 4;
@@ -165,13 +157,13 @@ __global__ void __launch_bounds__(CLEAR_THREADS) k_traj_clear_reduce(int P, cons
         const double q = w[0];
         const int j = (int)w[2], i = (int)w[3];
         if (clr_worse(q, j, i, bq, bj, bi)) { bq = q; bj = j; bi = i; }
-        br = clr_min(br, w[1]);
+        br = nan_min(br, w[1]);
     }
     for (int off = 32; off > 0; off >>= 1) {
         const double oq = __shfl_xor(bq, off), orr = __shfl_xor(br, off);
         const int oj = __shfl_xor(bj, off), oi = __shfl_xor(bi, off);
         if (clr_worse(oq, oj, oi, bq, bj, bi)) { bq = oq; bj = oj; bi = oi; }
-        br = clr_min(br, orr);
+        br = nan_min(br, orr);
     }
     if (lane == 0) {
         double *o = rows + (size_t)piece * 4;

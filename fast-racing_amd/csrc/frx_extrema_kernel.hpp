@@ -12,7 +12,7 @@
 // dc[i] = c[i] * (deg - i) the recursion forms on its way down.  A derivative's leading coefficient is c[0] times positive integers and so is zero only
 // where c[0] is: leading zeros are stripped once, at the top, as the host's strip finds them only there.
 // Candidates: the roots in ascending order, then tau = 0, then tau = 1 (the host's order).  A maximum is replaced on strict >, a minimum on strict <, so the
-// first candidate wins a tie; a value that is not a number takes the field and stays (chk_max / chk_min).  The host's early-out for a numerically constant
+// first candidate wins a tie; a value that is not a number takes the field and stays (nan_max / nan_min).  The host's early-out for a numerically constant
 // magnitude is NOT taken: the ends are always candidates, a piece of constant speed reports that speed.
 // Row: [P][10] - SPEED, ACC, THRUST_MIN, THRUST_MAX, BODY_RATE, then the local time tau T of each.  T not finite or <= 0, or a coefficient not finite: all
 // ten NaN, decided once up front.  A row depends on its own T, C and g alone.

@@ -103,6 +103,25 @@ FRX_HD double rsqrt_fast(double x) {
 #endif
 }
 
+// The flatness frame of CPU.hpp:266-276 from the acceleration: h = acc + g e3, zB = h / |h|, yB = normalise(0, zB.z, -zB.y) (yB.x = 0 is not stored),
+// xB = yB x zB without the products by that zero; F2 = h.h, invF = 1 / |h|, invM = 1 / |(0, zB.z, -zB.y)|.  The one arithmetic of the trajectory check,
+// the clearance and the sampler, whose rows are compared bit for bit with one another.
+struct FlatFrame { double F2, invF, zB[3], invM, yB1, yB2, xB[3]; };
+FRX_HD FlatFrame flat_frame(const double *acc, double gAcc) {
+    FlatFrame f;
+    const double h[3] = {acc[0], acc[1], acc[2] + gAcc};
+    f.F2 = dot3(h, h); f.invF = rsqrt_fast(f.F2);
+    f.zB[0] = h[0] * f.invF; f.zB[1] = h[1] * f.invF; f.zB[2] = h[2] * f.invF;
+    f.invM = rsqrt_fast(f.zB[2] * f.zB[2] + f.zB[1] * f.zB[1]);
+    f.yB1 = f.zB[2] * f.invM; f.yB2 = -f.zB[1] * f.invM;
+    f.xB[0] = f.yB1 * f.zB[2] - f.yB2 * f.zB[1]; f.xB[1] = f.yB2 * f.zB[0]; f.xB[2] = -(f.yB1 * f.zB[0]);
+    return f;
+}
+
+// NaN-propagating max / min: the result is NaN when either operand is (a running NaN stays, a later NaN replaces a number)
+FRX_HD double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
+FRX_HD double nan_min(double a, double b) { return (a < b || a != a) ? a : b; }
+
 // Read-only view of doubles behind a pointer; fence() is where a device view forgets what it has read (see LdsView in
 // frx_kernels.hpp).  The host and the generic device path use this one.
 struct PtrView {

@@ -71,13 +71,8 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) k_traj_sample(const int *__res
             poly_eval<1>(c, sl, vel);
             poly_eval<2>(c, sl, acc);
             poly_eval<3>(c, sl, jer);
-            // frame (CPU.hpp:266-276, as frx_check_kernel.hpp): zB = h / |h|, yB = normalise(0, zB.z, -zB.y), xB = yB x zB
-            const double h[3] = {acc[0], acc[1], acc[2] + gAcc};
-            const double F2 = dot3(h, h), invF = rsqrt_fast(F2);
-            const double zB[3] = {h[0] * invF, h[1] * invF, h[2] * invF};
-            const double invM = rsqrt_fast(zB[2] * zB[2] + zB[1] * zB[1]);
-            const double yB1 = zB[2] * invM, yB2 = -zB[1] * invM;
-            const double xB[3] = {yB1 * zB[2] - yB2 * zB[1], yB2 * zB[0], -(yB1 * zB[0])};
+            const FlatFrame fr = flat_frame(acc, gAcc);                      // frame (CPU.hpp:266-276): the check's
+            const double *xB = fr.xB, *zB = fr.zB, yB1 = fr.yB1, yB2 = fr.yB2, F2 = fr.F2, invF = fr.invF, invM = fr.invM;
             // quaternion of R = [xB yB zB] (R01 = yB.x = 0): branch on the largest of (trace, R00, R11, R22), the earlier on a tie; then w >= 0
             const double R00 = xB[0], R11 = yB1, R22 = zB[2], R01 = 0.0, R02 = zB[0], R10 = xB[1], R12 = zB[1], R20 = xB[2], R21 = yB2;
             const double tr = R00 + R11 + R22;

@@ -1,0 +1,80 @@
+// Piece rows -> candidate rows and flag words of frx_trajectory_check / _extrema / _clearance (include/frx.h documents the rows).  Plain C++: no HIP and
+// no handle, so the blocking entries (frx_api.cpp), frx_debug_fold_rows and a host-only program share this one implementation.
+//
+// One shape: the candidates b = 0..B-1 own the pieces poff[b]..poff[b+1]-1 of T[] and of rows[] (piece rows, FIELDS doubles each), folded in piece order;
+// a time is counted from the candidate's start on the prefix of durations summed left to right.  limits = {vel_max, thr_acc_min, thr_acc_max,
+// body_rate_max}, compared with no slack.  cand_out ([B][FIELDS]) and flags ([B]) may each be NULL.  A candidate without pieces leaves its row as it is.
+#pragma once
+#include <cmath>
+
+#include "../../include/frx.h"
+#include "frx_math.hpp"
+
+namespace frx {
+
+// The walk the three folds share.  Candidate b's row o (the caller's, or a scratch row when cand_out is NULL) takes its pieces in order through
+// merge(o, piece row r, local piece index k, t0 = the piece's start from the candidate's); then flags[b] = bits(o) | `nonfinite` if a field of o is not finite.
+template <int FIELDS, class Merge, class Bits>
+inline void fold_rows(int B, const int *poff, const double *T, const double *rows, double *cand_out, unsigned *flags, unsigned nonfinite, Merge merge, Bits bits) {
+    for (int b = 0; b < B; b++) {
+        double own[FIELDS] = {0.0};
+        double *o = cand_out ? cand_out + (size_t)FIELDS * b : own;
+        double t0 = 0.0;
+        for (int gp = poff[b]; gp < poff[b + 1]; gp++) { merge(o, rows + (size_t)FIELDS * gp, gp - poff[b], t0); t0 += T[gp]; }
+        if (!flags) continue;
+        flags[b] = bits(o);
+        for (int f = 0; f < FIELDS; f++)
+            if (!std::isfinite(o[f])) flags[b] |= nonfinite;
+    }
+}
+// the four limits, which the check's and the extrema's rows hold in different fields
+inline unsigned fold_limit_bits(double speed, double thr_min, double thr_max, double body_rate, const double *limits) {
+    return (speed > limits[0] ? FRX_CHECK_FLAG_SPEED : 0u) | (thr_min < limits[1] ? FRX_CHECK_FLAG_THRUST_MIN : 0u) |
+           (thr_max > limits[2] ? FRX_CHECK_FLAG_THRUST_MAX : 0u) | (body_rate > limits[3] ? FRX_CHECK_FLAG_BODY_RATE : 0u);
+}
+
+// check: max (min for THRUST_MIN), NaN propagating; the worst reach keeps the first piece that attains it (a NaN counts as the worst), with its time
+inline void fold_check(int B, const int *poff, const double *T, const double *rows, const double *limits, double *cand_out, unsigned *flags) {
+    fold_rows<FRX_CHECK_FIELDS>(B, poff, T, rows, cand_out, flags, FRX_CHECK_FLAG_NONFINITE,
+        [](double *o, const double *r, int k, double t0) {
+            const double a = o[FRX_CHECK_CORRIDOR], c = r[FRX_CHECK_CORRIDOR];
+            if (k == 0 || (a == a && (c > a || c != c))) { o[FRX_CHECK_WORST_T] = k ? t0 + r[FRX_CHECK_WORST_T] : r[FRX_CHECK_WORST_T]; o[FRX_CHECK_WORST_K] = (double)k; }
+            for (int f = 0; f < 6; f++) o[f] = k == 0 ? r[f] : f == FRX_CHECK_THRUST_MIN ? nan_min(o[f], r[f]) : nan_max(o[f], r[f]);
+        },
+        [limits](const double *o) {
+            return (o[FRX_CHECK_CORRIDOR] > 0.0 ? FRX_CHECK_FLAG_CORRIDOR : 0u) |
+                   fold_limit_bits(o[FRX_CHECK_SPEED], o[FRX_CHECK_THRUST_MIN], o[FRX_CHECK_THRUST_MAX], o[FRX_CHECK_BODY_RATE], limits);
+        });
+}
+
+// extrema: per field the value with its time; a later piece replaces on strict > (< for THRUST_MIN) or when it is not a number, and a field that is not a
+// number stays
+inline void fold_extrema(int B, const int *poff, const double *T, const double *rows, const double *limits, double *cand_out, unsigned *flags) {
+    fold_rows<FRX_EXTREMA_FIELDS>(B, poff, T, rows, cand_out, flags, FRX_CHECK_FLAG_NONFINITE,
+        [](double *o, const double *r, int k, double t0) {
+            for (int f = 0; f < 5; f++) {
+                const double a = o[f], c = r[f];
+                const bool better = f == FRX_EXTREMA_THRUST_MIN ? c < a : c > a;
+                if (k == 0 || (a == a && (better || c != c))) { o[f] = c; o[5 + f] = t0 + r[5 + f]; }
+            }
+        },
+        [limits](const double *o) {
+            return fold_limit_bits(o[FRX_EXTREMA_SPEED], o[FRX_EXTREMA_THRUST_MIN], o[FRX_EXTREMA_THRUST_MAX], o[FRX_EXTREMA_BODY_RATE], limits);
+        });
+}
+
+// clearance: the kernel's order on (ELL, piece) - NaN beats any number, then the smaller value, then the earlier piece - with its time and point; DIST is
+// a NaN-propagating min.  The limits play no part.
+inline void fold_clearance(int B, const int *poff, const double *T, const double *rows, const double *, double *cand_out, unsigned *flags) {
+    fold_rows<FRX_CLEAR_FIELDS>(B, poff, T, rows, cand_out, flags, FRX_CLEAR_FLAG_NONFINITE,
+        [](double *o, const double *r, int k, double t0) {
+            const double a = o[FRX_CLEAR_ELL], c = r[FRX_CLEAR_ELL];
+            if (k == 0 || (a == a && (c < a || c != c))) {
+                o[FRX_CLEAR_ELL] = c; o[FRX_CLEAR_WORST_T] = k ? t0 + r[FRX_CLEAR_WORST_T] : r[FRX_CLEAR_WORST_T]; o[FRX_CLEAR_WORST_I] = r[FRX_CLEAR_WORST_I];
+            }
+            o[FRX_CLEAR_DIST] = k == 0 ? r[FRX_CLEAR_DIST] : nan_min(o[FRX_CLEAR_DIST], r[FRX_CLEAR_DIST]);
+        },
+        [](const double *o) { return o[FRX_CLEAR_ELL] < 1.0 ? FRX_CLEAR_FLAG_COLLISION : 0u; });
+}
+
+} // namespace frx

@@ -132,6 +132,12 @@ int frx_debug_compact_from_history(int m, int n, int hs, int bound, int newest, 
  * handle, 0 returns to the library's rule.  Rows do not depend on it. */
 int frx_debug_set_clear_chunk(frx_problem *p, int points);
 
+/* Tests: the host fold of frx_trajectory_check (kind 0), _extrema (1) and _clearance (2), piece rows to candidate rows and flag words - the code the blocking
+ * entries run (fast-racing_amd/csrc/frx_traj_fold.hpp) - on rows the caller supplies: candidate b owns the pieces piece_off[b] .. piece_off[b + 1] - 1 of T[] and
+ * rows[] (FRX_CHECK_ / FRX_EXTREMA_ / FRX_CLEAR_FIELDS doubles a piece); limits[4] = {vel_max, thr_acc_min, thr_acc_max, body_rate_max}.  cand_out ([B][fields])
+ * and flags ([B]) may each be NULL.  Needs no handle and no device. */
+int frx_debug_fold_rows(int kind, int B, const int *piece_off, const double *T, const double *rows, const double *limits, double *cand_out, unsigned *flags);
+
 /* Tests: the sight line of frx_corridor_generate_batch (map_blocked, fast-racing_amd/csrc/frx_chain_kernel.hpp) run on the device for n_pairs pairs of points
  * a[3 n_pairs], b[3 n_pairs] (host buffers; the map's cells are uploaded): out[i] = 0 / 1, to be compared with frx_map_is_blocked verdict for verdict. */
 int frx_debug_map_blocked_device(int device, const frx_voxel_map *map, int n_pairs, const double *a, const double *b, int *out);
