@@ -29,6 +29,7 @@
 #include "../../include/frx.h"
 #include "../../include/frx_debug.h"
 #include "frx_device.hpp"
+#include "frx_launch_forms.hpp"
 #include "frx_internal.hpp"
 #include "frx_lbfgs.hpp"
 #include "frx_host_pool.hpp"
@@ -243,8 +244,7 @@ struct frx_problem {
     int dv_mem = 0; size_t dv_hs = 0;
     double *pending_f = nullptr, *pending_g = nullptr;      // outputs of an frx_objective_eval_async awaiting frx_wait
     // line-search tap of k_backward_knot (set only while optimize_device_vectors runs)
-    const double *tap_d = nullptr; const int *tap_flags = nullptr; void *tap_res = nullptr;
-    unsigned *tap_arrive = nullptr; volatile unsigned *tap_flag = nullptr; unsigned tap_round = 0;
+    frx::TapLaunch tap;
     DevBuf<unsigned> d_arrive; PinBuf<unsigned> h_flag; DevBuf<int> d_flags, d_pflags;
     // resident round kernel (frx_round_kernel.hpp): cluster exchange buffers and mapped mailboxes, allocated on first use
     DevBuf<double> d_pubsyg, d_part, d_upub, d_dpub, d_rdbg, d_out20ll;
@@ -298,10 +298,9 @@ int launch_eval(frx_problem *p, const double *x_dev, double *f_dev, double *g_de
     // handle takes the stage kernels by itself - also on the capturable _device form and inside the host-vector L-BFGS, which have no status check of their own.
     // No HIP call here (the caller may be capturing): the device's sticky word is cleared at the next host-synchronous point (eval_cluster_status).
     if (p->eval_fused && p->h_ev_status.p && *(volatile unsigned *)p->h_ev_status.p != 0u) { p->eval_fused_code = *(volatile unsigned *)p->h_ev_status.p; p->eval_fused = 0; }
-    const bool solo_ok = backward && p->geo.lds_solo && p->geo.solver == frx::SOLVER_KNOT_PCR && (!p->dp.stamps || p->eval_solo == 2);   // (cycle stamps of the stage kernels' phases: frx_profile_phases; the forced form carries them too)
-    auto solo = [&]() { return frx::launch_eval_solo(p->dp, p->geo, x_dev, p->d_T.p, p->d_C.p, p->d_out20.p, f_dev, g_dev, st, p->tap_d, p->tap_flags, p->tap_res, p->tap_arrive, p->tap_flag, p->tap_round); };
-    if (solo_ok && p->eval_solo == 2) return solo();                          // (forced: tests and measurements at batch sizes the other forms would take)
-    if (backward && p->eval_fused && p->geo.solver == frx::SOLVER_KNOT_PCR && !p->tap_d && !p->dp.cand_active && (!p->dp.stamps || p->eval_fused_stamps)) {
+    switch (frx::eval_route(backward, p->tap.d != nullptr, p->dp.cand_active != nullptr, p->dp.stamps != nullptr, p->eval_fused != 0, p->eval_fused_stamps != 0, p->eval_solo, p->B,
+                            p->eval_solo_min_B, p->eval_solo_max_B, p->geo.lds_solo != 0, p->geo.solver == frx::SOLVER_KNOT_PCR)) {
+    case frx::EVAL_CLUSTER: {
         // the handle's constant arguments live in device memory, in TWO copies: the one uploaded at create (no stamps pointer) and the one a diagnostic uploads
         // before it switches the cycle stamps on.  A launch picks the copy with the kernel's instantiation (launch_eval_cluster) and never copies anything itself:
         // the caller may be capturing, and a graph captured before a diagnostic still points at arguments nobody has touched since.
@@ -309,13 +308,15 @@ int launch_eval(frx_problem *p, const double *x_dev, double *f_dev, double *g_de
         if (stamped && !p->d_ev_args_st.p) return (int)hipErrorInvalidValue;
         return frx::launch_eval_cluster(p->geo, p->B, stamped ? p->ev_args_st.data() : p->ev_args.data(), stamped ? p->d_ev_args_st.p : p->d_ev_args.p, x_dev, f_dev, g_dev, p->eval_fused_ticks, st, p->h_ev_status.p);
     }
-    // batches beyond the clusters' reach: one workgroup per candidate runs the three stage bodies back to back - plain evaluations AND the optimiser's rounds (same
-    // stage buffers, tap and skipped candidates as the three launches; bit-identical results)
-    if (solo_ok && p->eval_solo == 1 && p->B >= p->eval_solo_min_B && p->B <= p->eval_solo_max_B) return solo();
+    // batches beyond the clusters' reach (or the form forced, for tests and measurements): one workgroup per candidate runs the three stage bodies back to back - plain
+    // evaluations AND the optimiser's rounds (same stage buffers, tap and skipped candidates as the three launches; bit-identical results)
+    case frx::EVAL_SOLO: return frx::launch_eval_solo(p->dp, p->geo, x_dev, p->d_T.p, p->d_C.p, p->d_out20.p, f_dev, g_dev, st, p->tap);
+    case frx::EVAL_STAGES: break;
+    }
     int e = frx::launch_forward(p->dp, p->geo, x_dev, p->d_T.p, p->d_C.p, backward ? p->d_band.p : (double *)nullptr, st);
     if (e || !backward) return e;
     if ((e = frx::launch_penalty(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_out20.p, st))) return e;
-    return frx::launch_backward(p->dp, p->geo, x_dev, p->d_T.p, p->d_C.p, p->d_band.p, p->d_out20.p, f_dev, g_dev, st, p->tap_d, p->tap_flags, p->tap_res, p->tap_arrive, p->tap_flag, p->tap_round);
+    return frx::launch_backward(p->dp, p->geo, x_dev, p->d_T.p, p->d_C.p, p->d_band.p, p->d_out20.p, f_dev, g_dev, st, p->tap);
 }
 
 // The one-launch evaluation's sticky error word (a wait inside the launch expired: the f of the candidates concerned are NaN, so the word is only fetched when
@@ -469,15 +470,14 @@ int frx_problem_create(const frx_config *cfg, int device, int B, const int *coar
         if (const char *pw = std::getenv("FRX_PENALTY_WAVES")) { const int w = std::atoi(pw); if (w >= 1 && w <= 4) best_w = w; }
         //  W is chosen for lane utilisation, but the workgroup's LDS grows with it (ppg corridor blocks of Kmax + 1 records): step W down
         // until the block fits the CU - a corridor with many half-spaces runs on fewer waves instead of failing create
-        auto pen_lds = [&](int w) { const int ppg = (64 * w) / ge.lpp; return sizeof(double) * ((size_t)ppg * 19 + (size_t)ppg * (p->Kmax + 1) * 4 + (size_t)64 * w * 21); };
-        while (best_w > 1 && pen_lds(best_w) > (size_t)160 * 1024) best_w--;
+        while (best_w > 1 && frx::pen_wg_bytes((64 * best_w) / ge.lpp, p->Kmax, best_w, 21) > (size_t)160 * 1024) best_w--;
         ge.pen_w = best_w; ge.ppg = (64 * best_w) / ge.lpp;
     }
     ge.lds_fwd = sizeof(double) * ((size_t)6 * p->maxN * (FRX_BAND_W + 3) + p->maxN + p->maxCN);
     ge.lds_bwd = sizeof(double) * ((size_t)6 * p->maxN * (FRX_BAND_W + 6) + 2 * (size_t)p->maxN + p->maxCN);
-    ge.lds_pen = sizeof(double) * ((size_t)ge.ppg * 19 + (size_t)ge.ppg * (p->Kmax + 1) * 4 + (size_t)64 * ge.pen_w * 21);
+    ge.lds_pen = frx::pen_wg_bytes(ge.ppg, p->Kmax, ge.pen_w, 21);
     // large batches (four-wave workgroups), one sample per lane: the two-phase form of the integrator (k_penalty_lat2) - half the transpose buffer, four waves per SIMD
-    ge.lds_pen2 = (ge.pen_w == 4 && spp <= 64) ? sizeof(double) * ((size_t)ge.ppg * 19 + (size_t)ge.ppg * (p->Kmax + 1) * 4 + (size_t)64 * ge.pen_w * 11) : 0;
+    ge.lds_pen2 = (ge.pen_w == 4 && spp <= 64) ? frx::pen_wg_bytes(ge.ppg, p->Kmax, ge.pen_w, 11) : 0;
     ge.solver = frx::SOLVER_KNOT_PCR;
     ge.knot_threads = 64 * ((p->maxN + 63) / 64);
     {
@@ -936,19 +936,17 @@ int frx_debug_set_eval_solo(frx_problem *p, int mode) {
     return FRX_OK;
 }
 // Diagnostic (bench): which penalty kernel a stage launch of this handle takes - 0 = k_penalty (FRX_PENALTY_FORM=thr), 1 = k_penalty_lat, 2 = k_penalty_lat2 (four-wave
-// workgroups, one sample per lane: the large-batch form; FRX_PENALTY_TWOPHASE=0 keeps the one-phase launch).  Mirrors launch_penalty (frx_device.hip).
+// workgroups, one sample per lane: the large-batch form; FRX_PENALTY_TWOPHASE=0 keeps the one-phase launch).
 int frx_debug_penalty_kernel(const frx_problem *p) {
     if (!p) return -1;
-    const char *f = std::getenv("FRX_PENALTY_FORM");
-    if (f && f[0] != 'l') return 0;
-    const char *tp = std::getenv("FRX_PENALTY_TWOPHASE");
-    return (p->geo.lds_pen2 && !(tp && tp[0] == '0')) ? 2 : 1;
+    const char *f = std::getenv("FRX_PENALTY_FORM"), *tp = std::getenv("FRX_PENALTY_TWOPHASE");
+    return frx::penalty_form_code(frx::penalty_form(p->geo.lds_pen2 != 0, p->geo.lpp, !f ? 0 : f[0] == 'l' ? 1 : 2, tp ? tp[0] : 0));
 }
 int frx_debug_eval_solo(const frx_problem *p) {
-    if (!p || !p->geo.lds_solo || p->geo.solver != frx::SOLVER_KNOT_PCR) return 0;
-    if (!(p->eval_solo == 2 || (p->eval_solo == 1 && p->B >= p->eval_solo_min_B && p->B <= p->eval_solo_max_B))) return 0;
-    if (p->eval_fused && p->eval_solo != 2) return 0;                          // (a plain evaluation of a batch the chip holds as clusters takes that form first)
-    return frx::eval_solo_blocks_per_cu(p->geo);
+    if (!p) return 0;
+    const frx::EvalRoute plain = frx::eval_route(true, false, false, false, p->eval_fused != 0, p->eval_fused_stamps != 0, p->eval_solo, p->B, p->eval_solo_min_B,
+                                                 p->eval_solo_max_B, p->geo.lds_solo != 0, p->geo.solver == frx::SOLVER_KNOT_PCR);
+    return plain == frx::EVAL_SOLO ? frx::eval_solo_blocks_per_cu(p->geo) : 0;
 }
 // Diagnostic (bench): average duration of one evaluation at x in the form frx_objective_eval_device takes, HIP events around `reps` back-to-back evaluations.
 int frx_eval_launch_time(frx_problem *p, const double *x, int reps, double *out_us) {
@@ -1384,13 +1382,13 @@ static int optimize_device_vectors(frx_problem *p, const frx_lbfgs_params &pm, d
     // with the knot/PCR kernels the reductions the line search needs ride on k_backward_knot (LineSearchTap); the banded-LU
     // kernels keep the separate k_lbfgs_post
     const bool fused_post = p->geo.solver == frx::SOLVER_KNOT_PCR;
-    struct TapGuard { frx_problem *q; ~TapGuard() { q->tap_d = nullptr; q->tap_flags = nullptr; q->tap_res = nullptr; q->dp.cand_active = nullptr; q->dp.piece_active = nullptr; q->tap_arrive = nullptr; q->tap_flag = nullptr; } } tap_guard{p};
+    struct TapGuard { frx_problem *q; ~TapGuard() { q->tap = frx::TapLaunch(); q->dp.cand_active = nullptr; q->dp.piece_active = nullptr; } } tap_guard{p};
     const char *mb_env = std::getenv("FRX_MAILBOX");
     const bool mailbox = fused_post && !(mb_env && mb_env[0] == '0');
     if (fused_post) {
         if (!p->d_flags.p && (e = p->d_flags.alloc(B)) != hipSuccess) return fail(FRX_ERR_ALLOC, hipGetErrorString(e));
         dv.dflags = p->d_flags.p;
-        p->tap_d = p->d_dir.p; p->tap_flags = p->d_flags.p; p->tap_res = p->h_res.p;
+        p->tap.d = p->d_dir.p; p->tap.flags = p->d_flags.p; p->tap.res = p->h_res.p;
         // large batches: the objective kernels skip candidates that are not being evaluated this round (finished ones above all)
         const char *sk = std::getenv("FRX_SKIP_INACTIVE");
         if (sk ? sk[0] != '0' : B > 64) {
@@ -1404,7 +1402,7 @@ static int optimize_device_vectors(frx_problem *p, const frx_lbfgs_params &pm, d
         if (!p->d_arrive.p && ((e = p->d_arrive.alloc(1)) != hipSuccess || (e = p->h_flag.alloc(1)) != hipSuccess)) return fail(FRX_ERR_ALLOC, hipGetErrorString(e));
         HIP_TRY(hipMemsetAsync(p->d_arrive.p, 0, sizeof(unsigned), p->stream));
         p->h_flag.p[0] = 0;
-        p->tap_arrive = p->d_arrive.p; p->tap_flag = p->h_flag.p; p->tap_round = 0;
+        p->tap.arrive = p->d_arrive.p; p->tap.flag = p->h_flag.p; p->tap.round = 0;
     }
     // completion of a round: the last workgroup of k_backward_knot posts the round number in mapped memory (LineSearchTap).
     // The spin is bounded: a stream that drains without the post (arrival counter out of step, e.g. a launch that never
@@ -1413,15 +1411,15 @@ static int optimize_device_vectors(frx_problem *p, const frx_lbfgs_params &pm, d
         if (!mailbox || !evaluated) return wait_stream();
         const auto tw = clk::now();
         for (unsigned spins = 1;; spins++) {
-            if (*(volatile unsigned *)p->h_flag.p == p->tap_round) return FRX_OK;
+            if (*(volatile unsigned *)p->h_flag.p == p->tap.round) return FRX_OK;
             if ((spins & 0x3FFF) == 0) {
                 const hipError_t q = hipStreamQuery(p->stream);
                 if (q == hipSuccess) {
-                    if (*(volatile unsigned *)p->h_flag.p == p->tap_round) return FRX_OK;
-                    return fail(FRX_ERR_TIMEOUT, "round " + std::to_string(p->tap_round) + ": the stream drained but completion was never posted (arrival counter out of step)");
+                    if (*(volatile unsigned *)p->h_flag.p == p->tap.round) return FRX_OK;
+                    return fail(FRX_ERR_TIMEOUT, "round " + std::to_string(p->tap.round) + ": the stream drained but completion was never posted (arrival counter out of step)");
                 }
                 if (q != hipErrorNotReady) return fail(FRX_ERR_HIP, std::string("device round failed: ") + hipGetErrorString(q));
-                if (ms_since(tw) > round_timeout_ms) return fail(FRX_ERR_TIMEOUT, "round " + std::to_string(p->tap_round) + " did not complete within FRX_ROUND_TIMEOUT_MS");
+                if (ms_since(tw) > round_timeout_ms) return fail(FRX_ERR_TIMEOUT, "round " + std::to_string(p->tap.round) + " did not complete within FRX_ROUND_TIMEOUT_MS");
             }
             __builtin_ia32_pause();
         }
@@ -1447,7 +1445,7 @@ static int optimize_device_vectors(frx_problem *p, const frx_lbfgs_params &pm, d
         auto td = clk::now();
         HIP_TRY((hipError_t)frx::launch_lbfgs_pre(dv, p->h_cmd.p, p->h_res.p, p->stream));
         if (any_eval) {
-            if (mailbox) p->tap_round++;
+            if (mailbox) p->tap.round++;
             if (rounds == drop_round) HIP_TRY((hipError_t)launch_eval(p, p->d_x.p, p->d_f.p, p->d_g.p, p->stream, false));
             else HIP_TRY((hipError_t)launch_eval(p, p->d_x.p, p->d_f.p, p->d_g.p, p->stream, true));
             if (!fused_post) HIP_TRY((hipError_t)frx::launch_lbfgs_post(dv, p->d_f.p, p->h_cmd.p, p->h_res.p, p->stream));

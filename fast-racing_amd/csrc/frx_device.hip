@@ -8,39 +8,47 @@
 #include <mutex>
 
 #include "frx_kernels.hpp"
+#include "frx_launch_forms.hpp"
 #include "frx_lbfgs_kernels.hpp"
 
 namespace frx {
 
-// The dynamic-LDS limit of a kernel is a property of the FUNCTION, not of a handle: handles of different geometry live side by side (tests, a planner with several
-// corridors), so the limit only ever grows - a handle created later with a smaller need must not lower it under an older handle's launches.
-static int raise_lds_limit(const void *fn, size_t bytes, size_t &held) {
-    if (bytes <= held) return 0;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) held = bytes;
-    return (int)e;
-}
-int launch_set_limits(const LaunchGeom &g) {
+// (frx_device.hpp) one table for every kernel of the library (LdsLimits, frx_launch_forms.hpp: grow-only per device and function), under one mutex
+int raise_lds_limit(const void *fn, size_t bytes) {
     static std::mutex mu;
-    static size_t held_all[64][13] = {};                             // per device: a function's attributes belong to the device that is current
+    static LdsLimits limits;
+    if (!bytes) return 0;
     std::lock_guard<std::mutex> lock(mu);
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-    size_t *held = held_all[dev];
-    int e;
-    if ((e = raise_lds_limit((const void *)k_forward, g.lds_fwd, held[0]))) return e;
-    if ((e = raise_lds_limit((const void *)k_backward, g.lds_bwd, held[1]))) return e;
-    if ((e = raise_lds_limit((const void *)k_penalty, g.lds_pen, held[2]))) return e;
-    if ((e = raise_lds_limit((const void *)k_penalty_lat, g.lds_pen, held[3]))) return e;
-    if (g.lds_pen2) {                                                  // the instantiation launch_penalty takes for this geometry
-        const void *fn = g.lpp == 17 ? (const void *)k_penalty_lat2<17> : g.lpp == 49 ? (const void *)k_penalty_lat2<49> : (const void *)k_penalty_lat2<0>;
-        if ((e = raise_lds_limit(fn, g.lds_pen2, held[g.lpp == 17 ? 4 : g.lpp == 49 ? 10 : 11]))) return e;
-        if ((e = raise_lds_limit((const void *)k_penalty_lat2_r5, g.lds_pen2, held[12]))) return e;
+    if (hipGetDevice(&dev) != hipSuccess) return (int)hipErrorInvalidDevice;
+    return limits.raise(dev, fn, bytes, [](const void *f, size_t n) { return (int)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n); });
+}
+// the stage kernel of the penalty integral by its form (frx_launch_forms.hpp): f(kernel)
+template <class F> static int with_penalty_kernel(PenaltyForm form, F &&f) {
+    switch (form) {
+    case PEN_THR: return f(k_penalty);
+    case PEN_LAT: return f(k_penalty_lat);
+    case PEN_LAT2_17: return f(k_penalty_lat2<17>);
+    case PEN_LAT2_49: return f(k_penalty_lat2<49>);
+    case PEN_LAT2_0: return f(k_penalty_lat2<0>);
+    case PEN_LAT2_R5: return f(k_penalty_lat2_r5);
     }
-    if ((e = raise_lds_limit((const void *)k_forward_knot, g.lds_kfwd, held[5]))) return e;
-    if ((e = raise_lds_limit((const void *)k_backward_knot, g.lds_kbwd, held[6]))) return e;
-    if ((e = raise_lds_limit((const void *)k_forward_knot64, g.lds_kfwd, held[7]))) return e;
-    if ((e = raise_lds_limit((const void *)k_backward_knot64, g.lds_kbwd, held[8]))) return e;
+    return (int)hipErrorInvalidValue;
+}
+int launch_set_limits(const LaunchGeom &g) {
+    int e;
+    if ((e = raise_lds_limit((const void *)k_forward, g.lds_fwd))) return e;
+    if ((e = raise_lds_limit((const void *)k_backward, g.lds_bwd))) return e;
+    // every penalty form launch_penalty can take for this geometry: the one-phase forms, and with lds_pen2 the two-phase instantiation of its lpp and the round-5 form
+    for (PenaltyForm form : {PEN_THR, PEN_LAT, penalty_lat2_form(g.lpp), PEN_LAT2_R5}) {
+        const size_t bytes = form == PEN_THR || form == PEN_LAT ? g.lds_pen : g.lds_pen2;
+        if (!bytes) continue;
+        if ((e = with_penalty_kernel(form, [&](auto kernel) { return raise_lds_limit((const void *)kernel, bytes); }))) return e;
+    }
+    if ((e = raise_lds_limit((const void *)k_forward_knot, g.lds_kfwd))) return e;
+    if ((e = raise_lds_limit((const void *)k_backward_knot, g.lds_kbwd))) return e;
+    if ((e = raise_lds_limit((const void *)k_forward_knot64, g.lds_kfwd))) return e;
+    if ((e = raise_lds_limit((const void *)k_backward_knot64, g.lds_kbwd))) return e;
     if (g.ev_G && (e = eval_cluster_raise_limit(g.lds_ev))) return e;                   // (frx_device_eval.hip: the kernel lives in that translation unit)
     return 0;
 }
@@ -56,31 +64,23 @@ int launch_penalty(const DevProblem &dp, const LaunchGeom &g, const double *T, c
     // default: the latency form (148 VGPRs, 3 waves per SIMD, phases interleaved by the scheduler) - measured faster at the headline batch
     // (4.97 vs 5.23 us) AND at 1024 candidates (39.8 vs 42.3 us) than the throughput form (126 VGPRs, 4 waves per SIMD); FRX_PENALTY_FORM=thr selects that one
     static const int forced = [] { const char *e = std::getenv("FRX_PENALTY_FORM"); return !e ? 0 : e[0] == 'l' ? 1 : 2; }();
-    const bool lat = forced != 2;
-    const int nwg = (dp.P + g.ppg - 1) / g.ppg;
     const char *tp_env = std::getenv("FRX_PENALTY_TWOPHASE");           // (read per launch: the test toggles it inside one process)
-    const bool two_phase = !(tp_env && tp_env[0] == '0');
-    if (lat && g.lds_pen2 && tp_env && tp_env[0] == '5') hipLaunchKernelGGL(k_penalty_lat2_r5, dim3(nwg), dim3(256), g.lds_pen2, (hipStream_t)stream, dp, T, C, out20, g.lpp, g.ppg, g.Kmax);   // (A/B: the round-5 form)
-    else if (lat && two_phase && g.lds_pen2) {                         // (pen_w == 4: 256 threads; the two boundary resolutions kappa = 16 / 48 have instantiations of their own)
-        if (g.lpp == 17) hipLaunchKernelGGL(k_penalty_lat2<17>, dim3(nwg), dim3(256), g.lds_pen2, (hipStream_t)stream, dp, T, C, out20, g.lpp, g.ppg, g.Kmax);
-        else if (g.lpp == 49) hipLaunchKernelGGL(k_penalty_lat2<49>, dim3(nwg), dim3(256), g.lds_pen2, (hipStream_t)stream, dp, T, C, out20, g.lpp, g.ppg, g.Kmax);
-        else hipLaunchKernelGGL(k_penalty_lat2<0>, dim3(nwg), dim3(256), g.lds_pen2, (hipStream_t)stream, dp, T, C, out20, g.lpp, g.ppg, g.Kmax);
-    }
-    else if (lat) hipLaunchKernelGGL(k_penalty_lat, dim3(nwg), dim3(64 * g.pen_w), g.lds_pen, (hipStream_t)stream, dp, T, C, out20, g.lpp, g.ppg, g.Kmax);
-    else hipLaunchKernelGGL(k_penalty, dim3(nwg), dim3(64 * g.pen_w), g.lds_pen, (hipStream_t)stream, dp, T, C, out20, g.lpp, g.ppg, g.Kmax);
-    return (int)hipGetLastError();
+    const PenaltyForm form = penalty_form(g.lds_pen2 != 0, g.lpp, forced, tp_env ? tp_env[0] : 0);
+    const bool one_phase = form == PEN_THR || form == PEN_LAT;         // (the two-phase forms: pen_w == 4, 256 threads)
+    return with_penalty_kernel(form, [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((dp.P + g.ppg - 1) / g.ppg), dim3(one_phase ? 64 * g.pen_w : 256), one_phase ? g.lds_pen : g.lds_pen2, (hipStream_t)stream, dp, T, C, out20, g.lpp, g.ppg, g.Kmax);
+        return (int)hipGetLastError();
+    });
 }
 int launch_backward(const DevProblem &dp, const LaunchGeom &g, const double *x, const double *T, const double *C,
-                    const double *band, const double *out20, double *f, double *grad, void *stream, const double *tap_d, const int *tap_flags,
-                    void *tap_res, unsigned *tap_arrive, volatile unsigned *tap_flag, unsigned tap_round) {
+                    const double *band, const double *out20, double *f, double *grad, void *stream, const TapLaunch &t) {
+    const LineSearchTap tap{t.d, t.flags, (DvResult *)t.res, t.arrive, t.flag, t.round};
     if (g.solver == SOLVER_KNOT_PCR && g.knot_threads == 64)
         hipLaunchKernelGGL(k_backward_knot64, dim3(dp.B), dim3(256), g.lds_kbwd, (hipStream_t)stream, dp, x, T, C, out20, f,
-                           grad, g.maxCN, g.maxXb, g.maxVb, g.pcrw, g.pcr_steps,
-                           LineSearchTap{tap_d, tap_flags, (DvResult *)tap_res, tap_arrive, tap_flag, tap_round});
+                           grad, g.maxCN, g.maxXb, g.maxVb, g.pcrw, g.pcr_steps, tap);
     else if (g.solver == SOLVER_KNOT_PCR)
         hipLaunchKernelGGL(k_backward_knot, dim3(dp.B), dim3(256), g.lds_kbwd, (hipStream_t)stream, dp, x, T, C, out20, f,
-                           grad, g.maxCN, g.maxXb, g.maxVb, g.knot_threads, g.pcrw, g.pcr_steps,
-                           LineSearchTap{tap_d, tap_flags, (DvResult *)tap_res, tap_arrive, tap_flag, tap_round});
+                           grad, g.maxCN, g.maxXb, g.maxVb, g.knot_threads, g.pcrw, g.pcr_steps, tap);
     else
         hipLaunchKernelGGL(k_backward, dim3(dp.B), dim3(64), g.lds_bwd, (hipStream_t)stream, dp, x, T, C, band, out20, f, grad, g.maxN,
                            g.maxCN);

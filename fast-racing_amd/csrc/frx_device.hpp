@@ -4,6 +4,7 @@
 // arithmetic) while the kernels keep hipcc's device code generation.
 #pragma once
 #include <cstddef>
+#include <cstdlib>
 
 #include "frx_math.hpp"
 
@@ -56,14 +57,26 @@ struct LaunchGeom {
     size_t lds_solo = 0;                   // one workgroup per candidate, one launch per evaluation (frx_solo_kernel.hpp): dynamic LDS, 0 = not applicable
 };
 
+// the launchers' A/B switches: is the environment variable set, and does it begin with '0' / with ch?
+inline bool env_is(const char *name, char ch) { const char *e = std::getenv(name); return e && e[0] == ch; }
+inline bool env_off(const char *name) { return env_is(name, '0'); }
+
+// The line-search tap of the adjoint kernels (LineSearchTap, frx_kernels.hpp) as the host passes it: all null = a plain evaluation.
+struct TapLaunch {
+    const double *d = nullptr; const int *flags = nullptr; void *res = nullptr;
+    unsigned *arrive = nullptr; volatile unsigned *flag = nullptr; unsigned round = 0;
+};
+
 // all return a hipError_t value as int (0 = hipSuccess); stream is a hipStream_t
+// The dynamic-LDS limit of a kernel is a property of the FUNCTION, not of a handle or a launch: handles of different geometry live side by side (tests, a planner
+// with several corridors) and launches of different need may be in flight together, so the limit only ever grows, per device - every launcher raises it here.  A need
+// already held is no HIP call at all (a later launch may be inside a stream capture).
+int raise_lds_limit(const void *fn, size_t bytes);
 int launch_set_limits(const LaunchGeom &g);
 int launch_forward(const DevProblem &dp, const LaunchGeom &g, const double *x, double *T, double *C, double *band, void *stream);
 int launch_penalty(const DevProblem &dp, const LaunchGeom &g, const double *T, const double *C, double *out20, void *stream);
 int launch_backward(const DevProblem &dp, const LaunchGeom &g, const double *x, const double *T, const double *C,
-                    const double *band, const double *out20, double *f, double *grad, void *stream,
-                    const double *tap_d = nullptr, const int *tap_flags = nullptr, void *tap_res = nullptr,
-                    unsigned *tap_arrive = nullptr, volatile unsigned *tap_flag = nullptr, unsigned tap_round = 0);
+                    const double *band, const double *out20, double *f, double *grad, void *stream, const TapLaunch &tap = TapLaunch());
 
 
 // One launch per evaluation (frx_eval_kernel.hpp): clusters of g.ev_G workgroups, one per candidate.  ll: [P][40 + 38] granule words (penalty partials, then (C, T)), words: [64 B + 1] (the last one: status), both
@@ -87,8 +100,7 @@ int eval_solo_geometry(LaunchGeom &g, int samples_per_piece);     // fills lds_s
 int eval_solo_raise_limit(const LaunchGeom &g);
 int eval_solo_blocks_per_cu(const LaunchGeom &g);                 // workgroups of the kernel a CU holds (occupancy query of the runtime; 0 on error)
 int launch_eval_solo(const DevProblem &dp, const LaunchGeom &g, const double *x, double *T, double *C, double *out20, double *f, double *grad, void *stream,
-                     const double *tap_d = nullptr, const int *tap_flags = nullptr, void *tap_res = nullptr,
-                     unsigned *tap_arrive = nullptr, volatile unsigned *tap_flag = nullptr, unsigned tap_round = 0);
+                     const TapLaunch &tap = TapLaunch());
 
 // ---- dense feasibility check of a batch of trajectories (frx_check_kernel.hpp) ----
 // lanes per piece (a power of two) and pieces per wave for `intervals` + 1 samples per piece; 0 when a corridor block of Kmax half-spaces does not fit a wave's LDS

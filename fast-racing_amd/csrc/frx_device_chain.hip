@@ -2,8 +2,6 @@
 // (k_corridor_chain, frx_chain_kernel.hpp; both run the same dilate_cell) and their launchers.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
 #include "frx_chain_kernel.hpp"
 #include "frx_device.hpp"
 
@@ -16,8 +14,7 @@ int launch_dilate(const DilateLaunch &d, void *stream) {
     a.S = d.S; a.n_obs = d.n_obs; a.cap_planes = d.cap_planes; a.pcap = d.pcap;
     a.n_planes = d.n_planes; a.h_rec = d.h_rec; a.ell_C = d.ell_C; a.ell_d = d.ell_d;
     const size_t lds = dilate_lds_bytes(d.pcap);
-    hipError_t e = hipFuncSetAttribute((const void *)k_dilate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+    if (const int e = raise_lds_limit((const void *)k_dilate, lds)) return e;
     hipLaunchKernelGGL(k_dilate, dim3(d.S), dim3(256), lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
@@ -43,20 +40,9 @@ int launch_chain(const ChainLaunch &c, void *stream) {
     a.map_height = c.map_height; a.max_seg = c.max_seg;
     a.n_paths = c.n_paths; a.n_obs = c.n_obs; a.cap_polys = c.cap_polys; a.cap_planes = c.cap_planes; a.pcap = c.pcap;
     a.h_slot = c.h_slot; a.cell_planes = c.cell_planes; a.n_polys = c.n_polys; a.status = c.status;
-    // The function's limit is raised to the whole LDS once per device, never to one launch's need: launches of different cap_planes may be in flight side by
-    // side.  Later calls - a capture among them - are the launch alone.
-    {
-        static std::mutex mu;
-        static bool raised[64] = {};
-        std::lock_guard<std::mutex> lock(mu);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-        if (!raised[dev]) {
-            const hipError_t attr = hipFuncSetAttribute((const void *)k_corridor_chain, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (attr != hipSuccess) return (int)attr;
-            raised[dev] = true;
-        }
-    }
+    // The function's limit is raised to the whole LDS, never to one launch's need: launches of different cap_planes may be in flight side by side.  Later calls -
+    // a capture among them - are the launch alone.
+    if (const int e = raise_lds_limit((const void *)k_corridor_chain, (size_t)160 * 1024)) return e;
     hipLaunchKernelGGL(k_corridor_chain, dim3(c.n_paths), dim3(256), lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

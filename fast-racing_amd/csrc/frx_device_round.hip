@@ -3,10 +3,10 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 
 #define FRX_KERNEL_LINKAGE static          // the stage kernels of frx_kernels.hpp belong to frx_device.hip: here only their bodies are used
 #include "frx_round_kernel.hpp"
+#include "frx_launch_forms.hpp"
 
 namespace frx {
 
@@ -17,7 +17,7 @@ static int round_ct_doubles(const LaunchGeom &g) {
     return ((g.maxN * 19 + 1) & ~1) + 5 * xpad + vpad + ((pw + 1) & ~1) + 4 * g.knot_threads;
 }
 static int round_eval_doubles(const LaunchGeom &g) {
-    const size_t pen = (size_t)g.ppw * 19 + (size_t)g.ppw * (g.Kmax + 1) * 4 + 64 * 21;              // doubles per wave (LaunchGeom::lds_pen)
+    const size_t pen = pen_wave_doubles(g.ppw, g.Kmax);
     size_t e = std::max(g.lds_kfwd, g.lds_kbwd) / sizeof(double) + 2;
     // <= 64 pieces: the evaluation bodies find x, polytopes, direction and multipliers in the resident operands, so their scratch ends
     // behind the knot arrays (rows | knot arrays | Tf, gT | gCo | cross-wave partials)
@@ -30,13 +30,13 @@ size_t round_lds_bytes(const LaunchGeom &g, int m, int E) {
     if ((E != ROUND_E && E != ROUND_E_SMALL) || m < 1 || m > 128 || g.solver != SOLVER_KNOT_PCR) return 0;
     return sizeof(double) * (size_t)round_lds(m, 2 * E, round_eval_doubles(g)).total;
 }
-static bool n64_class(const LaunchGeom &g) { static const bool generic = [] { const char *e = std::getenv("FRX_RESIDENT_NR"); return e && e[0] == '0'; }(); return g.knot_threads == 64 && !generic; }   // FRX_RESIDENT_NR=0: the generic instantiation (A/B)
+static bool n64_class(const LaunchGeom &g) { static const bool generic = env_off("FRX_RESIDENT_NR"); return g.knot_threads == 64 && !generic; }   // FRX_RESIDENT_NR=0: the generic instantiation (A/B)
 int launch_round(const DevProblem &dp, const LaunchGeom &g, const RoundLaunch &r, void *stream) {
     if (r.E != ROUND_E && r.E != ROUND_E_SMALL) return (int)hipErrorInvalidValue;
     RoundArgs a;
     a.dp = dp;
     a.maxCN = g.maxCN; a.maxXb = g.maxXb; a.maxVb = g.maxVb; a.nrow = g.knot_threads; a.nsteps = g.pcr_steps; a.lpp = g.lpp; a.ppw = g.ppw; a.Kmax = g.Kmax;
-    a.pen_lds = g.ppw * 19 + g.ppw * (g.Kmax + 1) * 4 + 64 * 21;
+    a.pen_lds = pen_wave_doubles(g.ppw, g.Kmax);
     a.x = r.x; a.g = r.g; a.xp = r.xp; a.gp = r.gp; a.d = r.d; a.f = r.f; a.T = r.T; a.C = r.C; a.out20 = r.out20; a.pcrw = g.pcrw;
     a.out20ll = g.knot_threads == 64 ? r.out20ll : nullptr;                                                      // (only the <= 64-piece adjoint polls granules)
     a.pubsyg = r.pubsyg; a.part = r.part; a.upub = r.upub; a.dpub = r.dpub; a.dbg = r.dbg; a.dbg_cap = r.dbg_cap; a.dbg_cands = r.dbg_cands;
@@ -59,16 +59,14 @@ int launch_round(const DevProblem &dp, const LaunchGeom &g, const RoundLaunch &r
     const bool n64 = n64_class(g);
     const dim3 grid(8 * r.G * ((r.S + 7) / 8)), block(256);
     auto go = [&](auto kernel) -> int {
-        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
+        if (const int e = raise_lds_limit((const void *)kernel, lds)) return e;
         hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)stream, a);
         return (int)hipGetLastError();
     };
     // the arguments by POINTER (k_round<.., ARGP>): copied into the handle's device buffer in front of the launch, on its stream (pageable source: staged before the call returns)
     [[maybe_unused]] auto go_ptr = [&](auto kernel) -> int {
-        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        if ((e = hipMemcpyAsync(r.args_dev, &a, sizeof(a), hipMemcpyHostToDevice, (hipStream_t)stream)) != hipSuccess) return (int)e;
+        if (const int e = raise_lds_limit((const void *)kernel, lds)) return e;
+        if (const hipError_t e = hipMemcpyAsync(r.args_dev, &a, sizeof(a), hipMemcpyHostToDevice, (hipStream_t)stream)) return (int)e;
         hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)stream, (const RoundArgs *)r.args_dev);
         return (int)hipGetLastError();
     };
@@ -78,7 +76,7 @@ int launch_round(const DevProblem &dp, const LaunchGeom &g, const RoundLaunch &r
     // launch instead of once per round, gains 0.23 us of 17.4: frx_device_eval.hip.)  The by-pointer instantiations are therefore only built with
     // -DFRX_ROUND_ARGPTR_BUILD (and then taken with FRX_ROUND_ARGPTR=1); the default is by value.
 #ifdef FRX_ROUND_ARGPTR_BUILD
-    static const bool argp = [] { const char *e = std::getenv("FRX_ROUND_ARGPTR"); return e && e[0] == '1'; }();
+    static const bool argp = env_is("FRX_ROUND_ARGPTR", '1');
 #endif
     a.rs.cand = r.rs_cand; a.rs.f_last = r.rs_f; a.rs.S = r.rs_S; a.rs.Y = r.rs_Y; a.rs.hs = r.rs_hs; a.rs.newest = r.rs_newest; a.rs.bound = r.rs_bound; a.rs.rinv = r.rs_rinv; a.rs.yy = r.rs_yy; a.rs.vd = r.rs_vd;
     if (r.rs_cand) {                                                   // take-over instantiation: <= 64 pieces, no profile

@@ -1,0 +1,90 @@
+// Which kernel form a launch takes, as pure functions of integers and bools, and the grow-only table of the kernels' LDS limits: shared by the launchers
+// (frx_device*.hip), the diagnostics that report a form (frx_api.cpp) and the CPU-side enumeration of every decision (tests/test_launch_forms_cpu.py).  Plain C++,
+// no HIP, no environment: the callers read the switches and make the HIP calls.
+#pragma once
+#include <cstddef>
+#include <map>
+#include <utility>
+
+namespace frx {
+
+// ---- LDS of the penalty integrator: piece records | corridor blocks of Kmax + 1 records | the lanes' partials ----
+// doubles per WAVE (penalty_body with a 64-lane group: the resident round kernel, the one-launch evaluation)
+constexpr int pen_wave_doubles(int ppw, int Kmax) { return ppw * 19 + ppw * (Kmax + 1) * 4 + 64 * 21; }
+// bytes per WORKGROUP of `waves` waves (stage kernels): 21 doubles per lane in the one-phase forms, 11 in the two-phase ones
+constexpr size_t pen_wg_bytes(int ppg, int Kmax, int waves, int doubles_per_lane) {
+    return sizeof(double) * ((size_t)ppg * 19 + (size_t)ppg * (Kmax + 1) * 4 + (size_t)64 * waves * doubles_per_lane);
+}
+
+// ---- the dynamic-LDS limit of every kernel (raise_lds_limit, frx_device.hip) ----
+// What is held per (device, function), and the rule: the limit only grows.  set(fn, bytes) makes the call (0 = done) and is only asked for a need above what is
+// held; a need already held, or none at all, is no call.  A failed call leaves the table as it was.
+class LdsLimits {
+    std::map<std::pair<int, const void *>, size_t> held_;
+public:
+    template <class Set> int raise(int dev, const void *fn, size_t bytes, Set &&set) {
+        if (!bytes) return 0;
+        size_t &held = held_[{dev, fn}];
+        if (bytes <= held) return 0;
+        const int e = set(fn, bytes);
+        if (!e) held = bytes;
+        return e;
+    }
+};
+
+// ---- k_eval_cluster<ARGP, ET, TAIL, HO, CH, GEO> ----
+struct EvalClusterForm { bool argp, et, tail, ho, ch, geo; };           // geo: the geometry class EvalGeomK16
+inline bool operator==(const EvalClusterForm &a, const EvalClusterForm &b) {
+    return a.argp == b.argp && a.et == b.et && a.tail == b.tail && a.ho == b.ho && a.ch == b.ch && a.geo == b.geo;
+}
+// the six FRX_EVAL_* switches as set (true unless the variable begins with '0'); a switch only counts with the ones in front of it at their defaults:
+struct EvalSwitches {
+    bool argptr, early_t, tail, handoff, chain, geom;
+    constexpr bool handoff_on() const { return handoff && argptr && tail; }
+    constexpr bool chain_on() const { return chain && handoff_on(); }
+    constexpr bool geom_on() const { return geom && handoff_on() && early_t; }
+};
+// The form a launch takes.  geom_class: the handle has the one-launch form and its geometry equals the class's integers; stamped: the argument block carries the
+// stamps pointer (a diagnostic's evaluation - the production chain has no stamp code).  FRX_EVAL_TAIL=0 only shows with the argument pointer and early durations.
+// Returns false when the form takes its arguments by pointer and there is no device block.
+inline bool eval_cluster_form(const EvalSwitches &s, bool geom_class, bool stamped, bool have_dev_args, EvalClusterForm &f) {
+    const bool chained = s.chain_on() && !stamped;
+    if (s.geom_on() && geom_class) f = {true, true, true, true, chained, true};
+    else if (s.handoff_on()) f = {true, s.early_t, true, true, chained, false};
+    else if (s.argptr) f = {true, s.early_t, !(s.early_t && !s.tail), false, false, false};
+    else f = {false, s.early_t, true, false, false, false};
+    return !f.argp || have_dev_args;
+}
+// The forms whose dynamic-LDS limit a process raises: every form eval_cluster_form can give under these switches.  Returns their number: at most 4, one per
+// value of (geom_class, stamped) - an input added to eval_cluster_form is one more loop here and doubles the bound.
+inline int eval_cluster_raised_forms(const EvalSwitches &s, EvalClusterForm out[4]) {
+    int n = 0;
+    for (int geom_class = 0; geom_class <= (s.geom_on() ? 1 : 0); geom_class++)
+        for (int stamped = 0; stamped <= (s.chain_on() ? 1 : 0); stamped++) (void)eval_cluster_form(s, geom_class, stamped, true, out[n++]);
+    return n;
+}
+
+// ---- the stage launch of the penalty integral ----
+enum PenaltyForm { PEN_THR, PEN_LAT, PEN_LAT2_17, PEN_LAT2_49, PEN_LAT2_0, PEN_LAT2_R5 };
+// the two-phase instantiation of a geometry: the two boundary resolutions kappa = 16 / 48 have their own
+constexpr PenaltyForm penalty_lat2_form(int lpp) { return lpp == 17 ? PEN_LAT2_17 : lpp == 49 ? PEN_LAT2_49 : PEN_LAT2_0; }
+// forced: FRX_PENALTY_FORM unset 0, 'l..' 1, anything else 2 (the throughput form); twophase_char: first character of FRX_PENALTY_TWOPHASE, 0 when unset
+// ('0': the one-phase launch, '5': the round-5 form, A/B)
+constexpr PenaltyForm penalty_form(bool lds_pen2, int lpp, int forced, char twophase_char) {
+    return forced == 2 ? PEN_THR : !lds_pen2 || twophase_char == '0' ? PEN_LAT : twophase_char == '5' ? PEN_LAT2_R5 : penalty_lat2_form(lpp);
+}
+constexpr int penalty_form_code(PenaltyForm f) { return f == PEN_THR ? 0 : f == PEN_LAT ? 1 : 2; }   // (frx_debug_penalty_kernel)
+
+// ---- the route of an evaluation ----
+enum EvalRoute { EVAL_CLUSTER, EVAL_SOLO, EVAL_STAGES };
+// A plain evaluation of a batch the chip holds at once: ONE launch of clusters; batches beyond their reach (and the optimiser's rounds there): one workgroup per
+// candidate; else the three stage kernels.  eval_solo: 0 never, 1 inside [solo_min_B, solo_max_B], 2 forced (in front of the clusters, and with the cycle stamps).
+constexpr EvalRoute eval_route(bool backward, bool tap, bool cand_active, bool stamps, bool eval_fused, bool eval_fused_stamps, int eval_solo, int B, int solo_min_B,
+                               int solo_max_B, bool lds_solo, bool knot_solver) {
+    const bool solo_ok = backward && lds_solo && knot_solver && (!stamps || eval_solo == 2);
+    return solo_ok && eval_solo == 2 ? EVAL_SOLO
+         : backward && eval_fused && knot_solver && !tap && !cand_active && (!stamps || eval_fused_stamps) ? EVAL_CLUSTER
+         : solo_ok && eval_solo == 1 && B >= solo_min_B && B <= solo_max_B ? EVAL_SOLO : EVAL_STAGES;
+}
+
+} // namespace frx

@@ -269,3 +269,44 @@ extern "C" void hostcheck_solo_lds(int maxN, int maxXb, int maxVb, int maxCN, in
     out8[0] = L.ctl; out8[1] = L.xs; out8[2] = L.pw; out8[3] = L.wq; out8[4] = L.vs; out8[5] = L.ev; out8[6] = L.total;
     out8[7] = (ppg < maxN ? ppg : maxN) * (Kmax + 1) * 4 + 256 * frx::SOLO_QS + 2;
 }
+
+// ---- which kernel form a launch takes (fast-racing_amd/csrc/frx_launch_forms.hpp): the launchers' decisions as integers, for tests/test_launch_forms_cpu.py ----
+#include "../../fast-racing_amd/csrc/frx_launch_forms.hpp"
+static frx::EvalSwitches hostcheck_switches(const int *sw6) { return {sw6[0] != 0, sw6[1] != 0, sw6[2] != 0, sw6[3] != 0, sw6[4] != 0, sw6[5] != 0}; }
+static void hostcheck_form_out(const frx::EvalClusterForm &f, int *out6) { out6[0] = f.argp; out6[1] = f.et; out6[2] = f.tail; out6[3] = f.ho; out6[4] = f.ch; out6[5] = f.geo; }
+// sw6: FRX_EVAL_ARGPTR, _EARLY_T, _TAIL, _HANDOFF, _CHAIN, _GEOM as set; out6: ARGP, ET, TAIL, HO, CH, geometry class; returns 0 when the form needs the device block and there is none
+extern "C" int hostcheck_eval_cluster_form(const int *sw6, int geom_class, int stamped, int have_dev_args, int *out6) {
+    frx::EvalClusterForm f;
+    const bool ok = frx::eval_cluster_form(hostcheck_switches(sw6), geom_class != 0, stamped != 0, have_dev_args != 0, f);
+    hostcheck_form_out(f, out6);
+    return ok;
+}
+// out24: up to four forms as above; returns their number
+extern "C" int hostcheck_eval_cluster_raised(const int *sw6, int *out24) {
+    frx::EvalClusterForm f[4];
+    const int n = frx::eval_cluster_raised_forms(hostcheck_switches(sw6), f);
+    for (int i = 0; i < n; i++) hostcheck_form_out(f[i], out24 + 6 * i);
+    return n;
+}
+// returns the PenaltyForm (THR, LAT, LAT2_17, LAT2_49, LAT2_0, LAT2_R5 = 0..5); *code: what frx_debug_penalty_kernel reports for it
+extern "C" int hostcheck_penalty_form(int lds_pen2, int lpp, int forced, int twophase_char, int *code) {
+    const frx::PenaltyForm f = frx::penalty_form(lds_pen2 != 0, lpp, forced, (char)twophase_char);
+    *code = frx::penalty_form_code(f);
+    return (int)f;
+}
+// in12: backward, tap, cand_active, stamps, eval_fused, eval_fused_stamps, eval_solo, B, solo_min_B, solo_max_B, lds_solo, knot solver; returns CLUSTER, SOLO, STAGES = 0..2
+extern "C" int hostcheck_eval_route(const int *in12) {
+    return (int)frx::eval_route(in12[0] != 0, in12[1] != 0, in12[2] != 0, in12[3] != 0, in12[4] != 0, in12[5] != 0, in12[6], in12[7], in12[8], in12[9], in12[10] != 0, in12[11] != 0);
+}
+extern "C" int hostcheck_pen_wave_doubles(int ppw, int Kmax) { return frx::pen_wave_doubles(ppw, Kmax); }
+extern "C" long long hostcheck_pen_wg_bytes(int ppg, int Kmax, int waves, int doubles_per_lane) { return (long long)frx::pen_wg_bytes(ppg, Kmax, waves, doubles_per_lane); }
+// A fresh LdsLimits table driven through a script of n raises with a setter that only records: fn[i] names one of 8 functions, fail[i] != 0 makes the setter return
+// the error 1 at step i.  called[i]: the bytes the setter was asked for at step i, 0 = no call; rc[i]: what raise returned.
+extern "C" void hostcheck_lds_limits(int n, const int *dev, const int *fn, const long long *bytes, const int *fail, long long *called, int *rc) {
+    static const char fns[8] = {};
+    frx::LdsLimits limits;
+    for (int i = 0; i < n; i++) {
+        called[i] = 0;
+        rc[i] = limits.raise(dev[i], &fns[fn[i] & 7], (size_t)bytes[i], [&](const void *f, size_t b) { called[i] = f == &fns[fn[i] & 7] ? (long long)b : -1; return fail[i] ? 1 : 0; });
+    }
+}
