@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "frx_map_mark_cloud", "frx_map_is_blocked", "frx_grid_search", "frx_jps_plan", "frx_route_plan",
     "frx_trajectory_check", "frx_trajectory_check_device", "frx_trajectory_sample", "frx_trajectory_sample_device",
     "frx_trajectory_extrema", "frx_trajectory_extrema_device",
+    "frx_gate_from_corners", "frx_trajectory_gates", "frx_trajectory_gates_device", "frx_gate_flags",
     "frx_trajectory_clearance", "frx_trajectory_clearance_workspace", "frx_trajectory_clearance_device",
     "frx_corridor_generate_batch", "frx_corridor_generate_batch_device",
     "frx_enumerate_vertices_batch", "frx_enumerate_vertices_batch_device", "frx_corridor_slots_to_tasks_device",
@@ -86,6 +87,9 @@ CHECK_MAX_INTERVALS = 16384
 CHECK_FLAG_CORRIDOR, CHECK_FLAG_SPEED, CHECK_FLAG_THRUST_MIN, CHECK_FLAG_THRUST_MAX, CHECK_FLAG_BODY_RATE, CHECK_FLAG_NONFINITE = 1, 2, 4, 8, 16, 32
 # frx_trajectory_extrema (include/frx.h): fields of a row; its flags are the CHECK_FLAG_* bits (no CORRIDOR bit)
 EXTREMA_FIELDS = ("speed", "acc", "thrust_min", "thrust_max", "body_rate", "t_speed", "t_acc", "t_thrust_min", "t_thrust_max", "t_body_rate")
+# frx_trajectory_gates (include/frx.h): fields of a gate's row and flag bits
+GATE_FIELDS = ("n_cross", "n_pass", "margin", "time", "piece", "u", "v", "reach_u", "reach_v", "normal_speed")
+GATE_FLAG_MISSED, GATE_FLAG_REPEAT, GATE_FLAG_ORDER, GATE_FLAG_NONFINITE = 1, 2, 4, 8
 # frx_trajectory_clearance (include/frx.h): fields of a row, flag bits, the largest cloud; CLEAR_TILE sample states and CLEAR_PASS cloud points are what a
 # workgroup of the kernel holds at a time (fast-racing_amd/csrc/frx_device.hpp), the sizes at which it takes another turn of a loop
 CLEAR_FIELDS = ("ell", "dist", "worst_t", "worst_i")
@@ -173,6 +177,10 @@ def lib():
         L.frx_trajectory_check_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.frx_trajectory_extrema.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_trajectory_extrema_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_gate_from_corners.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_gates.argtypes = [C.c_void_p] * 7
+        L.frx_trajectory_gates_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_gate_flags.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_trajectory_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         L.frx_trajectory_sample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_trajectory_clearance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -526,6 +534,30 @@ def traj_max_rates(T, Cf):
     return mv, ma
 
 
+def gate_from_corners(corners, with_fit: bool = False):
+    """Gate records (n, 9) {c, a, b} from corners (n, 4, 3) in order round each opening (frx_gate_from_corners, host only); with_fit adds the
+    (n, 2) fit {a.b / (|a| |b|), largest distance of a corner from the record's rectangle}."""
+    corners = np.ascontiguousarray(corners, dtype=np.float64)
+    if corners.size == 0 or corners.size % 12 != 0 or corners.shape[-1] not in (3, 12):
+        raise ValueError(f"gate_from_corners: corners must have shape (n, 4, 3), got {corners.shape}")
+    n = corners.size // 12
+    gates = np.zeros((n, 9)); fit = np.zeros((n, 2))
+    _check(lib().frx_gate_from_corners(n, corners.ctypes.data, gates.ctypes.data, fit.ctypes.data if with_fit else None))
+    return (gates, fit) if with_fit else gates
+
+
+def gate_flags(gate_rows, gate_off):
+    """GATE_FLAG_* words (B,) uint32 of the candidates from their gate rows (n_gates, 10) (frx_gate_flags, host only)."""
+    gate_off = np.ascontiguousarray(gate_off, dtype=np.int32).reshape(-1)
+    rows = np.ascontiguousarray(gate_rows, dtype=np.float64).reshape(-1, len(GATE_FIELDS))
+    B = gate_off.size - 1
+    if B >= 1 and rows.shape[0] < int(gate_off.max()):
+        raise ValueError(f"gate_flags: {rows.shape[0]} rows for gate_off up to {int(gate_off.max())}")
+    flags = np.zeros(max(B, 0), np.uint32)
+    _check(lib().frx_gate_flags(B, gate_off.ctypes.data, rows.ctypes.data if rows.size else flags.ctypes.data, flags.ctypes.data))
+    return flags
+
+
 def traj_to_msg(T, Cf):
     """PolynomialTrajectory array fields of one trajectory: (coef_x, coef_y, coef_z, time, order)."""
     n = len(T)
@@ -774,6 +806,28 @@ class Problem:
     def trajectory_extrema_device(self, T_ptr: int, C_ptr: int, out_ptr: int, stream: int = 0):
         """frx_trajectory_extrema_device: the piece rows (P x 10 doubles at out_ptr) as one launch on `stream`, device pointers, no synchronisation."""
         _check(lib().frx_trajectory_extrema_device(self.h, T_ptr, C_ptr, out_ptr, stream))
+
+    def trajectory_gates(self, T, Cf, gates, gate_off):
+        """Exact gate passage certificate of the batch (T, C) (frx_trajectory_gates): gates (n_gates, 9) records {c, a, b}, candidate b owning the
+        gates gate_off[b] .. gate_off[b + 1] - 1 in the order they are to be flown.  dict(gate (n_gates, 10), flags (B,) uint32 of GATE_FLAG_* bits)
+        plus the rows' fields by name (GATE_FIELDS)."""
+        T, Cf = self._traj_TC("trajectory_gates", T, Cf)
+        gate_off = np.ascontiguousarray(gate_off, dtype=np.int32).reshape(-1)
+        gates = np.ascontiguousarray(gates, dtype=np.float64)
+        if gate_off.size != self.B + 1:
+            raise ValueError(f"trajectory_gates: gate_off must hold {self.B + 1} offsets, got {gate_off.size}")
+        if gates.ndim != 2 or gates.shape[1] != 9 or gates.shape[0] != int(gate_off[-1]):
+            raise ValueError(f"trajectory_gates: gates must have shape ({int(gate_off[-1])}, 9), got {gates.shape}")
+        rows = np.zeros((gates.shape[0], len(GATE_FIELDS))); flags = np.zeros(self.B, np.uint32)
+        _check(lib().frx_trajectory_gates(self.h, T.ctypes.data, Cf.ctypes.data, gate_off.ctypes.data, gates.ctypes.data, rows.ctypes.data, flags.ctypes.data))
+        out = {"gate": rows, "flags": flags}
+        out.update({name: rows[:, i] for i, name in enumerate(GATE_FIELDS)})
+        return out
+
+    def trajectory_gates_device(self, T_ptr: int, C_ptr: int, n_gates: int, gate_off_ptr: int, gates_ptr: int, out_ptr: int, stream: int = 0):
+        """frx_trajectory_gates_device: the gate rows (n_gates x 10 doubles at out_ptr) as one launch on `stream`, device pointers (gate_off_ptr: B + 1
+        int32), no copy, no synchronisation, no allocation."""
+        _check(lib().frx_trajectory_gates_device(self.h, T_ptr, C_ptr, int(n_gates), gate_off_ptr, gates_ptr, out_ptr, stream))
 
     def trajectory_sample(self, T, Cf, n_samples: int, dt: float = 0.0, t0: float = 0.0, times=None):
         """Every candidate of the batch (T, C) at n_samples times with its SE(3) outputs (frx_trajectory_sample): times (B, n_samples) from each

@@ -36,6 +36,7 @@
 #include "frx_host_setup.hpp"
 #include "frx_compact.hpp"
 #include "frx_traj_fold.hpp"
+#include "frx_gate_host.hpp"
 
 namespace {
 
@@ -235,6 +236,7 @@ struct frx_problem {
     DevBuf<double> d_check;                                 // [P][8] rows of frx_trajectory_check, allocated on its first call
     DevBuf<double> d_extrema;                               // [P][10] rows of frx_trajectory_extrema, allocated on its first call
     DevBuf<double> d_sample;                                // frx_trajectory_sample: [B][S][20] rows, then [B][S] times; grown as needed
+    DevBuf<double> d_gates;                                 // frx_trajectory_gates: [n_gates][10] rows, the records [n_gates][9], then gate_off [B + 1] as ints; grown as needed
     DevBuf<double> d_clear;                                 // frx_trajectory_clearance: [P][4] rows, the cloud [n_obs][3], then the partials [P][chunks][4]; grown as needed
     int clear_chunk = 0;                                    // tests (frx_debug_set_clear_chunk): > 0 = cloud points per chunk, 0 = the library's own split
     // device-vector L-BFGS state (allocated on first use)
@@ -1139,6 +1141,59 @@ int frx_trajectory_extrema(frx_problem *p, const double *T, const double *C, dou
     FRX_TRY(fetch_rows(p, p->d_extrema.p, n_rows, piece_out));
     const double lim[4] = {p->cfg.vel_max, p->cfg.thr_acc_min, p->cfg.thr_acc_max, p->cfg.body_rate_max};
     frx::fold_extrema(p->B, p->poff.data(), T, p->h_out20.p, lim, cand_out, flags);
+    return FRX_OK;
+}
+
+int frx_gate_from_corners(int n, const double *corners, double *gates, double *fit) {
+    if (n < 1 || !corners || !gates) return fail(FRX_ERR_INVALID_ARG, "frx_gate_from_corners: n must be >= 1 and corners, gates not NULL");
+    frx::gate_from_corners(n, corners, gates, fit);
+    return FRX_OK;
+}
+
+// gate_off of B candidates: starts at 0 and never falls
+static int gate_off_args(int B, const int *gate_off) {
+    if (gate_off[0] != 0) return fail(FRX_ERR_INVALID_ARG, "gate_off[0] must be 0");
+    for (int b = 0; b < B; b++)
+        if (gate_off[b + 1] < gate_off[b]) return fail(FRX_ERR_INVALID_ARG, "gate_off must not fall (candidate " + std::to_string(b) + ")");
+    return FRX_OK;
+}
+
+int frx_gate_flags(int B, const int *gate_off, const double *gate_rows, unsigned *flags) {
+    if (B < 1 || !gate_off || !gate_rows || !flags) return fail(FRX_ERR_INVALID_ARG, "frx_gate_flags: B must be >= 1 and no argument NULL");
+    FRX_TRY(gate_off_args(B, gate_off));
+    frx::gate_flags(B, gate_off, gate_rows, flags);
+    return FRX_OK;
+}
+
+int frx_trajectory_gates_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_gates, const int *gate_off_dev, const double *gates_dev,
+                                double *gate_out_dev, void *hip_stream) {
+    static_assert(FRX_GATE_FIELDS == (int)frx::GATE_FIELDS, "frx.h and frx_device.hpp agree");
+    if (!p || !T_dev || !C_dev || !gate_off_dev || !gates_dev || !gate_out_dev) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (n_gates < 1) return fail(FRX_ERR_INVALID_ARG, "n_gates must be >= 1");
+    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    HIP_TRY((hipError_t)frx::launch_gates(p->B, p->dp.poff, p->dp.pc.gAcc, p->dp.pc.ell, T_dev, C_dev, n_gates, gate_off_dev, gates_dev, gate_out_dev, hip_stream));
+    return FRX_OK;
+}
+
+int frx_trajectory_gates(frx_problem *p, const double *T, const double *C, const int *gate_off, const double *gates, double *gate_out, unsigned *flags) {
+    if (!p || !T || !C || !gate_off || !gates || !gate_out) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    FRX_TRY(gate_off_args(p->B, gate_off));
+    const int n_gates = gate_off[p->B];
+    if (n_gates < 1) return fail(FRX_ERR_INVALID_ARG, "frx_trajectory_gates: no gates (gate_off[B] < 1)");
+    HIP_TRY(hipSetDevice(p->device));
+    // one buffer: the rows [n_gates][10], the records [n_gates][9], then gate_off as B + 1 ints
+    const size_t n_rows = (size_t)FRX_GATE_FIELDS * n_gates, n_rec = 9 * (size_t)n_gates, n_off = ((size_t)p->B + 2) / 2;
+    FRX_TRY(grow(p->d_gates, n_rows + n_rec + n_off, "frx_trajectory_gates"));
+    double *d_rows = p->d_gates.p, *d_rec = d_rows + n_rows;
+    int *d_off = (int *)(d_rec + n_rec);
+    FRX_TRY(stage_TC(p, T, C));
+    HIP_TRY(hipMemcpyAsync(d_rec, gates, sizeof(double) * n_rec, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(d_off, gate_off, sizeof(int) * ((size_t)p->B + 1), hipMemcpyHostToDevice, p->stream));
+    FRX_TRY(frx_trajectory_gates_device(p, p->d_T.p, p->d_C.p, n_gates, d_off, d_rec, d_rows, p->stream));
+    HIP_TRY(hipMemcpyAsync(gate_out, d_rows, sizeof(double) * n_rows, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (flags) frx::gate_flags(p->B, gate_off, gate_out, flags);
     return FRX_OK;
 }
 

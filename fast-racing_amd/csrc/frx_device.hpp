@@ -113,6 +113,13 @@ enum { EXTREMA_FIELDS = 10 };
 // out: [P][10] (frx.h FRX_EXTREMA_*) of the pieces (T, C) under gravity g_acc; T / C / out are device pointers.  One launch, no dynamic LDS.
 int launch_extrema(int P, double g_acc, const double *T, const double *C, double *out, void *stream);
 
+// ---- exact gate passage certificate (frx_gates_kernel.hpp) ----
+enum { GATE_FIELDS = 10 };
+// out: [n_gates][10] (frx.h FRX_GATE_*) of the gate records gates [n_gates][9] against the pieces (T, C) of the B candidates poff [B + 1] lays out; candidate b owns
+// the gates gate_off[b] .. gate_off[b + 1] - 1.  ell: the body ellipsoid's three semi-axes (host).  Everything else is a device pointer.  One launch, no dynamic LDS.
+int launch_gates(int B, const int *poff, double g_acc, const double *ell, const double *T, const double *C, int n_gates, const int *gate_off,
+                 const double *gates, double *out, void *stream);
+
 // ---- batched sampling with SE(3) outputs (frx_sample_kernel.hpp) ----
 // 1 when candidates of up to maxN fine pieces fit the kernel's LDS
 int sample_fits(int maxN);

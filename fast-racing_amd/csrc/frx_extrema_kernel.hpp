@@ -204,6 +204,7 @@ __device__ __forceinline__ void ext_rate_task(const double (*wh)[3], double *lds
     }
 }
 
+#ifndef FRX_EXT_NO_KERNEL                                                // (frx_gates_kernel.hpp takes the device functions above and not the kernel)
 // grid (ceil(P / 64), EXT_TASKS), 64 threads; out [P][EXT_FIELDS]
 __global__ void __launch_bounds__(64) k_traj_extrema(int P, double g, const double *__restrict__ T, const double *__restrict__ C, double *__restrict__ out) {
 #pragma clang fp contract(off)
@@ -259,5 +260,6 @@ __global__ void __launch_bounds__(64) k_traj_extrema(int P, double g, const doub
     ext_rate_task(wa, lds, hi);
     o[4] = __builtin_sqrt(hi.v) / h; o[9] = hi.t * h;
 }
+#endif
 
 } // namespace frx

@@ -353,6 +353,73 @@ int frx_trajectory_check_device(frx_problem *p, const double *T_dev, const doubl
 int frx_trajectory_extrema(frx_problem *p, const double *T, const double *C, double *piece_out, double *cand_out, unsigned *flags);
 int frx_trajectory_extrema_device(frx_problem *p, const double *T_dev, const double *C_dev, double *piece_out_dev, void *hip_stream);
 
+/* Exact gate passage certificate of a batch of results, on the device.  The reference reads four corner poses per gate and keeps their mean
+ * (se3_node_cpu.cpp:44-61); the centres are way-points of the path search (MinCoPlan_CPU.cpp:13-35) and nothing checks afterwards that the result flies
+ * through a gate.  The corridors of frx_trajectory_check are dilated cells round the searched path, not the gate openings.  These entries answer, for
+ * every (candidate, gate): does the candidate cross the gate's plane, when, inside the opening with how much room for the body at the attitude it has
+ * there, and in gate order.
+ * A gate record is 9 doubles {c[3], a[3], b[3]}: the opening is {c + s a + t b : |s| <= 1, |t| <= 1}, a and b the half-edge vectors; the caller vouches
+ * that they are orthogonal.  Derived, one correctly rounded operation after the other: wu = |a|, wv = |b|, eu = a / wu, ev = b / wv, m = a x b,
+ * n = m / |m| (divisions by the norm, no reciprocal).  Candidate b owns the gates gate_off[b] .. gate_off[b + 1] - 1 in the order they are to be
+ * flown; a candidate may own none.
+ * Crossings.  On every piece, in normalised time tau = t / T with w_k = c_k T^k, f(tau) = n.(w_0 - c) + sum_{k >= 1} (n.w_k) tau^k is a quintic; its
+ * roots on [0, 1] are found as frx_trajectory_extrema finds roots (every sign change, bracketed by the derivative's roots and bisected down to adjacent
+ * doubles): the crossing instants are exact, nothing is sampled.  A root that is exactly tau == 0 is dropped unless the piece is the candidate's first:
+ * a knot on the plane counts once, for the earlier piece.  An exact zero of f at a critical point is a root of that recursion, so a trajectory that
+ * touches the plane without changing sides counts as a crossing, with NORMAL_SPEED 0.
+ * At a crossing: p, v, a of the piece, h = a + g e3, zB = h / sqrt(h.h), yB = (0, zB.z, -zB.y) / sqrt(zB.z^2 + zB.y^2), xB = yB x zB (the frame of the
+ * check and the penalty, with square root and division in place of their fast reciprocal root); d = p - c, s = eu.d, t = ev.d;
+ *   ru = sqrt((e0 xB.eu)^2 + (e1 yB.eu)^2 + (e2 zB.eu)^2), rv likewise with ev: the body ellipsoid's reach along the gate's axes, in the form of
+ *   FRX_CHECK_CORRIDOR, WITHOUT safe_margin;   MARGIN = min(wu - |s| - ru, wv - |t| - rv);   the crossing PASSES when MARGIN >= 0.
+ * Fields of a gate's row (FRX_GATE_FIELDS doubles):
+ *   FRX_GATE_N_CROSS, FRX_GATE_N_PASS   crossings and passing crossings over all the candidate's pieces (sums of integers: exact)
+ *   the REPORTED crossing: FRX_GATE_MARGIN; FRX_GATE_TIME from the candidate's start, cum[k] + tau T_k with cum summed left to right as
+ *   frx_trajectory_sample defines it; FRX_GATE_PIECE the local index k; FRX_GATE_U (s), FRX_GATE_V (t); FRX_GATE_REACH_U (ru), FRX_GATE_REACH_V (rv);
+ *   FRX_GATE_NORMAL_SPEED n.v, signed
+ * The reported crossing is the least under one total order: a crossing whose margin is NaN first, then passing crossings before the others; among
+ * passing ones the earlier (piece, then root); among the others the larger margin, then the earlier.  So the row names the first passage if there is
+ * one and the nearest miss otherwise.  No crossing: N_CROSS = N_PASS = 0, MARGIN = -inf, PIECE = -1, the other fields 0.  All ten fields NaN when a
+ * piece of the candidate has T not finite or <= 0 or a coefficient not finite, or when the gate record is not finite or has |a|, |b| or |a x b|
+ * equal to 0.  Rows are bit-identical run to run, between the forms, and whatever else is in the batch.  Flags per candidate: FRX_GATE_FLAG_*.
+ * What the certificate is NOT.  It holds at the instant the body's centre is in the gate's plane.  The reach is the body's full projection on the
+ * gate's axis, which is at least its section by the plane: conservative in extent.  It is not swept in time: a long body at a shallow angle may
+ * touch the frame before or after that instant.  The gate's frame as an obstacle belongs to frx_trajectory_clearance.
+ *   frx_gate_from_corners        host only, no device: n gates of four corners in order round the opening (corners n x 12, what
+ *                                se3_node_cpu.cpp:44-61 reads) -> records (gates n x 9).  c = (((c0 + c1) + c2) + c3) / 4 (the reference's sum),
+ *                                a = ((c1 - c0) + (c2 - c3)) / 4, b = ((c3 - c0) + (c2 - c1)) / 4.  fit (n x 2, may be NULL):
+ *                                {a.b / (|a| |b|), max_i |corner_i - (c -/+ a -/+ b)|} - how far from a rectangle the corners are.
+ *   frx_trajectory_gates         blocking, host pointers: T[total fine pieces], C[total fine pieces x 18], gate_off[B + 1], gates[gate_off[B] x 9];
+ *                                gate_out (gate_off[B] x 10); flags (B) may be NULL and is filled as frx_gate_flags fills it.  Keeps one device buffer
+ *                                per handle for the gates and grows it (FRX_ERR_ALLOC when it cannot).
+ *   frx_trajectory_gates_device  ONE launch on the caller's stream, device pointers: no copy, no synchronisation, no allocation (capturable in a
+ *                                hipGraph).  The caller vouches for gate_off_dev: monotone, starting at 0, ending at n_gates.
+ *   frx_gate_flags               host only: the flag words from gate rows (for callers of the _device form).
+ * FRX_ERR_INVALID_ARG, reported before a device is looked for: NULL arguments (flags of the blocking form and fit excepted), n or B < 1,
+ * n_gates < 1 (device form), gate_off[0] != 0 or a non-monotone gate_off (frx_gate_flags).  FRX_ERR_NO_DEVICE without a device.  The blocking form
+ * reads B from the handle - a handle exists only where a device does - and then returns FRX_ERR_INVALID_ARG for gate_off[0] != 0, a non-monotone
+ * gate_off or gate_off[B] < 1, before anything is staged.  Serves both kinds of handle. */
+#define FRX_GATE_FIELDS 10
+#define FRX_GATE_N_CROSS 0
+#define FRX_GATE_N_PASS 1
+#define FRX_GATE_MARGIN 2
+#define FRX_GATE_TIME 3
+#define FRX_GATE_PIECE 4
+#define FRX_GATE_U 5
+#define FRX_GATE_V 6
+#define FRX_GATE_REACH_U 7
+#define FRX_GATE_REACH_V 8
+#define FRX_GATE_NORMAL_SPEED 9
+#define FRX_GATE_FLAG_MISSED 1u         /* a gate with N_PASS == 0 */
+#define FRX_GATE_FLAG_REPEAT 2u         /* a gate with N_PASS > 1 */
+#define FRX_GATE_FLAG_ORDER 4u          /* the TIMEs of the gates that passed are not strictly increasing in gate order */
+#define FRX_GATE_FLAG_NONFINITE 8u      /* a NaN in one of the candidate's rows */
+int frx_gate_from_corners(int n, const double *corners /* n x 12 */, double *gates /* n x 9 */, double *fit);
+int frx_trajectory_gates(frx_problem *p, const double *T, const double *C, const int *gate_off /* B + 1 */, const double *gates,
+                         double *gate_out /* gate_off[B] x FRX_GATE_FIELDS */, unsigned *flags /* B, may be NULL */);
+int frx_trajectory_gates_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_gates, const int *gate_off_dev,
+                                const double *gates_dev, double *gate_out_dev, void *hip_stream);
+int frx_gate_flags(int B, const int *gate_off, const double *gate_rows, unsigned *flags);
+
 /* Batched sampling of results with their SE(3) outputs, on the device.  The reference's traj_server evaluates one PolynomialTrajectory message at
  * control rate (traj_server.cpp:397-456: position, velocity, acceleration, jerk) and its controller derives attitude and thrust from the
  * acceleration; frx_msg_sample is that call for one time.  These entries sample every candidate of the handle's batch at S = n_samples times
