@@ -77,7 +77,7 @@ ABI_SYMBOLS = [
 DEBUG_SYMBOLS = [
     "frx_debug_trace", "frx_resident_profile", "frx_debug_direction_log", "frx_debug_direction_log_read", "frx_debug_set_resident_retry",
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
-    "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_eval_geometry", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
+    "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_eval_geometry", "frx_debug_eval_front", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
     "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device", "frx_debug_dv_layout", "frx_debug_dv_round", "frx_debug_fold_rows",
 ]
 
@@ -147,6 +147,7 @@ def lib():
         L.frx_debug_set_eval_fused.argtypes = [C.c_void_p, C.c_int]
         L.frx_debug_eval_fused.argtypes = [C.c_void_p]
         L.frx_debug_eval_geometry.argtypes = [C.c_void_p]
+        L.frx_debug_eval_front.argtypes = [C.c_void_p]
         L.frx_debug_set_eval_solo.argtypes = [C.c_void_p, C.c_int]
         L.frx_debug_eval_solo.argtypes = [C.c_void_p]
         L.frx_debug_penalty_kernel.argtypes = [C.c_void_p]
@@ -933,6 +934,11 @@ class Problem:
     def eval_geometry(self) -> int:
         """1 = the one-launch evaluation of this handle launches the compile-time geometry class (frx_eval_kernel.hpp, EvalGeomK16), 0 = the run-time form."""
         return int(lib().frx_debug_eval_geometry(self.h))
+
+    def eval_front(self) -> int:
+        """1 = the one-launch evaluation of this handle takes the two-trip front (frx_eval_kernel.hpp, FR: front records and the argument block's leading lines), 0 = the
+        front that walks the offset tables (FRX_EVAL_FRONT=0, or a form without it)."""
+        return int(lib().frx_debug_eval_front(self.h))
 
     def set_eval_solo(self, mode: int):
         """Diagnostic: 0 = never the solo form (one workgroup per candidate, one launch per evaluation, frx_solo_kernel.hpp), 1 = from the handle's batch-size

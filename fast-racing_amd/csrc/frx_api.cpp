@@ -30,6 +30,7 @@
 #include "../../include/frx_debug.h"
 #include "frx_device.hpp"
 #include "frx_launch_forms.hpp"
+#include "frx_eval_front.hpp"
 #include "frx_internal.hpp"
 #include "frx_lbfgs.hpp"
 #include "frx_host_pool.hpp"
@@ -279,6 +280,7 @@ struct frx_problem {
     int eval_fused = 0, eval_fused_G = 0, eval_fused_stamps = 0;
     unsigned long long eval_fused_ticks = 25000000ull;      // bound of every wait inside the launch, ticks of the 100 MHz counter: 250 ms (a healthy evaluation takes ~20 us; FRX_EVAL_TIMEOUT_MS)
     std::vector<unsigned char> ev_args, ev_args_st;         // the one-launch evaluation's constant arguments (frx::eval_cluster_args), host copies: without / with the stamps pointer
+    DevBuf<frx::EvalFront> d_ev_front;                      // the one-launch evaluation's front records, one per candidate (frx_eval_front.hpp): constant for the handle's life, uploaded at create
     DevBuf<unsigned char> d_ev_args, d_ev_args_st;          // their device copies: uploaded at create / by the diagnostic that sets the pointer (profile_eval_cluster) - never by an evaluation
     PinBuf<unsigned> h_ev_status;                           // mapped host word: the code of an expired wait, written by the leader that saw it - launch_eval reads it without a synchronisation
     unsigned eval_fused_code = 0;                           // the code that retired the one-launch form on this handle (0: none)
@@ -570,6 +572,9 @@ int frx_problem_create(const frx_config *cfg, int device, int B, const int *coar
         p->d_ev_words = (unsigned *)(p->d_ev_ll.p + n_ll);
         { NumaScope numa_alloc(device); CR(p->h_ev_status.alloc(16)); }
         p->ev_args.assign(frx::eval_cluster_args_bytes(), 0); CR(p->d_ev_args.alloc(p->ev_args.size()));
+        std::vector<frx::EvalFront> front((size_t)B);                      // from the host copies of the tables uploaded above
+        frx::eval_front_fill(B, p->poff.data(), p->coff.data(), p->xoff.data(), cvoff.data(), p->softT, p->geo.ppw, front.data());
+        CR(p->d_ev_front.upload(front));
     }
     {   // pinned staging buffers: pages from the device's NUMA node (NumaScope)
         NumaScope numa_alloc(device);
@@ -597,7 +602,7 @@ int frx_problem_create(const frx_config *cfg, int device, int B, const int *coar
     d.wp_vbeg = p->d_wp_vbeg.p; d.wp_nv = p->d_wp_nv.p; d.wp_xbeg = p->d_wp_xbeg.p;
     d.hblk = p->d_hblk.p; d.vrec = p->d_vrec.p; d.wq_glob = p->d_wq.p; d.stamps = nullptr; d.cand_active = nullptr; d.piece_active = nullptr;
     if (p->eval_fused_G) {                                                  // (the first evaluation may be captured: the device copy of its arguments is complete before create returns)
-        frx::eval_cluster_args(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_ev_ll.p, p->d_ev_words, p->ev_args.data());
+        frx::eval_cluster_args(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_ev_ll.p, p->d_ev_words, p->d_ev_front.p, p->ev_args.data());
         const hipError_t e_ = hipMemcpy(p->d_ev_args.p, p->ev_args.data(), p->ev_args.size(), hipMemcpyHostToDevice);
         if (e_ != hipSuccess) { const std::string m_ = std::string("upload of the evaluation arguments: ") + hipGetErrorString(e_); (void)hipStreamDestroy(p->stream); delete p; return fail(FRX_ERR_HIP, m_); }
     }
@@ -698,7 +703,7 @@ static int profile_eval_cluster(frx_problem *p, const double *x, long long *out,
     p->dp.stamps = p->d_stamps.p; p->eval_fused_stamps = 1;
     {   // the argument block with the stamps pointer: a device copy of its own, uploaded here (a blocking call), so that no evaluation ever has to
         p->ev_args_st.assign(frx::eval_cluster_args_bytes(), 0);
-        frx::eval_cluster_args(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_ev_ll.p, p->d_ev_words, p->ev_args_st.data());
+        frx::eval_cluster_args(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_ev_ll.p, p->d_ev_words, p->d_ev_front.p, p->ev_args_st.data());
         hipError_t e_ = p->d_ev_args_st.p ? hipSuccess : p->d_ev_args_st.alloc(p->ev_args_st.size());
         if (e_ == hipSuccess) e_ = hipMemcpy(p->d_ev_args_st.p, p->ev_args_st.data(), p->ev_args_st.size(), hipMemcpyHostToDevice);
         if (e_ != hipSuccess) { p->dp.stamps = nullptr; p->eval_fused_stamps = 0; return fail(FRX_ERR_HIP, hipGetErrorString(e_)); }
@@ -929,6 +934,7 @@ int frx_debug_set_eval_fused(frx_problem *p, int enable) {
 }
 int frx_debug_eval_fused(const frx_problem *p) { return (p && p->eval_fused) ? p->eval_fused_G : 0; }
 int frx_debug_eval_geometry(const frx_problem *p) { return (p && p->eval_fused) ? frx::eval_cluster_class(p->geo) : 0; }
+int frx_debug_eval_front(const frx_problem *p) { return (p && p->eval_fused) ? frx::eval_cluster_front(p->geo) : 0; }
 // Diagnostic (bench, tests): the solo form of an evaluation (one workgroup per candidate, one launch).  mode: 0 = never, 1 = from the handle's threshold on (the
 // default), 2 = at every batch size.  frx_debug_eval_solo: workgroups of the kernel a CU holds when the NEXT evaluation of this handle takes the form, 0 = it does not.
 int frx_debug_set_eval_solo(frx_problem *p, int mode) {

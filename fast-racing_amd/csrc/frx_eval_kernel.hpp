@@ -34,11 +34,25 @@
 #pragma once
 #include <type_traits>
 
+#include "frx_eval_front.hpp"
 #include "frx_round_kernel.hpp"
 
 namespace frx {
 
+// The three leading lines of the argument block (FR below): every pointer and integer that an ADDRESS of the front's loads, or the LDS layout, is made of, the time layer's two
+// switches, and in the third line the run-time VALUES the geometry class parks in vector registers across the forward map (the other instantiations do not read that line) -
+// copies of fields of `dp` and of the geometry further down, which keep their places (DevProblem is every other kernel's too).
+struct EvalArgsLead {
+    const int *piece_coarse, *piece_iv, *wp_nv, *wp_vbeg, *wp_xbeg;
+    const double *vrec, *hblk, *headPVA, *tailPVA;
+    unsigned *status, *words;
+    int maxN19, maxXb, maxVb, maxCN, nsteps, pen_lds, ppw, Kmax, soft, c2;
+    double chi[4], inv_kappa; ll_u64 *out20ll; int kappa, pad[3];
+};
+static_assert(sizeof(EvalArgsLead) == 192 && offsetof(EvalArgsLead, chi) == 128, "three 64-byte lines");
+
 struct EvalClusterArgs {                      // constant for the life of a handle (a copy lives in device memory: ARGP below)
+    EvalArgsLead lead;
     DevProblem dp;
     double *T, *C;
     ll_u64 *out20ll;                         // 20 granules per piece: the penalty partials, members -> leader (its own buffer: the round kernel's carries tags of its own).  Candidate c owns the 40 N words
@@ -48,7 +62,9 @@ struct EvalClusterArgs {                      // constant for the life of a hand
                                              // members 1 .. G-1 (written at their entry), word 32 = tag of the last completed evaluation
     unsigned *status;                        // [1] sticky error word
     int G, maxCN, maxXb, maxVb, nsteps, lpp, ppw, Kmax, pen_lds, maxN19;
+    const EvalFront *front;                  // [B] front records (frx_eval_front.hpp), a device allocation of the handle; a launch passes it as the kernel's third argument
 };
+static_assert(offsetof(EvalClusterArgs, lead) == 0, "the leading lines lead");
 
 // LDS of a workgroup (doubles): 2 control | (C, T) copy, x, polytopes, multipliers, waypoint sums, evaluation scratch (leader AND members: both run the forward map) | members: 4 waves x pen_lds
 struct EvalClusterLds { int ctl, xs, vs, pw, wq, ev, mem, total; };
@@ -77,14 +93,22 @@ struct EvalCallArgs {                         // what changes per call
     const double *x; double *f, *g;
     unsigned *status_host;                   // optional, mapped host memory: the code of an expired wait, where the launcher sees it without a synchronisation (frx_api.cpp: launch_eval)
     rk_u64 timeout_ticks;                    // bound of every spin
-    int test_drop_members;                   // tests (frx_debug_set_eval_fused(p, 2)): the members leave at once, as if they never got a CU - the leader's wait for the partials expires
-    int force_wt;                            // 1 = every payload store write-through, as if no two workgroups shared an XCD (tests: FRX_EVAL_FUSED_WT=1)
+    unsigned short G, B;                     // (FR) the handle's G and B - with them and the records' pointer (the kernel's third argument) a workgroup knows its cluster, its place in it and its
+                                             // record's address from the kernarg segment alone.  Handle constants, so a captured graph may hold them; B G <= the CU count is the launcher's rule
+    unsigned char test_drop_members;         // tests (frx_debug_set_eval_fused(p, 2)): the members leave at once, as if they never got a CU - the leader's wait for the partials expires
+    unsigned char force_wt;                  // 1 = every payload store write-through, as if no two workgroups shared an XCD (tests: FRX_EVAL_FUSED_WT=1)
 };
+static_assert(sizeof(EvalCallArgs) + 2 * sizeof(void *) <= 64, "argument pointer, call arguments and the records' pointer: one 64-byte line of the kernarg segment");
 // The early barrier of the early-duration form (forward_knot_body<.., ET>): the caller's loads behind the body's, then one barrier that zeroes the counters and makes the
 // status early-out workgroup-uniform.
-template <class F, bool NS = false> struct EvalEarlySync {
+// FRN (FR below): the caller has issued wave 0's tau load itself and holds what the early-duration block otherwise reads from the index tables and the argument block.
+template <class F, bool NS = false, bool FRN = false> struct EvalEarlySync {
     static constexpr bool nostamps = NS;          // (CH below: no cycle stamps compiled into the forward map)
+    static constexpr bool front_held = FRN;
     const F &f; long long *st; bool steps;
+    long long *front;                             // (cluster 0's leader, stamped form) [0] wave 0's tau load issued, [1] tau in its register: slots 32, 33 of the stamp block
+    // (FRN) the candidate's tau / variable / vertex-double counts, the time layer's two switches, the candidate's first vertex record, wave 0's tau
+    int nT, nx, nvd, soft, c2; gptr<const double> vsrc; double tau;
     __device__ __forceinline__ bool sync() const { return f(); }
 };
 // TAIL (the default; FRX_EVAL_TAIL=0 takes the other form, A/B): thread 0 of the leader stores f and `done` inside the adjoint, right behind the objective's sum
@@ -125,31 +149,74 @@ template <class GEO> struct eval_geom {
     static_assert(ppw * lpp <= 64 && ppw * hstride <= 2 * 64, "a wave-task: one lane per sample, one double2 of its corridor blocks per lane");
 };
 template <> struct eval_geom<void> { static constexpr bool fixed = false; static constexpr int lpp = 0, ppw = 0, kmax = 0, nsteps = 0, hstride = 0, pen_lds = 0; };
-template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void>
-__global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::conditional<ARGP, const EvalClusterArgs *__restrict__, EvalClusterArgs>::type arg, EvalCallArgs call) {
+// FR (the default wherever the form has the argument pointer and early durations; FRX_EVAL_FRONT=0 takes the other front, A/B): TWO trips behind the entry.  Through the
+// tables the front is a chain of first touches, each waited for before the next address exists: the argument block's lines one by one, poff, coff / xoff / cvoff, the
+// per-piece and waypoint tables, the end states, the class's parked values - and only then tau (2.0 us from the leader's entry to the tau load on the stamps,
+// profiles/NOTES.md).  Here the kernarg segment alone gives a workgroup its cluster and its place in it (G and B travel in EvalCallArgs, the records' pointer is the
+// kernel's third argument); it reads its candidate's record (EvalFront, one line) and the three leading lines of the argument block (EvalArgsLead) as one group of scalar
+// loads, waits ONCE, and issues every global load of the front as one group: the status word and `done` (neither is waited for in front of the barrier by anybody but
+// thread 0's wave), wave 0's tau, the piece and waypoint tables' entries, the end states - the body receives them as a KnotPre - then the body's own first staging trip
+// and the members' corridor block.  The class's parked values come with the third leading line: requested behind the loads they would be a trip of their own, waited
+// for at the early barrier.  Integers only: no floating-point expression, operand or order changes, f and the gradient are the other front's bits
+// (tests/test_gpu_eval_front.py).  The read of the broadcast status word behind the early barrier is an LDS read by type here (as a generic volatile read it is a flat load
+// with a wait for every load the wave has in flight).
+template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void, bool FR = false>
+__global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::conditional<ARGP, const EvalClusterArgs *__restrict__, EvalClusterArgs>::type arg, EvalCallArgs call,
+                                                         const EvalFront *__restrict__ front) {   // (front: a kernel argument of its own - through a restrict pointer to const the record is a scalar load)
     static_assert(!CH || (ARGP && TAIL && HO), "the production form: argument pointer, inline tail, value-major hand-off");
     typedef eval_geom<GEO> GC;
     constexpr bool GF = GC::fixed;
     static_assert(!GF || (ARGP && ET && TAIL && HO), "the geometry class: the default form of every other switch");
+    static_assert(!FR || (ARGP && ET), "the two-trip front: the argument pointer and early durations");
     const EvalClusterArgs &a = [&]() -> const EvalClusterArgs & { if constexpr (ARGP) return *arg; else return arg; }();
     const auto stp = [&]() -> long long * { if constexpr (CH) return nullptr; else return a.dp.stamps; };   // (CH: a constant - every stamp below folds away)
     extern __shared__ __attribute__((aligned(16))) double sm[];
+    long long fr_entry = 0, fr_entry_cyc = 0;                       // (FR, stamped form: the clocks are read in front of the first load, the stamps go out once their pointer is there)
+    if constexpr (FR && !CH) { fr_entry = (long long)wall_clock64(); fr_entry_cyc = (long long)__builtin_readcyclecounter(); }
     const int lane8 = blockIdx.x & 7, rest = blockIdx.x >> 3;
-    const int wg = rest % a.G, k = lane8 + 8 * (rest / a.G);       // (k_round's mapping: a cluster's blocks share blockIdx % 8 - one XCD, as observed)
-    if (k >= a.dp.B) return;
+    const int nG = [&]() -> int { if constexpr (FR) return call.G; else return a.G; }();
+    const int wg = rest % nG, k = lane8 + 8 * (rest / nG);         // (k_round's mapping: a cluster's blocks share blockIdx % 8 - one XCD, as observed)
+    if (k >= [&]() -> int { if constexpr (FR) return call.B; else return a.dp.B; }()) return;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int c = k;
-    // (diagnostic, frx_debug_profile_eval_cluster: cycle stamps of cluster 0 - 40..43 the leader: entry, forward map done, adjoint done, end; 64..68 its tail, see EvalTail; 70..76 its poll for the partials, see EvalHandoff; 44..48 wave 0 of member 1, see penalty_wave_ll, and 69: the gate word's value has arrived - these in ticks of the 100 MHz counter all workgroups share; 49: the leader's shader clock at entry, the origin of the bodies' own stamps 0..31)
+    // (FR) the first trip: the candidate's record and the leading lines, one group of scalar loads and one wait
+    EvalFront fr = {};
+    EvalArgsLead ld = {};
+    gptr<const int> l_pc = nullptr, l_piv = nullptr, l_wnv = nullptr, l_wvb = nullptr, l_wxb = nullptr;
+    gptr<const double> l_vrec = nullptr, l_hblk = nullptr, l_head = nullptr, l_tail = nullptr;
+    gptr<unsigned> l_status = nullptr, l_words = nullptr;
+    if constexpr (FR) {
+        fr = front[k]; ld = a.lead;
+        l_pc = (gptr<const int>)ld.piece_coarse; l_piv = (gptr<const int>)ld.piece_iv; l_wnv = (gptr<const int>)ld.wp_nv; l_wvb = (gptr<const int>)ld.wp_vbeg; l_wxb = (gptr<const int>)ld.wp_xbeg;
+        l_vrec = (gptr<const double>)ld.vrec; l_hblk = (gptr<const double>)ld.hblk; l_head = (gptr<const double>)ld.headPVA; l_tail = (gptr<const double>)ld.tailPVA;
+        l_status = (gptr<unsigned>)ld.status; l_words = (gptr<unsigned>)ld.words;
+        // (one statement: the loads go out together in front of it.  The class reads its geometry's integers from no line, and its parked values from the third)
+#define FRX_FRONT_PINS "+s"(fr.p0), "+s"(fr.N), "+s"(fr.c0), "+s"(fr.cN), "+s"(fr.x0), "+s"(fr.nx), "+s"(fr.nT), "+s"(fr.cv0), "+s"(fr.nvd), "+s"(fr.wbase), "+s"(fr.ntasks), \
+                        "+s"(l_pc), "+s"(l_piv), "+s"(l_wnv), "+s"(l_wvb), "+s"(l_wxb), "+s"(l_vrec), "+s"(l_hblk), "+s"(l_head), "+s"(l_tail), "+s"(l_status), "+s"(l_words), \
+                        "+s"(ld.maxN19), "+s"(ld.maxXb), "+s"(ld.maxVb), "+s"(ld.maxCN), "+s"(ld.soft), "+s"(ld.c2)
+        if constexpr (GF) asm volatile("" : FRX_FRONT_PINS, "+s"(ld.chi[0]), "+s"(ld.chi[1]), "+s"(ld.chi[2]), "+s"(ld.chi[3]), "+s"(ld.inv_kappa), "+s"(ld.kappa));
+        else asm volatile("" : FRX_FRONT_PINS, "+s"(ld.nsteps), "+s"(ld.pen_lds), "+s"(ld.ppw), "+s"(ld.Kmax));
+#undef FRX_FRONT_PINS
+    }
+    // (diagnostic, frx_debug_profile_eval_cluster: cycle stamps of cluster 0 - 40..43 the leader: entry, forward map done, adjoint done, end; 32, 33 wave 0's tau load issued / tau in its register, see forward_knot_body; 64..68 its tail, see EvalTail; 70..76 its poll for the partials, see EvalHandoff; 44..48 wave 0 of member 1, see penalty_wave_ll, and 69: the gate word's value has arrived - these in ticks of the 100 MHz counter all workgroups share; 49: the leader's shader clock at entry, the origin of the bodies' own stamps 0..31)
+    if constexpr (FR) { if (stp() && k == 0 && wg == 0 && t == 0) { stp()[40] = fr_entry; stp()[49] = fr_entry_cyc; } }
+    else
     if (stp() && k == 0 && wg == 0 && t == 0) { stp()[40] = (long long)wall_clock64(); stp()[49] = (long long)__builtin_readcyclecounter(); }
-    unsigned *flag = a.words + (size_t)k * 64, *done = flag + 32;
-    const int p0 = a.dp.poff[c], N = a.dp.poff[c + 1] - p0;
-    // (the geometry's integers: constants of the class, or the argument block's fields read at each use as before)
+    unsigned *flag = FR ? (unsigned *)l_words + (size_t)k * 64 : a.words + (size_t)k * 64, *done = flag + 32;
+    const int p0 = [&]() -> int { if constexpr (FR) return fr.p0; else return a.dp.poff[c]; }();
+    const int N = [&]() -> int { if constexpr (FR) return fr.N; else return a.dp.poff[c + 1] - p0; }();
+    // (the geometry's integers: constants of the class, or the argument block's fields read at each use as before; FR: in front of the forward map the leading lines' copies)
     const auto g_ppw = [&]() -> int { if constexpr (GF) return GC::ppw; else return a.ppw; };
     const auto g_pen_lds = [&]() -> int { if constexpr (GF) return GC::pen_lds; else return a.pen_lds; };
     const auto g_kmax = [&]() -> int { if constexpr (GF) return GC::kmax; else return a.Kmax; };
-    const int ntasks = (N + g_ppw() - 1) / g_ppw();                     // wave-tasks of this candidate: ppw pieces each; members 1 .. G-1 hold 4 (G - 1) >= ntasks waves
+    const auto f_ppw = [&]() -> int { if constexpr (GF) return GC::ppw; else if constexpr (FR) return ld.ppw; else return a.ppw; };
+    const auto f_pen_lds = [&]() -> int { if constexpr (GF) return GC::pen_lds; else if constexpr (FR) return ld.pen_lds; else return a.pen_lds; };
+    const auto f_kmax = [&]() -> int { if constexpr (GF) return GC::kmax; else if constexpr (FR) return ld.Kmax; else return a.Kmax; };
+    const int ntasks = [&]() -> int { if constexpr (FR) return fr.ntasks; else return (N + g_ppw() - 1) / g_ppw(); }();   // wave-tasks of this candidate: ppw pieces each; members 1 .. G-1 hold 4 (G - 1) >= ntasks waves
     if (wg != 0 && ((wg - 1) * 4 >= ntasks || call.test_drop_members)) return;   // a member without a task
     unsigned st0 = 0u;                                              // (ET: thread 0's copy of the status word, the workgroup's first load)
+    if constexpr (FR) { if (t == 0) st0 = __hip_atomic_load(l_status, FRX_RLX_AGENT); }
+    else
     if constexpr (ET) { if (t == 0) st0 = __hip_atomic_load(a.status, FRX_RLX_AGENT); }
     else {
     // A wait of an EARLIER launch expired and nobody has cleared the word yet (the capturable form has no host-synchronous point of its own: replays of a captured
@@ -159,8 +226,14 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
         return;
     }
     }
-    unsigned tag = __hip_atomic_load(done, FRX_RLX_AGENT) + 1u;     // (stays in a vector register: nothing waits for the load until the tag is used)
+    // (stays in a vector register: nothing waits for the load until the tag is used.  FR: behind a global address the compiler knows to be uniform it would move the value to a scalar
+    // register at once, with a wait for every load in front of tau - so the load goes through an offset of zero it does not know, and the tag is formed behind the early barrier)
+    unsigned tag = 0u, tag_v = 0u;
+    if constexpr (FR) { int tag_at = 0; asm volatile("" : "+v"(tag_at)); tag_v = __hip_atomic_load(done + tag_at, FRX_RLX_AGENT); }
+    else {
+    tag = __hip_atomic_load(done, FRX_RLX_AGENT) + 1u;
     if (tag >= (1u << 28)) tag = 1u;
+    }
     // Where does this workgroup run?  Payload between two workgroups of one XCD can meet in that XCD's L2 (plain stores, L1-bypassing loads); across XCDs it has
     // to be written through to memory - measured 2.1 us of an 18.5 us evaluation.  The block -> cluster mapping above puts a cluster on one XCD on the hardware
     // this was written on, but nothing relies on it: the members publish their XCD at entry, the leader compares before it sends (C, T), its own XCD travels in
@@ -169,9 +242,9 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
     my_xcc = call.force_wt ? 0u : (my_xcc & 7u) + 1u;                  // 0: "nowhere" - never equal to a partner's
     int nsteps = GC::nsteps;
-    if constexpr (!GF) nsteps = a.nsteps;
+    if constexpr (!GF) { if constexpr (FR) nsteps = ld.nsteps; else nsteps = a.nsteps; }
     if constexpr (CH || GF) asm volatile("" : "+s"(nsteps));            // (GEO: the class's constant, opaque in a scalar register - see above)
-    const EvalClusterLds L = eval_cluster_lds(a.maxN19, a.maxXb, a.maxVb, a.maxCN, nsteps, g_pen_lds());
+    const EvalClusterLds L = FR ? eval_cluster_lds(ld.maxN19, ld.maxXb, ld.maxVb, ld.maxCN, nsteps, f_pen_lds()) : eval_cluster_lds(a.maxN19, a.maxXb, a.maxVb, a.maxCN, nsteps, g_pen_lds());
     // Round 6: the MEMBERS run the forward map too - the same body on the same x, so their (C, T) are the leader's bit for bit - instead of waiting for the leader's
     // coefficients: until now (C, T) travelled as granules behind a gate word (sweep 0.7 us, gate seen 0.15, granules polled and staged 0.7 us on the members' side) while
     // the members' four waves had nothing to do for the first 8 us of the launch.  The leader sends nothing; its XCD goes into the gate word at ENTRY (the members look at
@@ -183,11 +256,11 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     ro.quiet = wg != 0;
     const int task = (wg - 1) * 4 + wave;                                  // (members) this wave's task: ppw pieces
     const bool has_task = wg != 0 && task < ntasks;
-    const int gp0 = p0 + task * g_ppw(), npieces = has_task ? min(g_ppw(), N - task * g_ppw()) : 0;
-    const int hstride = (g_kmax() + 1) * 4;
-    double *wsm = sm + L.mem + (size_t)wave * g_pen_lds(), *hS = wsm, *red = wsm + (size_t)g_ppw() * hstride;
+    const int gp0 = p0 + task * f_ppw(), npieces = has_task ? min(f_ppw(), N - task * f_ppw()) : 0;
+    const int hstride = (f_kmax() + 1) * 4;
+    double *wsm = sm + L.mem + (size_t)wave * f_pen_lds(), *hS = wsm, *red = wsm + (size_t)f_ppw() * hstride;
     double2 hv[4];                                                  // (ET, members) the first trip of the corridor blocks, loaded behind the forward map's loads
-    const double2 *h2 = (const double2 *)(a.dp.hblk + (size_t)gp0 * hstride);
+    const double2 *h2 = (const double2 *)((FR ? (const double *)l_hblk : a.dp.hblk) + (size_t)gp0 * hstride);
     const int nh2 = (npieces * hstride) >> 1;
     bool bad = false;
     // (GEO, members) the run-time values the samples read from the argument block: requested here, parked in vector registers across the forward map
@@ -195,9 +268,9 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     gptr<ll_u64> m_llv = nullptr;
     if constexpr (GF) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) m_chi[i] = a.dp.pc.chi[i];
-        m_invk = a.dp.inv_kappa; m_kappa = a.dp.kappa;
-        m_llv = (gptr<ll_u64>)(a.out20ll + (size_t)p0 * 40);
+        for (int i = 0; i < 4; i++) m_chi[i] = FR ? ld.chi[i] : a.dp.pc.chi[i];         // (FR: they came with the leading lines - no trip of their own)
+        m_invk = FR ? ld.inv_kappa : a.dp.inv_kappa; m_kappa = FR ? ld.kappa : a.dp.kappa;
+        m_llv = (gptr<ll_u64>)((FR ? ld.out20ll : a.out20ll) + (size_t)p0 * 40);
         asm volatile("" : "+v"(m_chi[0]), "+v"(m_chi[1]), "+v"(m_chi[2]), "+v"(m_chi[3]), "+v"(m_invk), "+v"(m_kappa), "+v"(m_llv));
     }
     if constexpr (ET) {
@@ -213,15 +286,53 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
             unsigned *w = (unsigned *)(ev + 24 * 64);               // forward_knot_body's progress words (its rowbuf is ev)
             if (t == 0) { w[0] = 0u; w[2] = 0u; w[3] = 0u; w[4] = 0u; w[5] = st0; *verdict = 0u; }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            bad = *(volatile unsigned *)(w + 5) != 0u;
+            if constexpr (FR) {
+                bad = ((lds_vuptr)w)[5] != 0u;                       // (an LDS read by type)
+                if (!bad && wg == 0 && t == 0) {                     // (the tag is formed where it is used: here by the leader's thread 0 alone, by everybody else behind the forward map)
+                    unsigned tv = tag_v;
+                    asm volatile("" : "+v"(tv));
+                    tag = tv + 1u;
+                    if (tag >= (1u << 28)) tag = 1u;
+                }
+            }
+            else bad = *(volatile unsigned *)(w + 5) != 0u;
             if (!bad && wg == 0 && t == 0) __hip_atomic_store(flag, (tag << 4) | (my_xcc ? my_xcc : 15u), FRX_RLX_AGENT);
             return bad;
         };
-        const int wg_last = min(a.G - 1, (ntasks - 1) / 4 + 1);           // the last-dispatched member with a task
+        const int wg_last = min(nG - 1, (ntasks - 1) / 4 + 1);            // the last-dispatched member with a task
         long long *est = nullptr;
         if (stp() && k == 0 && (wg == 0 || wg == wg_last)) est = stp() + (wg == 0 ? 50 : 60);
-        const EvalEarlySync<decltype(early), CH> es{early, est, wg == 0};
+        long long *const fst = (stp() && k == 0 && wg == 0) ? stp() + 32 : nullptr;
+        if constexpr (FR) {
+            // the second trip: the loads the body would make from the index tables (KnotPre: its own expressions with the record's integers), wave 0's tau in front of them
+            const int t2 = t - 64;                                   // index among the axis waves
+            double tau = 0.0, r_bs[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            asm volatile("" : "+v"(tau));                            // (the zero is written here, in front of the load: written behind it on the axis waves' path it would wait for every load of theirs)
+            int r_pc = 0, r_piv = 1, r_wnv = 1, r_wvb = 0, r_wxb = 0;
+            long long f_iss = 0;
+            if (wave == 0) {
+                if (fst) { asm volatile("" :: "v"(call.x + fr.x0 + lane), "v"(fr.nT)); f_iss = (long long)wall_clock64(); }
+                if (lane < fr.nT) tau = call.x[fr.x0 + lane];
+            }
+            if (t < fr.N) { r_pc = l_pc[fr.p0 + t]; r_piv = l_piv[fr.p0 + t]; }
+            const int wq = t2 >= 0 ? (t2 >> 1) : fr.N;               // waypoint wq is the axis waves' pair t2 >> 1
+            if (wq < fr.N - 1) { const int gw = fr.wbase + wq; r_wnv = l_wnv[gw]; r_wvb = l_wvb[gw]; r_wxb = l_wxb[gw]; }
+            if (t2 >= 0 && t2 < 3) {
+                const gptr<const double> hd = l_head + c * 9, tl = l_tail + c * 9;     // (the candidate's base in scalar arithmetic)
+#pragma unroll
+                for (int q = 0; q < 3; q++) { r_bs[q] = hd[3 * q + t2]; r_bs[3 + q] = tl[3 * q + t2]; }
+            }
+            if (wave == 0 && fst) { asm volatile("" :: "v"(tau)); const long long f_in = (long long)wall_clock64(); if (lane == 0) { fst[0] = f_iss; fst[1] = f_in; } }
+            const KnotPre kpre{fr.p0, fr.N, fr.c0, fr.cN, fr.x0, fr.cv0, r_pc, r_piv, r_wnv, r_wvb, r_wxb, {r_bs[0], r_bs[1], r_bs[2], r_bs[3], r_bs[4], r_bs[5]}};
+            const EvalEarlySync<decltype(early), CH, true> es{early, est, wg == 0, nullptr, fr.nT, fr.nx, fr.nvd, ld.soft, ld.c2, l_vrec + 3 * (size_t)fr.cv0, tau};
+            forward_knot_body<false, 64, 5, 0, true>(a.dp, call.x, a.T, a.C, ld.maxCN, ld.maxXb, ld.maxVb, 64, nullptr, nsteps, c, ev, ctl, true, &ro, &kpre, nullptr, &es);
+            asm volatile("" : "+v"(tag_v));
+            tag = tag_v + 1u;
+            if (tag >= (1u << 28)) tag = 1u;
+        } else {
+        const EvalEarlySync<decltype(early), CH> es{early, est, wg == 0, fst, 0, 0, 0, 0, 0, nullptr, 0.0};
         forward_knot_body<false, 64, 5, 0, true>(a.dp, call.x, a.T, a.C, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, nsteps, c, ev, ctl, true, &ro, nullptr, nullptr, &es);
+        }
         if (bad) {                                                   // an earlier launch's wait expired (see above): uniform over the workgroup
             if (wg == 0 && t == 0) call.f[k] = __builtin_nan("");
             return;

@@ -136,6 +136,9 @@ template <> struct ho_chain<void> { static constexpr bool value = false; };
 // (the early-duration form's sync object, EvalEarlySync: ES::nostamps - no cycle stamps compiled into forward_knot_body)
 template <class ES> struct es_nostamps { static constexpr bool value = ES::nostamps; };
 template <> struct es_nostamps<void> { static constexpr bool value = false; };
+// (ES::front_held - the caller holds the candidate's counts, the time layer's switches, the vertex base and wave 0's tau, already requested: the early-duration block reads no table)
+template <class ES> struct es_front { static constexpr bool value = ES::front_held; };
+template <> struct es_front<void> { static constexpr bool value = false; };
 // Pinning a wave-uniform value in scalar registers: `asm volatile("" : "+s"(v), ...)` defines it anew, so the compiler may not re-load it at its uses, and ONE statement for a
 // group of values lets their loads go out together in front of it.  as_uniform: a uniform value that came through a vector load moves to a scalar register first (a no-op otherwise).
 // gptr: a pointer goes through such a statement as a pointer to GLOBAL memory by type - as a plain one it would come out with its address space unknown, and its stores as flat stores.
@@ -1396,14 +1399,22 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
     if constexpr (ET) {
         static_assert(NR == 64 && (MODE & 1), "early durations: the wave-specialised <= 64-piece path of a caller that stages");
         const int wave = __builtin_amdgcn_readfirstlane(k >> 6), kk = k & 63;
-        const int nT = dp.soft ? cN : cN - 1;                      // tau of this candidate: x[x0, x0 + nT)
-        const int nx = dp.xoff[b + 1] - x0;
-        const int v0 = dp.cvoff[b], nvd = 3 * (dp.cvoff[b + 1] - v0);
-        const double *vsrc = dp.vrec + 3 * (size_t)v0;
+        constexpr bool FH = es_front<ES>::value;
+        const int nT = [&]() -> int { if constexpr (FH) return es->nT; else return dp.soft ? cN : cN - 1; }();   // tau of this candidate: x[x0, x0 + nT)
+        const int nx = [&]() -> int { if constexpr (FH) return es->nx; else return dp.xoff[b + 1] - x0; }();
+        const int nvd = [&]() -> int { if constexpr (FH) return es->nvd; else return 3 * (dp.cvoff[b + 1] - dp.cvoff[b]); }();
+        const double *vsrc = [&]() -> const double * { if constexpr (FH) return (const double *)es->vsrc; else return dp.vrec + 3 * (size_t)dp.cvoff[b]; }();
+        const auto t_soft = [&]() -> int { if constexpr (FH) return es->soft; else return dp.soft; };
+        const auto t_c2 = [&]() -> int { if constexpr (FH) return es->c2; else return dp.c2; };
         constexpr int UX = 4, UV = 16, NA = 192;                   // the first staging trip of the three axis waves, held in registers across the early barrier
         double tau = 0.0, sx[UX], sv[UV];
         if (wave == 0) {
-            if (kk < nT) tau = x[x0 + kk];
+            // es->front (optional, the stamped instantiation): [0] every operand of the tau load is in its register - the load issues next, [1] tau is in its register
+            long long *fst = nullptr, f_iss = 0;
+            if constexpr (!es_nostamps<ES>::value && !FH) fst = es->front;
+            if (fst) { asm volatile("" :: "v"(x + x0 + kk), "v"(nT)); f_iss = (long long)wall_clock64(); }
+            if constexpr (!FH) { if (kk < nT) tau = x[x0 + kk]; }   // (FH: requested by the caller, in front of its other loads, and read from es below - a copy here would be written on the axis waves' path too, behind a wait for all of their loads)
+            if (fst) { asm volatile("" :: "v"(tau)); const long long f_in = (long long)wall_clock64(); if (kk == 0) { fst[0] = f_iss; fst[1] = f_in; } }
         } else {
 #pragma unroll
             for (int u = 0; u < UX; u++) { const int i = nT + t2 + u * NA; sx[u] = nx > 0 ? x[x0 + (i < nx ? i : nx - 1)] : 0.0; }
@@ -1414,13 +1425,14 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
         if (wave == 0) {
             // forwardT (CPU.hpp:626-676) and splitToFineT (CPU.hpp:930-944) inside the wave, the same expressions in the same order as below; LDS operations of one wave
             // complete in order, so lane 0 sees the other lanes' writes without a barrier
+            if constexpr (FH) tau = es->tau;
             if (kk < nT) xs[kk] = tau;                                // (the adjoint reads tau from ro->xs)
-            if (dp.soft) {
-                if (kk < cN) Tc[kk] = tau_to_T(tau, dp.c2 != 0);
+            if (t_soft()) {
+                if (kk < cN) Tc[kk] = tau_to_T(tau, t_c2() != 0);
             } else if (kk == 0) {
                 const int Ms1 = cN - 1;
                 double sum = 0.0;
-                for (int i = 0; i < Ms1; i++) Tc[i] = tau_to_T(xs[i], dp.c2 != 0);
+                for (int i = 0; i < Ms1; i++) Tc[i] = tau_to_T(xs[i], t_c2() != 0);
                 Tc[Ms1] = 0.0;
                 for (int i = 0; i <= Ms1; i++) sum += Tc[i];
                 const double den = 1.0 + sum;

@@ -61,6 +61,10 @@ int frx_debug_eval_fused(const frx_problem *p);
  * half-spaces, six reduction steps - the handle's geometry equals it exactly), 0 = the run-time form (any other geometry, FRX_EVAL_GEOM=0, or no one-launch form at all).
  * The two give the same bits. */
 int frx_debug_eval_geometry(const frx_problem *p);
+/* Which front the handle's one-launch form takes: 1 = two trips behind the entry (the candidate's front record and the argument block's leading lines, then every
+ * operand load of the front in one group), 0 = the front that walks the offset tables (FRX_EVAL_FRONT=0, a form without the argument pointer or early durations, or no
+ * one-launch form at all).  The two give the same bits. */
+int frx_debug_eval_front(const frx_problem *p);
 /* The solo form of an evaluation (one workgroup per candidate runs forward map, penalty integral and adjoint in ONE launch; batches larger than the clusters of the
  * one-launch form reach; the per-stage rounds of frx_optimize take it too).  mode 0 = never, 1 = from the handle's batch-size threshold on (default; FRX_EVAL_SOLO_MIN_B),
  * 2 = at every batch size, also where the cluster form would apply.  Results are bit-identical to the three stage launches (replaces the same objectiveFunc,
