@@ -14,7 +14,13 @@
 // jerk energy with respect to the free knot derivatives: symmetric positive definite, U_k = L_{k+1}^T.
 // It is solved by parallel cyclic reduction (one lane per knot, ceil(log2(N-1)) steps), which is
 // stable for SPD block-tridiagonal systems.  Same spline, same exact-arithmetic result as the
-// reference's LU; FP64 rounding differs at the 1e-13 level (tests compare with the oracle).
+// reference's LU.  FP64 rounding, measured against an exact (long-double, pivoted, refined) solve
+// for piece durations inside [0.02 s, 5 s] - the asserted contract: <= 1e-11 of the largest
+// duration-normalised coefficient |c_k| h^k, <= 5e-8 of max|c| raw (the t^4 / t^5 coefficients of a
+// short piece between long ones), f and each block of its gradient <= 1e-9; a piece 1000 times
+// shorter than its neighbours leaves that envelope (1e-9 normalised).  tests/test_minco_exact_cpu.py
+// (this header compiled for the host) and tests/test_gpu_minco_exact.py (every device form);
+// DESIGN.md 3.1 has the figures.
 //
 // Adjoint (replaces A^-T, addPropCtoT, addPropCtoP): with cbar = d f / d c,
 //   1. piece-local:   dbar = (dc/dd)^T cbar,  hbar_local = cbar . dc/dh          (d = knot data of the piece)
