@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "frx_trajectory_check", "frx_trajectory_check_device", "frx_trajectory_sample", "frx_trajectory_sample_device",
     "frx_trajectory_extrema", "frx_trajectory_extrema_device",
     "frx_gate_from_corners", "frx_trajectory_gates", "frx_trajectory_gates_device", "frx_gate_flags",
+    "frx_trajectory_contain", "frx_trajectory_contain_device", "frx_contain_fold",
     "frx_trajectory_clearance", "frx_trajectory_clearance_workspace", "frx_trajectory_clearance_device",
     "frx_corridor_generate_batch", "frx_corridor_generate_batch_device",
     "frx_enumerate_vertices_batch", "frx_enumerate_vertices_batch_device", "frx_corridor_slots_to_tasks_device",
@@ -90,6 +91,8 @@ EXTREMA_FIELDS = ("speed", "acc", "thrust_min", "thrust_max", "body_rate", "t_sp
 # frx_trajectory_gates (include/frx.h): fields of a gate's row and flag bits
 GATE_FIELDS = ("n_cross", "n_pass", "margin", "time", "piece", "u", "v", "reach_u", "reach_v", "normal_speed")
 GATE_FLAG_MISSED, GATE_FLAG_REPEAT, GATE_FLAG_ORDER, GATE_FLAG_NONFINITE = 1, 2, 4, 8
+# frx_trajectory_contain (include/frx.h): fields of a row; its flags are CHECK_FLAG_CORRIDOR and CHECK_FLAG_NONFINITE
+CONTAIN_FIELDS = ("n_contact", "outside", "t_exit", "t_enter", "k_exit", "centre", "t_centre", "k_centre")
 # frx_trajectory_clearance (include/frx.h): fields of a row, flag bits, the largest cloud; CLEAR_TILE sample states and CLEAR_PASS cloud points are what a
 # workgroup of the kernel holds at a time (fast-racing_amd/csrc/frx_device.hpp), the sizes at which it takes another turn of a loop
 CLEAR_FIELDS = ("ell", "dist", "worst_t", "worst_i")
@@ -182,6 +185,9 @@ def lib():
         L.frx_trajectory_gates.argtypes = [C.c_void_p] * 7
         L.frx_trajectory_gates_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_gate_flags.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_contain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_contain_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        L.frx_contain_fold.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_trajectory_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         L.frx_trajectory_sample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_trajectory_clearance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -559,6 +565,22 @@ def gate_flags(gate_rows, gate_off):
     return flags
 
 
+def contain_fold(piece_rows, T, piece_off):
+    """Candidate rows (B, 8) and CHECK_FLAG_* words (B,) uint32 from the piece rows (P, 8) of trajectory_contain_device (frx_contain_fold, host only):
+    candidate b owns the pieces piece_off[b] .. piece_off[b + 1] - 1.  A candidate without pieces keeps a row of zeros."""
+    piece_off = np.ascontiguousarray(piece_off, dtype=np.int32).reshape(-1)
+    rows = np.ascontiguousarray(piece_rows, dtype=np.float64).reshape(-1, len(CONTAIN_FIELDS))
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+    B = piece_off.size - 1
+    if B >= 1 and (rows.shape[0] < int(piece_off.max()) or T.size < int(piece_off.max())):
+        raise ValueError(f"contain_fold: {rows.shape[0]} rows and {T.size} durations for piece_off up to {int(piece_off.max())}")
+    cand = np.zeros((max(B, 0), len(CONTAIN_FIELDS))); flags = np.zeros(max(B, 0), np.uint32)
+    pad = np.zeros(1)
+    _check(lib().frx_contain_fold(B, piece_off.ctypes.data, (T if T.size else pad).ctypes.data, (rows if rows.size else pad).ctypes.data,
+                                  cand.ctypes.data, flags.ctypes.data))
+    return cand, flags
+
+
 def traj_to_msg(T, Cf):
     """PolynomialTrajectory array fields of one trajectory: (coef_x, coef_y, coef_z, time, order)."""
     n = len(T)
@@ -807,6 +829,18 @@ class Problem:
     def trajectory_extrema_device(self, T_ptr: int, C_ptr: int, out_ptr: int, stream: int = 0):
         """frx_trajectory_extrema_device: the piece rows (P x 10 doubles at out_ptr) as one launch on `stream`, device pointers, no synchronisation."""
         _check(lib().frx_trajectory_extrema_device(self.h, T_ptr, C_ptr, out_ptr, stream))
+
+    def trajectory_contain(self, T, Cf, slack: float = 0.0):
+        """Exact corridor containment certificate of the batch (T, C) (frx_trajectory_contain; nothing is sampled): every face pulled in by slack
+        (0: the face of the check's CORRIDOR, safe_margin: the face the penalty aims at).  dict(piece (P, 8), cand (B, 8), flags (B,) uint32 of
+        CHECK_FLAG_CORRIDOR / _NONFINITE) plus the candidate rows' fields by name (CONTAIN_FIELDS)."""
+        T, Cf = self._traj_TC("trajectory_contain", T, Cf)
+        return self._traj_folded(CONTAIN_FIELDS, "cand", lib().frx_trajectory_contain, T.ctypes.data, Cf.ctypes.data, float(slack))
+
+    def trajectory_contain_device(self, T_ptr: int, C_ptr: int, out_ptr: int, slack: float = 0.0, stream: int = 0):
+        """frx_trajectory_contain_device: the piece rows (P x 8 doubles at out_ptr) as one launch on `stream`, device pointers, no synchronisation;
+        contain_fold gives its callers the candidate rows and flags."""
+        _check(lib().frx_trajectory_contain_device(self.h, T_ptr, C_ptr, float(slack), out_ptr, stream))
 
     def trajectory_gates(self, T, Cf, gates, gate_off):
         """Exact gate passage certificate of the batch (T, C) (frx_trajectory_gates): gates (n_gates, 9) records {c, a, b}, candidate b owning the

@@ -236,6 +236,7 @@ struct frx_problem {
     PinBuf<double> h_x, h_f, h_g, h_T, h_C, h_out20;
     DevBuf<double> d_check;                                 // [P][8] rows of frx_trajectory_check, allocated on its first call
     DevBuf<double> d_extrema;                               // [P][10] rows of frx_trajectory_extrema, allocated on its first call
+    DevBuf<double> d_contain;                               // [P][8] rows of frx_trajectory_contain, allocated on its first call
     DevBuf<double> d_sample;                                // frx_trajectory_sample: [B][S][20] rows, then [B][S] times; grown as needed
     DevBuf<double> d_gates;                                 // frx_trajectory_gates: [n_gates][10] rows, the records [n_gates][9], then gate_off [B + 1] as ints; grown as needed
     DevBuf<double> d_clear;                                 // frx_trajectory_clearance: [P][4] rows, the cloud [n_obs][3], then the partials [P][chunks][4]; grown as needed
@@ -1060,8 +1061,8 @@ int frx_penalty_eval_device(frx_problem *p, const double *T_dev, const double *C
     return FRX_OK;
 }
 
-// The blocking entries that take (T, C) from the host - penalty, check, extrema, clearance, sample - run: argument checks, stage_TC ((T, C) -> d_T, d_C through the
-// pinned h_T, h_C), their _device entry on the handle's stream, fetch_rows, then a fold on the host (frx_traj_fold.hpp for the three that have candidate rows).
+// The blocking entries that take (T, C) from the host - penalty, check, extrema, contain, clearance, sample - run: argument checks, stage_TC ((T, C) -> d_T, d_C through the
+// pinned h_T, h_C), their _device entry on the handle's stream, fetch_rows, then a fold on the host (frx_traj_fold.hpp for the four that have candidate rows).
 static int stage_TC(frx_problem *p, const double *T, const double *C) {
     std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
     std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
@@ -1200,6 +1201,38 @@ int frx_trajectory_gates(frx_problem *p, const double *T, const double *C, const
     HIP_TRY(hipMemcpyAsync(gate_out, d_rows, sizeof(double) * n_rows, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     if (flags) frx::gate_flags(p->B, gate_off, gate_out, flags);
+    return FRX_OK;
+}
+
+int frx_contain_fold(int B, const int *piece_off, const double *T, const double *rows, double *cand_out, unsigned *flags) {
+    if (B < 1 || !piece_off || !T || !rows) return fail(FRX_ERR_INVALID_ARG, "frx_contain_fold: B must be >= 1 and piece_off, T, rows not NULL");
+    if (piece_off[0] < 0) return fail(FRX_ERR_INVALID_ARG, "frx_contain_fold: piece_off[0] must be >= 0");
+    for (int b = 0; b < B; b++)
+        if (piece_off[b + 1] < piece_off[b]) return fail(FRX_ERR_INVALID_ARG, "frx_contain_fold: piece_off must not fall (candidate " + std::to_string(b) + ")");
+    frx::fold_contain(B, piece_off, T, rows, cand_out, flags);
+    return FRX_OK;
+}
+
+int frx_trajectory_contain_device(frx_problem *p, const double *T_dev, const double *C_dev, double slack, double *piece_out_dev, void *hip_stream) {
+    static_assert(FRX_CONTAIN_FIELDS == (int)frx::CONTAIN_FIELDS && FRX_CONTAIN_FIELDS <= 20, "frx.h and frx_device.hpp agree, and the rows fit the P x 20 staging");
+    if (!p || !T_dev || !C_dev || !piece_out_dev) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (!std::isfinite(slack)) return fail(FRX_ERR_INVALID_ARG, "slack must be finite");
+    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    HIP_TRY((hipError_t)frx::launch_contain(p->dp, p->Kmax, slack, T_dev, C_dev, piece_out_dev, hip_stream));
+    return FRX_OK;
+}
+
+int frx_trajectory_contain(frx_problem *p, const double *T, const double *C, double slack, double *piece_out, double *cand_out, unsigned *flags) {
+    if (!p || !T || !C || !cand_out) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (!std::isfinite(slack)) return fail(FRX_ERR_INVALID_ARG, "slack must be finite");
+    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n_rows = (size_t)FRX_CONTAIN_FIELDS * p->P;
+    if (!p->d_contain.p) HIP_TRY(p->d_contain.alloc(n_rows));
+    FRX_TRY(stage_TC(p, T, C));
+    FRX_TRY(frx_trajectory_contain_device(p, p->d_T.p, p->d_C.p, slack, p->d_contain.p, p->stream));
+    FRX_TRY(fetch_rows(p, p->d_contain.p, n_rows, piece_out));
+    frx::fold_contain(p->B, p->poff.data(), T, p->h_out20.p, cand_out, flags);
     return FRX_OK;
 }
 

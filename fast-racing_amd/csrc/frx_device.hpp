@@ -123,6 +123,14 @@ enum { GATE_FIELDS = 10 };
 int launch_gates(int B, const int *poff, double g_acc, const double *ell, const double *T, const double *C, int n_gates, const int *gate_off,
                  const double *gates, double *out, void *stream);
 
+// ---- exact corridor containment certificate (frx_contain_kernel.hpp) ----
+enum { CONTAIN_FIELDS = 8 };
+// log2 of the lanes a piece's faces take: the smallest power of two >= Kmax, at most 64
+int contain_group_log2(int Kmax);
+// out: [P][8] (frx.h FRX_CONTAIN_*) of the pieces (T, C) against the handle's corridor blocks (dp.hblk, Kmax faces at most), every face pulled in by slack;
+// T / C / out are device pointers.  One launch, no dynamic LDS.
+int launch_contain(const DevProblem &dp, int Kmax, double slack, const double *T, const double *C, double *out, void *stream);
+
 // ---- batched sampling with SE(3) outputs (frx_sample_kernel.hpp) ----
 // 1 when candidates of up to maxN fine pieces fit the kernel's LDS
 int sample_fits(int maxN);

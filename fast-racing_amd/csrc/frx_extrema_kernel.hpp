@@ -21,7 +21,7 @@
 // Shape: one lane per (piece, task); a workgroup is one wave of 64 consecutive pieces, blockIdx.y the task, so the degrees are compile-time and lanes diverge on
 // the data alone (number of roots, bisection steps).  The vector polynomials live in registers (compile-time indices); the lists a lane indexes at run time -
 // the critical polynomial, the current level's coefficients, two root lists - live in LDS as [slot][lane] (conflict-free 8-byte accesses):
-// 14 + 14 + 13 + 13 slots x 512 B = 27 648 B static.  Every loop is bounded (degree, 200); no atomics, no barrier, no traffic between lanes.
+// 14 + 14 + 13 + 13 slots x 512 B = 27 648 B static (ExtLayout<13>; another kernel may give ext_roots_unit a larger layout).  Every loop is bounded (degree, 200); no atomics, no barrier, no traffic between lanes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +29,13 @@ namespace frx {
 
 enum { EXT_TASKS = 4, EXT_FIELDS = 10, EXT_MAXDEG = 13,
        EXT_TOP = 0, EXT_LVL = 14, EXT_RA = 28, EXT_RB = 41, EXT_SLOTS = 54 };   // first slot of each per-lane list in LDS
+
+// The per-lane lists of ext_roots_unit for polynomials of degree up to MAXDEG: TOP and LVL hold MAXDEG + 1 coefficients, the two root lists MAXDEG roots.
+// ExtLayout<13> is the layout above (extrema, gates); k_traj_contain runs degree 16 on ExtLayout<16> (frx_contain_kernel.hpp).
+template <int MAXDEG>
+struct ExtLayout { enum { TOP = 0, LVL = MAXDEG + 1, RA = 2 * (MAXDEG + 1), RB = 2 * (MAXDEG + 1) + MAXDEG, SLOTS = 2 * (MAXDEG + 1) + 2 * MAXDEG, CAP = MAXDEG }; };
+static_assert((int)ExtLayout<EXT_MAXDEG>::LVL == (int)EXT_LVL && (int)ExtLayout<EXT_MAXDEG>::RA == (int)EXT_RA && (int)ExtLayout<EXT_MAXDEG>::RB == (int)EXT_RB &&
+              (int)ExtLayout<EXT_MAXDEG>::SLOTS == (int)EXT_SLOTS, "the default layout is the one the extrema and gates kernels were pinned on");
 
 // polynomial in LDS, highest power first, degree deg, at x
 __device__ __forceinline__ double ext_horner(const double *c, int deg, double x) {
@@ -38,11 +45,13 @@ __device__ __forceinline__ double ext_horner(const double *c, int deg, double x)
     return v;
 }
 
-// All sign-change roots on [0, 1], ascending, of the polynomial in lds[EXT_TOP ..] (highest power first, degree DEG before its leading zeros are
-// stripped).  lds points at this lane's column; slot s is lds[64 s].  Returns the count; *roots is the list's first slot (EXT_RA or EXT_RB).
-template <int DEG>
+// All sign-change roots on [0, 1], ascending, of the polynomial in lds[LAY::TOP ..] (highest power first, degree DEG before its leading zeros are
+// stripped).  lds points at this lane's column; slot s is lds[64 s].  Returns the count; *roots is the list's first slot (LAY::RA or LAY::RB).
+template <int DEG, class LAY = ExtLayout<EXT_MAXDEG>>
 __device__ __forceinline__ int ext_roots_unit(double *lds, int *roots) {
 #pragma clang fp contract(off)
+    static_assert(DEG <= (int)LAY::CAP, "the layout holds the polynomial");
+    enum { EXT_TOP = LAY::TOP, EXT_LVL = LAY::LVL, EXT_RA = LAY::RA, EXT_RB = LAY::RB };   // (the names of the default layout, for this one)
     int s0 = 0, deg = DEG;
     while (deg > 0 && lds[64 * (EXT_TOP + s0)] == 0.0) { s0++; deg--; }
     *roots = EXT_RA;
@@ -83,7 +92,7 @@ __device__ __forceinline__ int ext_roots_unit(double *lds, int *roots) {
                 }
                 r = 0.5 * (a + b);
             }
-            if (n < EXT_MAXDEG) out[64 * n++] = r;                       // (at most one root an interval, m intervals at most: n <= m always)
+            if (n < (int)LAY::CAP) out[64 * n++] = r;                      // (at most one root an interval, m intervals at most: n <= m always)
         }
         ncrit = n;
         const int t = cur; cur = oth; oth = t;

@@ -1,5 +1,5 @@
-// Piece rows -> candidate rows and flag words of frx_trajectory_check / _extrema / _clearance (include/frx.h documents the rows).  Plain C++: no HIP and
-// no handle, so the blocking entries (frx_api.cpp), frx_debug_fold_rows and a host-only program share this one implementation.
+// Piece rows -> candidate rows and flag words of frx_trajectory_check / _extrema / _clearance / _contain (include/frx.h documents the rows).  Plain C++: no HIP
+// and no handle, so the blocking entries (frx_api.cpp), frx_debug_fold_rows, frx_contain_fold and a host-only program share this one implementation.
 //
 // One shape: the candidates b = 0..B-1 own the pieces poff[b]..poff[b+1]-1 of T[] and of rows[] (piece rows, FIELDS doubles each), folded in piece order;
 // a time is counted from the candidate's start on the prefix of durations summed left to right.  limits = {vel_max, thr_acc_min, thr_acc_max,
@@ -75,6 +75,29 @@ inline void fold_clearance(int B, const int *poff, const double *T, const double
             o[FRX_CLEAR_DIST] = k == 0 ? r[FRX_CLEAR_DIST] : nan_min(o[FRX_CLEAR_DIST], r[FRX_CLEAR_DIST]);
         },
         [](const double *o) { return o[FRX_CLEAR_ELL] < 1.0 ? FRX_CLEAR_FLAG_COLLISION : 0u; });
+}
+
+// contain: N_CONTACT summed; OUTSIDE and CENTRE maxima in piece order (strict > replaces, a value that is not a number takes the field and stays); the
+// T_EXIT group from the first piece whose T_EXIT is not -1 (an excursion, or a row that is not a number); K_EXIT and K_CENTRE become the local piece index
+inline void fold_contain(int B, const int *poff, const double *T, const double *rows, double *cand_out, unsigned *flags) {
+    fold_rows<FRX_CONTAIN_FIELDS>(B, poff, T, rows, cand_out, flags, FRX_CHECK_FLAG_NONFINITE,
+        [](double *o, const double *r, int k, double t0) {
+            o[FRX_CONTAIN_N_CONTACT] = k == 0 ? r[FRX_CONTAIN_N_CONTACT] : o[FRX_CONTAIN_N_CONTACT] + r[FRX_CONTAIN_N_CONTACT];
+            const double a = o[FRX_CONTAIN_OUTSIDE], c = r[FRX_CONTAIN_OUTSIDE];
+            if (k == 0 || (a == a && (c > a || c != c))) o[FRX_CONTAIN_OUTSIDE] = c;
+            if (k == 0) { o[FRX_CONTAIN_T_EXIT] = -1.0; o[FRX_CONTAIN_T_ENTER] = -1.0; o[FRX_CONTAIN_K_EXIT] = -1.0; }
+            if (o[FRX_CONTAIN_T_EXIT] == -1.0 && r[FRX_CONTAIN_T_EXIT] != -1.0) {
+                o[FRX_CONTAIN_T_EXIT] = t0 + r[FRX_CONTAIN_T_EXIT]; o[FRX_CONTAIN_T_ENTER] = t0 + r[FRX_CONTAIN_T_ENTER]; o[FRX_CONTAIN_K_EXIT] = (double)k;
+            }
+            const double a2 = o[FRX_CONTAIN_CENTRE], c2 = r[FRX_CONTAIN_CENTRE];
+            if (k == 0 || (a2 == a2 && (c2 > a2 || c2 != c2))) {
+                o[FRX_CONTAIN_CENTRE] = c2; o[FRX_CONTAIN_T_CENTRE] = t0 + r[FRX_CONTAIN_T_CENTRE]; o[FRX_CONTAIN_K_CENTRE] = (double)k;
+            }
+        },
+        [](const double *o) { return o[FRX_CONTAIN_T_EXIT] >= 0.0 ? FRX_CHECK_FLAG_CORRIDOR : 0u; });
+    if (!flags) return;
+    for (int b = 0; b < B; b++)
+        if (poff[b + 1] == poff[b]) flags[b] = 0u;                       // (a row nobody wrote says nothing: T_EXIT = 0 in it is no excursion)
 }
 
 } // namespace frx

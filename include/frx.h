@@ -420,6 +420,60 @@ int frx_trajectory_gates_device(frx_problem *p, const double *T_dev, const doubl
                                 const double *gates_dev, double *gate_out_dev, void *hip_stream);
 int frx_gate_flags(int B, const int *gate_off, const double *gate_rows, unsigned *flags);
 
+/* Exact corridor containment certificate of a batch of results, on the device.  frx_trajectory_check samples the corridor at M + 1 nodes per piece: a
+ * body that pokes past a face between two nodes is reported as inside.  The reference never checks the corridor it optimises against at all.  These
+ * entries decide, for every piece and every face of its polytope, at which instants the body ellipsoid touches the face and during which intervals it
+ * is past it - nothing is sampled.
+ * The body is E = diag(eh, eh, ev) (horiz_half_len twice, vert_half_len), the face normals are unit vectors and [xB yB zB] is orthonormal, so
+ *   |E R^T n|^2 = eh^2 + Delta (zB.n)^2,   Delta = ev^2 - eh^2,   zB = h / |h|,   h = a + g e3.
+ * With d(tau) = n.(p - p_k) + slack (quintic), Q = h.h (degree 6) and u = n.h (cubic) the signed reach sd = d + |E R^T n| is zero exactly where
+ *   F(tau) = (d^2 - eh^2) Q - Delta u^2 = 0   and   d(tau) <= 0                                  (degree 16)
+ * (a root of F with d > 0 belongs to the far side of the ellipsoid and is dropped).  slack pulls every face in by that much: 0 is the face of
+ * FRX_CHECK_CORRIDOR, cfg.safe_margin the face the penalty aims at.  The roots are found as frx_trajectory_extrema finds roots (every sign change on
+ * [0, 1] in normalised time, bracketed by the derivative's roots and bisected down to adjacent doubles).
+ * Per face: a face with max d + max(eh, ev) < 0 is skipped (the body cannot reach it: no contact).  Otherwise the contacts in ascending order; an exact
+ * root at tau == 0 is dropped unless the piece is its candidate's first (a knot on a contact counts once, for the earlier piece).  Each interval of
+ * {0, contacts.., 1} is classed by sd at its midpoint with the direct formula; sd > 0, or a value that is not a number, is OUTSIDE.  The face's outside
+ * time is the left-to-right sum of its outside intervals, times T.
+ * Fields of a piece's row (FRX_CONTAIN_FIELDS doubles, times local in [0, T]):
+ *   FRX_CONTAIN_N_CONTACT   contact instants, summed over the piece's faces (an exact integer)
+ *   FRX_CONTAIN_OUTSIDE     the longest total time the body spends past one face, as a maximum over faces; 0: certified inside at every instant
+ *   FRX_CONTAIN_T_EXIT, _T_ENTER, _K_EXIT   start and end of the earliest interval during which the body is past some face, and that face (the lowest
+ *                           k on a tie); T_ENTER = T when the body is still out at the piece's end; all three -1 when there is no such interval
+ *   FRX_CONTAIN_CENTRE, _T_CENTRE, _K_CENTRE   the exact maximum over faces and time of d, WITHOUT the reach, from the roots of the quartic d' and the
+ *                           two ends (candidate order and ties as frx_trajectory_extrema; over faces the larger value, then the lower k).  It gives
+ *                           the rigorous enclosure CENTRE + min(eh, ev) <= max sd <= CENTRE + max(eh, ev).
+ * T not finite or <= 0, or a coefficient not finite: all eight NaN.  A row depends on its piece's own T, C, faces, g, eh, ev and slack and on whether
+ * the piece is its candidate's first; rows are bit-identical run to run, between the forms, and whatever else is in the batch.
+ * Candidate rows: N_CONTACT summed; OUTSIDE and CENTRE maxima in piece order (strict > replaces, a NaN takes the field and stays); the T_EXIT group
+ * from the first piece that has one (or whose row is NaN); times from the candidate's start on the durations summed left to right; K_EXIT and
+ * K_CENTRE hold the LOCAL PIECE index, as WORST_K's companion does in the check's candidate rows.  Flags: FRX_CHECK_FLAG_CORRIDOR when T_EXIT >= 0,
+ * FRX_CHECK_FLAG_NONFINITE when a field of the candidate's row is not finite.
+ * What the certificate is NOT.  The instants are exact, the depth of an excursion is not: CENTRE encloses max sd only to within |eh - ev|.  A contact
+ * at which sd touches zero without changing sign may go uncounted (the intervals on both sides are classed the same, so OUTSIDE and T_EXIT are
+ * unaffected).  h = 0 (free fall) leaves the attitude undefined: sd is not a number there and counts as outside.
+ *   frx_trajectory_contain         blocking, host pointers (T[total fine pieces], C[total fine pieces x 18]); piece_out (pieces x 8) and flags (B)
+ *                                  may be NULL, cand_out (B x 8) not.
+ *   frx_trajectory_contain_device  ONE launch on the caller's stream, device pointers: no copy, no synchronisation, no allocation (capturable in a
+ *                                  hipGraph); piece_out_dev (pieces x 8).
+ *   frx_contain_fold               host only, no handle: candidate rows and flags from piece rows (for callers of the _device form); candidate b
+ *                                  owns the pieces piece_off[b] .. piece_off[b + 1] - 1; cand_out and flags may each be NULL.
+ *                                  A candidate without pieces leaves its row as it is and gets no flags.
+ * FRX_ERR_INVALID_ARG, reported before a device is looked for: NULL arguments (the optional outputs excepted), a slack that is not finite, B < 1 or a
+ * falling piece_off (frx_contain_fold).  FRX_ERR_NO_DEVICE without a device.  Serves both kinds of handle. */
+#define FRX_CONTAIN_FIELDS 8
+#define FRX_CONTAIN_N_CONTACT 0
+#define FRX_CONTAIN_OUTSIDE 1
+#define FRX_CONTAIN_T_EXIT 2
+#define FRX_CONTAIN_T_ENTER 3
+#define FRX_CONTAIN_K_EXIT 4
+#define FRX_CONTAIN_CENTRE 5
+#define FRX_CONTAIN_T_CENTRE 6
+#define FRX_CONTAIN_K_CENTRE 7
+int frx_trajectory_contain(frx_problem *p, const double *T, const double *C, double slack, double *piece_out, double *cand_out, unsigned *flags);
+int frx_trajectory_contain_device(frx_problem *p, const double *T_dev, const double *C_dev, double slack, double *piece_out_dev, void *hip_stream);
+int frx_contain_fold(int B, const int *piece_off, const double *T, const double *rows, double *cand_out, unsigned *flags);
+
 /* Batched sampling of results with their SE(3) outputs, on the device.  The reference's traj_server evaluates one PolynomialTrajectory message at
  * control rate (traj_server.cpp:397-456: position, velocity, acceleration, jerk) and its controller derives attitude and thrust from the
  * acceleration; frx_msg_sample is that call for one time.  These entries sample every candidate of the handle's batch at S = n_samples times
