@@ -1780,11 +1780,12 @@ FRX_KERNEL_LINKAGE __global__ __launch_bounds__(256) void k_forward_knot64(DevPr
 // orders one straight-line body itself).  The resident form below - the partial-independent work hoisted in front of the poll by hand - measured 0.4 us
 // SLOWER as a stage kernel (8.00 against 7.62 us, build against build on one box, round 5), so each caller keeps the order that suits it; the arithmetic
 // is expression for expression the same.
-template <bool SH, int RB = 0>
+template <int RB = 0>
 __device__ __forceinline__ void backward_knot_wsp64_stage(const DevProblem &dp, const double *__restrict__ x, const double *__restrict__ Tin,
                                 const double *__restrict__ Cin, const double *__restrict__ out20, double *__restrict__ f,
                                 double *__restrict__ g, int maxCN, int maxXb, int maxVb, const double *__restrict__ pcrw, int nsteps,
                                 const LineSearchTap &tap, int b, double *sm, const double *ct_lds, const ResidentOps *ro) {
+    constexpr bool SH = false;                          // its callers are the stage kernels and k_eval_solo: T, C and the partials come from earlier launches or phases - plain loads and stores
     const int nrow = 64, nthr = 256;
     const int k = threadIdx.x, kk = k & 63, t2 = k - 64;
     const int wave = __builtin_amdgcn_readfirstlane(k >> 6);
@@ -1828,7 +1829,7 @@ __device__ __forceinline__ void backward_knot_wsp64_stage(const DevProblem &dp, 
         const double *ci = Cin + (size_t)(p0 + kp) * 18;
         const double *o = out20 + (size_t)(p0 + kp) * 20;
         h = ct_lds ? ct_lds[kp * 19 + 18] : ldg<SH>(Tin + p0 + kp);
-        const bool o_ll = SH && ro && ro->o20ll;                             // resident caller: the penalty partials arrive as granules (rk_ll_put in penalty_reduce), polled below
+        const bool o_ll = SH && ro && ro->o20ll;                             // (always false here - SH - and folded away: kept so that this block stays, token for token, the resident form's, until the two share one copy)
         if (wave == 0) {
             if (!o_ll) { o0 = ldg<SH>(o); o1 = ldg<SH>(o + 1); }
             // (the coarse-interval table of mergeToCoarseGradT too: loaded behind the barrier below, these two sat BEHIND the resident
@@ -1846,39 +1847,6 @@ __device__ __forceinline__ void backward_knot_wsp64_stage(const DevProblem &dp, 
                 r_wnv = dp.wp_nv[gw]; r_wvb = dp.wp_vbeg[gw]; r_wxb = dp.wp_xbeg[gw];
                 if (!ro && dp.wq_glob) { const double2 *wq = (const double2 *)(dp.wq_glob + 4 * (size_t)gw); r_wq0 = wq[0]; r_wq1 = wq[1]; }
             }
-        }
-    }
-    if (SH && ro && ro->o20ll) {
-        // Resident caller: the 20 partials of piece kp arrive as granules tagged with the number of this evaluation; lane kk of wave 0 polls {cost, d/dT},
-        // lane kk of an axis wave its six d/dc - the workgroups that integrate the penalty neither drain nor count in front of this read, and the leader
-        // does not wait for them before it calls this body.  Bounded: an expired wait records RK_ERR_ARRIVE (4) in the launch's status word.
-        const ll_u64 *og = ro->o20ll + 40 * (size_t)(p0 + kp);
-        const unsigned tg = ro->o20tag;
-        const ll_u64 t_end = (ll_u64)wall_clock64() + ro->spin_ticks;
-        constexpr int NG = 6;
-        ll_u64 w[NG][2];
-        const int ng = wave == 0 ? 2 : 6, gbase = wave == 0 ? 0 : 2 + (wave - 1), gstep = wave == 0 ? 1 : 3;
-        for (unsigned spins = 0;; spins++) {
-#pragma unroll
-            for (int q = 0; q < NG; q++) {
-                const ll_u64 *g2 = og + 2 * (gbase + gstep * (q < ng ? q : ng - 1));
-                w[q][0] = __hip_atomic_load(g2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); w[q][1] = __hip_atomic_load(g2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            bool all = true;
-#pragma unroll
-            for (int q = 0; q < NG; q++) all = all && rk_ll_ok(w[q][0], w[q][1], tg);
-            if (all) break;
-            if ((spins & 31u) == 31u && (__hip_atomic_load(ro->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || (ll_u64)wall_clock64() > t_end)) {
-                unsigned expect = 0u;
-                __hip_atomic_compare_exchange_strong(ro->status, &expect, 4u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (wave == 0) { o0 = rk_ll_value(w[0][0], w[0][1]); o1 = rk_ll_value(w[1][0], w[1][1]); }
-        else {
-#pragma unroll
-            for (int q = 0; q < 6; q++) cbq[q] = rk_ll_value(w[q][0], w[q][1]);
         }
     }
     if (!ro) {
@@ -2668,7 +2636,7 @@ __device__ __forceinline__ void backward_knot_body(const DevProblem &dp, const d
     const int nrow = NR > 0 ? NR : nrow_rt;
     if (NR == 64 || (NR == 0 && nrow == 64 && blockDim.x == 256)) {              // <= 64 pieces: one wave per axis
         if (SH) backward_knot_wsp64<SH, TL, HO>(dp, x, Tin, Cin, out20, f, g, maxCN, maxXb, maxVb, pcrw, nsteps, tap, b, sm, ct_lds, ro, tl, ho);       // resident caller: the order built around the poll
-        else backward_knot_wsp64_stage<SH, RB>(dp, x, Tin, Cin, out20, f, g, maxCN, maxXb, maxVb, pcrw, nsteps, tap, b, sm, ct_lds, ro);
+        else backward_knot_wsp64_stage<RB>(dp, x, Tin, Cin, out20, f, g, maxCN, maxXb, maxVb, pcrw, nsteps, tap, b, sm, ct_lds, ro);
         return;
     }
     if (NR == 64) return;
