@@ -465,6 +465,9 @@ enum {
     DV_TRIAL = 8,            // x = xp + step * d                                                   (lbfgs.hpp:825-826)
     DV_RESTORE = 16          // x = xp, g = gp: line search failed for good                         (lbfgs.hpp:1287-1288)
 };
+enum { DV_QUIT = 128, DV_STEP_IS_ONE = 64, DV_NEXT = 32 };   // extra command flags of the resident kernel (frx_round_kernel.hpp; the ones above are < 32); the second one lets
+                                               // the leader confirm a predicted command from the command WORD alone (no second read over PCIe); DV_NEXT: this
+                                               // candidate is finished, the cluster takes candidate slot | bound << 12 of the batch (work queue, see k_round)
 struct DvResult {            // device -> host
     double f;                // objective at the trial point
     double dg;               // g . d          (lbfgs.hpp:830)

@@ -54,9 +54,7 @@ typedef volatile __attribute__((address_space(3))) unsigned *rk_ldsword;
 
 enum { PH_ADV = 1, PH_CT = 2, PH_QUIT = 3, PH_INIT = 4, PH_NEXT = 5 };
 enum { RK_OK = 0, RK_ERR_CENSUS = 1, RK_ERR_HOST = 2, RK_ERR_PHASE = 3, RK_ERR_ARRIVE = 4, RK_ERR_DENSE = 5, RK_ERR_UFLAG = 6, RK_ERR_HOST_ABORT = 7, RK_ERR_SPECULATION = 8 };
-enum { DV_QUIT = 128, DV_STEP_IS_ONE = 64, DV_NEXT = 32 };   // extra command flags of the resident kernel (frx_lbfgs.hpp: DV_* are < 32); the second one lets
-                                               // the leader confirm a predicted command from the command WORD alone (no second read over PCIe); DV_NEXT: this
-                                               // candidate is finished, the cluster takes candidate slot | bound << 12 of the batch (work queue, see k_round)
+// (DV_QUIT, DV_STEP_IS_ONE, DV_NEXT - the extra command flags of this kernel - stand beside the other DV_* in frx_lbfgs.hpp, where the host sees them too)
 
 // host -> device: word = seq << 32 | bound << 20 | slot << 8 | flags (written last); step first.  device -> host: seq written last.
 struct RoundCmd { rk_u64 word; double step; };                          // cluster k's command is h_cmd[k * cmd_stride] (cmd_stride 4: one cache line per cluster)

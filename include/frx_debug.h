@@ -113,13 +113,13 @@ int frx_debug_dv_round(int device, int B, int m, const int *geom4, int hs, const
  * ns[9][2][8], f1/f2[9][2][2]; graph_search.h:72-127), generated from rules instead of spelled out; for the parity test. */
 int frx_jps_tables(int *ns3, int *f13, int *f23, int *ns2, int *f12, int *f22);
 
-/* Host CPU budget of a resident plan (frx_api.cpp, host_cpu_share): *budget = CPUs this process may use (affinity mask, cut by the cgroup quota cpu.max);
+/* Host CPU budget of a resident plan (frx_host_cpus.cpp, host_cpu_share): *budget = CPUs this process may use (affinity mask, cut by the cgroup quota cpu.max);
  * *share = this plan's part of them when LOCAL_WORLD_SIZE ranks of a node (FRX_LOCAL_RANKS overrides) and `extra_plans` further plans of this process
  * (the other shards of a frx_multi job) spin next to it; *mailbox_threads = the service threads a resident plan of `clusters` clusters would start
  * (the caller included): min(one per sixteen clusters, at most four; share - 1), at least one.  FRX_HOST_CPUS overrides the budget (tests). */
 int frx_debug_host_cpu_share(int clusters, int extra_plans, double *budget, int *share, int *mailbox_threads);
 
-/* Take-over (frx_api.cpp, TakeOver): a batch too large for the resident round kernel runs as per-stage rounds until no more candidates are left than the chip has
+/* Take-over (frx_optimize.cpp, TakeOver): a batch too large for the resident round kernel runs as per-stage rounds until no more candidates are left than the chip has
  * clusters for; those continue on the resident kernel with their history as it stands.  frx_debug_taken_over: how many candidates of the last plan finished
  * that way (0: none).  frx_debug_compact_from_history: the host code that rebuilds the resident kernel's dense state for such a candidate - R^-1 by slot
  * ([128][129]), Y^T Y ([128][128]), D = diag(s.y) ([128]) - from history rows S, Y [m][hs] (n significant doubles per row), `bound` valid pairs, the newest

@@ -310,3 +310,24 @@ extern "C" void hostcheck_lds_limits(int n, const int *dev, const int *fn, const
         rc[i] = limits.raise(dev[i], &fns[fn[i] & 7], (size_t)bytes[i], [&](const void *f, size_t b) { called[i] = f == &fns[fn[i] & 7] ? (long long)b : -1; return fail[i] ? 1 : 0; });
     }
 }
+
+// ---- the resident plan's geometry and command word (fast-racing_amd/csrc/frx_resident_plan.hpp), for tests/test_resident_plan_cpu.py ----
+#include "../../fast-racing_amd/csrc/frx_resident_plan.hpp"
+// n rows of 20 ints: solver, knot_threads, m, B, Bsel, min_n, maxXb, maxN, ppw, cus, resident_mode, takeover, dv_mem, have_history, then the knobs as ResidentKnobs holds
+// them: e, g, clusters_set, clusters, queue, queue_max.  out: n rows of {applicable, E, G, S, NXP, n_words, queue}
+extern "C" void hostcheck_resident_plan_rows(long long n, const int *rows, long long *out) {
+    for (long long i = 0; i < n; i++) {
+        const int *r = rows + 20 * i;
+        frx::ResidentKnobs kn;
+        kn.e = r[14]; kn.g = r[15]; kn.clusters_set = r[16] != 0; kn.clusters = r[17]; kn.queue = r[18]; kn.queue_max = r[19];
+        const frx::ResidentPlan pl = frx::resident_plan({r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10], r[11] != 0, r[12], r[13] != 0}, kn);
+        long long *o = out + 7 * i;
+        o[0] = pl.applicable; o[1] = pl.E; o[2] = pl.G; o[3] = pl.S; o[4] = pl.NXP; o[5] = (long long)pl.n_words; o[6] = pl.queue;
+    }
+}
+extern "C" int hostcheck_resident_capacity(int maxXb, int cus) { return frx::resident_capacity(maxXb, cus); }
+extern "C" unsigned long long hostcheck_round_command_word(unsigned long long seq, int flags, int slot, int bound, double step) { return frx::round_command_word(seq, flags, slot, bound, step); }
+
+// ---- the mailbox protocol against a thread that plays the clusters (resident_mailbox_main.cpp), for tests/test_resident_mailbox_cpu.py ----
+#define HOSTCHECK_LIBRARY
+#include "resident_mailbox_main.cpp"

@@ -63,7 +63,7 @@ def test_a_failed_candidate_never_wins(frx, sc):
 def test_config3_whole_eight_shards_on_one_device(frx, sc):
     """BASELINE.json configs[3] WHOLE: 256 perturbed candidates block-partitioned into eight shards of 32 - the shape of an 8-GPU node -
     with every shard on device 0 (the box has one GPU; the in-process communicator stands in for RCCL, which refuses a device twice).
-    The eight resident launches take turns on the device (one resident grid per device at a time, csrc/frx_api.cpp), so every shard's
+    The eight resident launches take turns on the device (one resident grid per device at a time, csrc/frx_optimize.cpp), so every shard's
     plan is bit-identical to the same 32 candidates on a handle of their own, and the winner is the argmin over all 256."""
     B, N, gates, kappa = sc.CONFIGS["perturbed256"]
     assert B == 256

@@ -240,7 +240,7 @@ def test_batches_larger_than_the_chip_take_the_work_queue_and_small_problems_the
     assert s["resident"] == 0 and np.array_equal(s["status"], r["status"]) and np.array_equal(s["evals"], r["evals"])
     assert np.max(np.abs(s["objective"] - r["objective"]) / np.abs(s["objective"])) < 1e-6
     prob.close()
-    # fewer variables than twice the history length: the compact representation would invert an ill-conditioned R (frx_api.cpp)
+    # fewer variables than twice the history length: the compact representation would invert an ill-conditioned R (frx_resident_plan.hpp)
     small = frx.Problem(sc.make_batch(2, 2, 5, 1), sc.ZHANGJIAJIE, qd_intervals=8)
     r = small.optimize(1e-6)
     assert r["resident"] == 0 and np.all(r["status"] >= 0)
