@@ -19,6 +19,7 @@
 #include "../../include/frx_debug.h"
 #include "frx_handle.hpp"
 #include "frx_launch_forms.hpp"
+#include "frx_problem_tables.hpp"
 #include "frx_host_pool.hpp"
 #include "frx_compact.hpp"
 #include "frx_traj_fold.hpp"
@@ -88,6 +89,170 @@ int eval_cluster_status(frx_problem *p, const double *f) {
 using frx::launch_eval;
 using frx::eval_cluster_status;
 
+// ---- the steps of frx_problem_create, in the order it takes them ----
+namespace {
+
+// The handle while create builds it: every early return destroys its stream and deletes it (a finished handle leaves through frx_problem_destroy, which
+// synchronises the stream first).
+struct HandleOwner {
+    frx_problem *p;
+    explicit HandleOwner(frx_problem *q) : p(q) {}
+    HandleOwner(const HandleOwner &) = delete;
+    HandleOwner &operator=(const HandleOwner &) = delete;
+    ~HandleOwner() {
+        if (!p) return;
+        if (p->stream) (void)hipStreamDestroy(p->stream);
+        delete p;
+    }
+    frx_problem *release() { frx_problem *q = p; p = nullptr; return q; }
+};
+
+// the one place create reads the environment
+frx::CreateSwitches create_switches_from_env() {
+    frx::CreateSwitches s;
+    if (const char *e = std::getenv("FRX_PENALTY_WAVES")) s.penalty_waves = std::atoi(e);
+    if (const char *e = std::getenv("FRX_EVAL_FUSED")) s.eval_fused = e[0];
+    if (const char *e = std::getenv("FRX_LOCAL_RANKS")) s.local_ranks = std::max(1, std::atoi(e));
+    else if (const char *e2 = std::getenv("LOCAL_WORLD_SIZE")) s.local_ranks = std::max(1, std::atoi(e2));
+    if (const char *e = std::getenv("FRX_EVAL_SOLO")) s.eval_solo = e[0];
+    if (const char *e = std::getenv("FRX_EVAL_SOLO_MIN_B")) s.solo_min_B = std::atoi(e);
+    if (const char *e = std::getenv("FRX_EVAL_SOLO_MAX_B")) s.solo_max_B = std::atoi(e);
+    if (const char *e = std::getenv("FRX_EVAL_TIMEOUT_MS")) s.eval_timeout_ms = std::atof(e);
+    s.setup_timing = std::getenv("FRX_SETUP_TIMING") != nullptr;
+    return s;
+}
+
+int create_hip_error(hipError_t e, const char *step) {
+    return fail(e == hipErrorOutOfMemory ? FRX_ERR_ALLOC : FRX_ERR_HIP, std::string(step) + ": " + hipGetErrorString(e));
+}
+
+// the host description of every candidate and the descriptor tables (frx_problem_tables.hpp)
+int create_tables(frx_problem *p, const int *coarse_n, const double *ini_state, const double *fin_state, const int *h_off, const double *h_rec, const int *v_off,
+                  const double *v_rec, frx::ProblemTables &tb) {
+    frx::TablesRefusal why;
+    const int rc = frx::problem_tables_fill(p->cfg, p->softT, p->B, coarse_n, ini_state, fin_state, h_off, h_rec, v_off, v_rec, p->cand, tb, &why);
+    switch (why) {
+    case frx::TABLES_COARSE_N: return fail(rc, "coarse_n[b] < 1");
+    case frx::TABLES_NO_VERTICES: return fail(rc, "a corridor polytope has no vertices");
+    case frx::TABLES_NO_HALFSPACES: return fail(rc, "an H-polytope has no half-spaces");
+    case frx::TABLES_OK: break;
+    }
+    return FRX_OK;
+}
+
+// launch geometry + LDS budgets, the forms of the evaluation this handle takes, and the refusals of what does not fit
+int create_geometry(frx_problem *p, const frx::ProblemTables &tb, const frx::CreateSwitches &sw, int ndev) {
+    int cus = 256;
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, p->device) == hipSuccess) cus = prop.multiProcessorCount; }
+    frx::LaunchGeom &ge = p->geo;
+    frx::launch_geometry_fill(ge, tb, p->cfg.qd_intervals, 4 * cus, sw.penalty_waves);
+    if (!frx::eval_cluster_admitted(frx::eval_cluster_geometry(ge), p->B, cus, sw.eval_fused, sw.local_ranks, ndev)) { ge.ev_G = 0; ge.lds_ev = 0; }
+    p->eval_fused_G = ge.ev_G; p->eval_fused = ge.ev_G ? 1 : 0;
+    if (sw.eval_timeout_ms > 0.0) p->eval_fused_ticks = (unsigned long long)(sw.eval_timeout_ms * 1e5);
+    frx::eval_solo_geometry(ge, p->cfg.qd_intervals + 1);
+    const frx::SoloChoice solo = frx::eval_solo_choice(ge.lds_solo != 0, sw.eval_solo, sw.solo_min_B, sw.solo_max_B);
+    p->eval_solo = solo.eval_solo; p->eval_solo_min_B = solo.min_B; p->eval_solo_max_B = solo.max_B;
+    const frx::GeomVerdict v = frx::geometry_verdict(ge.knot_threads, ge.lds_kbwd, ge.lds_fwd, ge.lds_bwd, ge.lds_pen);
+    if (v.refusal == frx::GEOM_KNOT_CAPACITY)
+        return fail(FRX_ERR_CAPACITY, "a candidate's knot system does not fit one workgroup: " + std::to_string(ge.lds_kbwd / 1024) + " KB of LDS needed, 160 KB available (" +
+                                          std::to_string(ge.knot_threads) + " knot threads, limit 256; about 128 pieces per candidate fit; the reference caps at 100, cuda_computer.cuh:24)");
+    if (v.refusal == frx::GEOM_PENALTY_CAPACITY)
+        return fail(FRX_ERR_CAPACITY, "piece count / half-space count too large for the LDS-resident kernels (160 KiB per CU)");
+    p->banded_ok = v.banded_ok;
+    if (!p->banded_ok) { ge.lds_fwd = ge.lds_bwd = 1024; }          // "unavailable" (frx_problem_set_solver), no limit to raise
+    return FRX_OK;
+}
+
+hipError_t create_stream_and_limits(frx_problem *p) {
+    hipError_t e;
+    if ((e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking)) || (e = (hipError_t)frx::launch_set_limits(p->geo)) || (e = (hipError_t)frx::eval_solo_raise_limit(p->geo))) return e;
+    if (p->geo.lds_solo && frx::eval_solo_blocks_per_cu(p->geo) < 1) { p->geo.lds_solo = 0; p->eval_solo = 0; }
+    if (p->geo.ev_G && frx::eval_cluster_blocks_per_cu(p->geo.lds_ev) < 1) { p->geo.ev_G = 0; p->geo.lds_ev = 0; p->eval_fused_G = 0; p->eval_fused = 0; }   // (the runtime's own occupancy answer: a CU must hold a workgroup of the cluster kernel)
+    return hipSuccess;
+}
+
+hipError_t upload_tables(frx_problem *p, const frx::ProblemTables &tb) {
+    hipError_t e;
+    if ((e = p->d_cvoff.upload(tb.cvoff)) || (e = p->d_poff.upload(tb.poff)) || (e = p->d_coff.upload(tb.coff)) || (e = p->d_xoff.upload(tb.xoff)) || (e = p->d_boff.upload(tb.boff)) ||
+        (e = p->d_piece_hbeg.upload(tb.piece_hbeg)) || (e = p->d_piece_K.upload(tb.piece_K)) || (e = p->d_piece_coarse.upload(tb.piece_coarse)) || (e = p->d_piece_iv.upload(tb.piece_iv)) ||
+        (e = p->d_coarse_iv.upload(tb.coarse_iv)) || (e = p->d_coarse_fbeg.upload(tb.coarse_fbeg)) ||
+        (e = p->d_wp_vbeg.upload(tb.wp_vbeg)) || (e = p->d_wp_nv.upload(tb.wp_nv)) || (e = p->d_wp_xbeg.upload(tb.wp_xbeg)) ||
+        (e = p->d_head.upload(tb.head)) || (e = p->d_tail.upload(tb.tail)) || (e = p->d_hblk.upload(tb.hblk)) || (e = p->d_vrec.upload(tb.vrec))) return e;
+    return hipSuccess;
+}
+
+hipError_t allocate_work_space(frx_problem *p, const frx::ProblemTables &tb) {
+    const size_t P = tb.P;
+    hipError_t e;
+    if ((e = p->d_x.alloc(tb.NX)) || (e = p->d_f.alloc(p->B)) || (e = p->d_g.alloc(tb.NX)) ||
+        (e = p->d_T.alloc(P)) || (e = p->d_C.alloc(P * 18)) || (e = p->d_band.alloc(tb.boff[p->B])) || (e = p->d_out20.alloc(P * 20)) ||
+        (e = p->d_pcrw.alloc((size_t)(p->geo.pcr_steps * 8 + 4) * P)) ||
+        (e = p->d_wq.alloc(4 * P)) || (e = hipMemset(p->d_wq.p, 0, sizeof(double) * 4 * P))) return e;
+    p->geo.pcrw = p->d_pcrw.p;
+    return hipSuccess;
+}
+
+// granules, control words, the mapped status word, the argument block and the front records of the one-launch evaluation, when the handle takes it
+hipError_t allocate_eval_cluster(frx_problem *p, const frx::ProblemTables &tb) {
+    if (!p->eval_fused_G) return hipSuccess;
+    const size_t n_ll = (size_t)40 * tb.P, n_w64 = ((size_t)64 * p->B + 2) / 2;
+    hipError_t e;
+    if ((e = p->d_ev_ll.alloc(n_ll + n_w64)) || (e = hipMemset(p->d_ev_ll.p, 0, sizeof(unsigned long long) * (n_ll + n_w64)))) return e;   // (not on the handle's stream: the first evaluation may come on the caller's)
+    p->d_ev_words = (unsigned *)(p->d_ev_ll.p + n_ll);
+    { NumaScope numa_alloc(p->device); if ((e = p->h_ev_status.alloc(16))) return e; }
+    p->ev_args.assign(frx::eval_cluster_args_bytes(), 0);
+    if ((e = p->d_ev_args.alloc(p->ev_args.size()))) return e;
+    std::vector<frx::EvalFront> front((size_t)p->B);
+    frx::eval_front_fill(p->B, tb.poff.data(), tb.coff.data(), tb.xoff.data(), tb.cvoff.data(), p->softT, p->geo.ppw, front.data());
+    return p->d_ev_front.upload(front);
+}
+
+// pinned staging buffers: pages from the device's NUMA node (NumaScope)
+hipError_t allocate_staging(frx_problem *p, const frx::ProblemTables &tb) {
+    NumaScope numa_alloc(p->device);
+    const size_t P = tb.P;
+    hipError_t e;
+    if ((e = p->h_x.alloc(tb.NX)) || (e = p->h_f.alloc(p->B)) || (e = p->h_g.alloc(tb.NX)) || (e = p->h_T.alloc(P)) || (e = p->h_C.alloc(P * 18)) || (e = p->h_out20.alloc(P * 20))) return e;
+    return hipSuccess;
+}
+
+// what the handle keeps of the tables on the host
+void adopt_tables(frx_problem *p, frx::ProblemTables &tb) {
+    p->poff = std::move(tb.poff); p->coff = std::move(tb.coff); p->xoff = std::move(tb.xoff); p->boff = std::move(tb.boff); p->dimT = std::move(tb.dimT);
+    p->P = tb.P; p->Pc = tb.Pc; p->NX = tb.NX; p->Kmax = tb.Kmax; p->maxN = tb.maxN; p->maxCN = tb.maxCN; p->sumKfine = tb.sumKfine;
+}
+
+void fill_dev_problem(frx_problem *p) {
+    const frx_config *cfg = &p->cfg;
+    frx::DevProblem &d = p->dp;
+    d.B = p->B; d.P = p->P; d.kappa = cfg->qd_intervals; d.inv_kappa = 1.0 / cfg->qd_intervals; d.soft = p->softT ? 1 : 0; d.c2 = cfg->c2_diffeo ? 1 : 0;
+    d.rho = p->softT ? cfg->rho : 0.0;                                   // CPU.hpp:1098-1107
+    d.sumT = p->softT ? 1.0 : cfg->total_t;
+    d.pc.ell[0] = cfg->horiz_half_len; d.pc.ell[1] = cfg->horiz_half_len; d.pc.ell[2] = cfg->vert_half_len;
+    d.pc.safeMargin = cfg->safe_margin;
+    d.pc.vMaxSqr = cfg->vel_max * cfg->vel_max;
+    d.pc.thrMinSqr = cfg->thr_acc_min * cfg->thr_acc_min;
+    d.pc.thrMaxSqr = cfg->thr_acc_max * cfg->thr_acc_max;
+    d.pc.bdrMaxSqr = cfg->body_rate_max * cfg->body_rate_max;
+    d.pc.gAcc = cfg->grav_acc;
+    for (int q = 0; q < 4; q++) d.pc.chi[q] = cfg->penalty_pvtb[q];
+    d.cvoff = p->d_cvoff.p; d.poff = p->d_poff.p; d.coff = p->d_coff.p; d.xoff = p->d_xoff.p; d.boff = p->d_boff.p;
+    d.headPVA = p->d_head.p; d.tailPVA = p->d_tail.p;
+    d.piece_hbeg = p->d_piece_hbeg.p; d.piece_K = p->d_piece_K.p; d.piece_coarse = p->d_piece_coarse.p; d.piece_iv = p->d_piece_iv.p;
+    d.coarse_iv = p->d_coarse_iv.p; d.coarse_fbeg = p->d_coarse_fbeg.p;
+    d.wp_vbeg = p->d_wp_vbeg.p; d.wp_nv = p->d_wp_nv.p; d.wp_xbeg = p->d_wp_xbeg.p;
+    d.hblk = p->d_hblk.p; d.vrec = p->d_vrec.p; d.wq_glob = p->d_wq.p; d.stamps = nullptr; d.cand_active = nullptr; d.piece_active = nullptr;
+}
+
+// (the first evaluation may be captured: the device copy of its arguments is complete before create returns)
+hipError_t upload_eval_cluster_args(frx_problem *p) {
+    if (!p->eval_fused_G) return hipSuccess;
+    frx::eval_cluster_args(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_ev_ll.p, p->d_ev_words, p->d_ev_front.p, p->ev_args.data());
+    return hipMemcpy(p->d_ev_args.p, p->ev_args.data(), p->ev_args.size(), hipMemcpyHostToDevice);
+}
+
+} // namespace
+
 extern "C" {
 
 int frx_version(void) { return FRX_VERSION; }
@@ -118,238 +283,31 @@ int frx_problem_create(const frx_config *cfg, int device, int B, const int *coar
     if (hipSetDevice(device) != hipSuccess) return fail(FRX_ERR_NO_DEVICE, "hipSetDevice failed");
 
     const auto t_create0 = clk::now();
-    frx_problem *p = new (std::nothrow) frx_problem();
+    HandleOwner own(new (std::nothrow) frx_problem());
+    frx_problem *p = own.p;
     if (!p) return fail(FRX_ERR_ALLOC, "out of host memory");
     p->cfg = *cfg;
     p->device = device;
     p->B = B;
     p->softT = cfg->rho > 0;                                             // CPU.hpp:1097
-    p->cand.resize(B);
-    p->poff.assign(B + 1, 0); p->coff.assign(B + 1, 0); p->xoff.assign(B + 1, 0); p->boff.assign(B + 1, 0);
-    p->dimT.assign(B, 0);
+    const frx::CreateSwitches sw = create_switches_from_env();
 
-    std::vector<int> piece_hbeg, piece_K, piece_coarse, piece_iv, coarse_iv, coarse_fbeg, wp_vbeg, wp_nv, wp_xbeg, cvoff(B + 1, 0);
-    std::vector<double> hrec, horg, vrec, head(ini_state, ini_state + 9 * (size_t)B), tail(fin_state, fin_state + 9 * (size_t)B);
-    int hpoly = 0, vpoly = 0;                     // running polytope indices into h_off / v_off
-    for (int b = 0; b < B; b++) {
-        frx::HostCand &hc = p->cand[b];
-        const int cN = coarse_n[b];
-        if (cN < 1) { delete p; return fail(FRX_ERR_INVALID_ARG, "coarse_n[b] < 1"); }
-        // host description: V-polytopes as [v0, v_r - v0], gridMesh, waypoint index map, clipped boundary speeds (frx_host_setup.hpp)
-        if (frx::host_cand_init(hc, *cfg, p->softT, cN, ini_state + 9 * (size_t)b, fin_state + 9 * (size_t)b, v_off + vpoly, v_rec) != FRX_OK) {
-            delete p; return fail(FRX_ERR_EMPTY_POLYTOPE, "a corridor polytope has no vertices");
-        }
-        cvoff[b] = (int)(vrec.size() / 3);
-        // index maps (CPU.hpp:1129-1152), expanded into per-piece / per-waypoint device descriptors
-        const int gp0 = p->poff[b], gc0 = p->coff[b];
-        int offset = 0;
-        int xcur = p->xoff[b] + hc.dimT;
-        for (int i = 0; i < cN; i++) {
-            const int hb = h_off[hpoly + i], K = h_off[hpoly + i + 1] - hb;
-            if (K < 1) { delete p; return fail(FRX_ERR_INVALID_ARG, "an H-polytope has no half-spaces"); }
-            const int hbeg_dev = (int)(hrec.size() / 4);
-            const double *org = h_rec + 6 * (size_t)hb + 3;              // polytope origin = point of its first half-space
-            horg.push_back(org[0]); horg.push_back(org[1]); horg.push_back(org[2]);
-            for (int k = 0; k < K; k++) {                                // normalise outer normals, CPU.hpp:1116
-                const double *rec = h_rec + 6 * (size_t)(hb + k);
-                const double nn = std::sqrt(rec[0] * rec[0] + rec[1] * rec[1] + rec[2] * rec[2]);
-                const double n0 = rec[0] / nn, n1 = rec[1] / nn, n2 = rec[2] / nn;
-                hrec.push_back(n0); hrec.push_back(n1); hrec.push_back(n2);
-                // n.(pos - p_k) + margin = n.(pos - org) - c   with   c = n.(p_k - org) - margin   (CPU.hpp:325,328)
-                hrec.push_back(n0 * (rec[3] - org[0]) + n1 * (rec[4] - org[1]) + n2 * (rec[5] - org[2]) - cfg->safe_margin);
-            }
-            p->Kmax = std::max(p->Kmax, K);
-            coarse_iv.push_back(hc.intervals[i]);
-            coarse_fbeg.push_back(gp0 + offset);
-            for (int j = 0; j < hc.intervals[i]; j++) {
-                int vm = -1;
-                if (j < hc.intervals[i] - 1) vm = 2 * i;
-                else if (i < cN - 1) vm = 2 * i + 1;
-                if (vm >= 0) {
-                    const int nv = (int)(hc.cfgVs[vm].size() / 3);
-                    wp_vbeg.push_back((int)(vrec.size() / 3)); wp_nv.push_back(nv); wp_xbeg.push_back(xcur);
-                    vrec.insert(vrec.end(), hc.cfgVs[vm].begin(), hc.cfgVs[vm].end());   // waypoint order, contiguous per candidate
-                    xcur += nv - 1;
-                }
-                piece_hbeg.push_back(hbeg_dev); piece_K.push_back(K); piece_coarse.push_back(gc0 + i); piece_iv.push_back(hc.intervals[i]);
-                p->sumKfine += K;
-                offset++;
-            }
-        }
-        hpoly += cN;
-        vpoly += 2 * cN - 1;
-        p->dimT[b] = hc.dimT;
-        p->poff[b + 1] = gp0 + hc.fineN;
-        p->coff[b + 1] = gc0 + cN;
-        p->xoff[b + 1] = p->xoff[b] + hc.dimT + hc.dimP;
-        p->boff[b + 1] = p->boff[b] + 6 * hc.fineN * FRX_BAND_W;
-        p->maxN = std::max(p->maxN, hc.fineN);
-        p->maxCN = std::max(p->maxCN, cN);
-    }
-    cvoff[B] = (int)(vrec.size() / 3);
-    p->P = p->poff[B]; p->Pc = p->coff[B]; p->NX = p->xoff[B];
-    int maxXb = 1, maxVb = 3;
-    for (int b = 0; b < B; b++) {
-        maxXb = std::max(maxXb, p->xoff[b + 1] - p->xoff[b]);
-        maxVb = std::max(maxVb, 3 * (cvoff[b + 1] - cvoff[b]));
-    }
-
-    // launch geometry + LDS budgets
-    const int spp = cfg->qd_intervals + 1;
-    frx::LaunchGeom &ge = p->geo;
-    ge.maxN = p->maxN; ge.maxCN = p->maxCN; ge.Kmax = p->Kmax;
-    ge.lpp = std::min(spp, 64);
-    ge.ppw = 64 / ge.lpp;
-    {   // stage kernel k_penalty: a workgroup of W waves owns floor(64 W / lpp) whole pieces; W in 1..4 for the best lane utilisation (the
-        // fewest waves among equals) - kappa = 16: 51/64 lanes with one wave, 255/256 with four; stock kappa = 48: 49/64 and 245/256.
-        // Measured (profiles/r03_penalty_waves_per_workgroup.jsonl, kappa = 16): 1024 candidates 40.3 -> 35.9 us, 4096 candidates 153 -> 132 us
-        // (kappa = 48, 1024 candidates: 116 -> 95 us); but a launch that fits the chip's SIMDs in one go is ONE wave's latency, and there
-        // one-wave workgroups (no barrier, twice the CUs in use) win: 4.79 against 5.17 us at the headline batch.  FRX_PENALTY_WAVES=1..4 overrides.
-        int best_w = 1; double best_u = 0.0;
-        for (int w = 1; w <= 4; w++) {
-            const double u = (double)((64 * w) / ge.lpp * ge.lpp) / (64.0 * w);
-            if (u > best_u + 1e-9) { best_u = u; best_w = w; }
-        }
-        int simds = 1024;
-        { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess) simds = 4 * prop.multiProcessorCount; }
-        if ((p->P + ge.ppw - 1) / ge.ppw <= simds) best_w = 1;
-        if (const char *pw = std::getenv("FRX_PENALTY_WAVES")) { const int w = std::atoi(pw); if (w >= 1 && w <= 4) best_w = w; }
-        //  W is chosen for lane utilisation, but the workgroup's LDS grows with it (ppg corridor blocks of Kmax + 1 records): step W down
-        // until the block fits the CU - a corridor with many half-spaces runs on fewer waves instead of failing create
-        while (best_w > 1 && frx::pen_wg_bytes((64 * best_w) / ge.lpp, p->Kmax, best_w, 21) > (size_t)160 * 1024) best_w--;
-        ge.pen_w = best_w; ge.ppg = (64 * best_w) / ge.lpp;
-    }
-    ge.lds_fwd = sizeof(double) * ((size_t)6 * p->maxN * (FRX_BAND_W + 3) + p->maxN + p->maxCN);
-    ge.lds_bwd = sizeof(double) * ((size_t)6 * p->maxN * (FRX_BAND_W + 6) + 2 * (size_t)p->maxN + p->maxCN);
-    ge.lds_pen = frx::pen_wg_bytes(ge.ppg, p->Kmax, ge.pen_w, 21);
-    // large batches (four-wave workgroups), one sample per lane: the two-phase form of the integrator (k_penalty_lat2) - half the transpose buffer, four waves per SIMD
-    ge.lds_pen2 = (ge.pen_w == 4 && spp <= 64) ? frx::pen_wg_bytes(ge.ppg, p->Kmax, ge.pen_w, 11) : 0;
-    ge.solver = frx::SOLVER_KNOT_PCR;
-    ge.knot_threads = 64 * ((p->maxN + 63) / 64);
-    {
-        const size_t nt = ge.knot_threads;
-        ge.maxXb = maxXb; ge.maxVb = maxVb;
-        ge.pcr_steps = 0;
-        for (int s = 1; s < p->maxN - 1; s <<= 1) ge.pcr_steps++;
-        ge.lds_kfwd = sizeof(double) * (36 * nt + 9 * (nt + 1) + nt + p->maxCN + maxXb + maxVb + (size_t)(ge.pcr_steps * 8 + 5) * nt);
-        ge.pcr_steps = 0;
-        for (int s = 1; s < p->maxN - 1; s <<= 1) ge.pcr_steps++;
-        ge.lds_kbwd = sizeof(double) * (36 * nt + 9 * (nt + 1) + 2 * nt + p->maxCN + 2 * 4 + 2 + 2 * maxXb + maxVb + (size_t)(ge.pcr_steps * 8 + 5) * nt);
-    }
-    {   // one launch per evaluation when every cluster of the batch gets its CUs at once
-        int cus = 256;
-        { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount; }
-        const char *ef = std::getenv("FRX_EVAL_FUSED");
-        const int G = frx::eval_cluster_geometry(ge);
-        //  ranks of one node that SHARE a device (more local ranks than devices): their grids would compete for the CUs a cluster's leader assumes - off
-        // unless asked for (FRX_EVAL_FUSED=1); a lone process, or one rank per device, takes the form
-        int ranks = 1;
-        if (const char *e = std::getenv("FRX_LOCAL_RANKS")) ranks = std::max(1, std::atoi(e));
-        else if (const char *e2 = std::getenv("LOCAL_WORLD_SIZE")) ranks = std::max(1, std::atoi(e2));
-        const bool shared_device = ranks > ndev && !(ef && ef[0] == '1');
-        if (!G || (long long)B * G > cus || (ef && ef[0] == '0') || shared_device) { ge.ev_G = 0; ge.lds_ev = 0; }
-        p->eval_fused_G = ge.ev_G; p->eval_fused = ge.ev_G ? 1 : 0;
-        // (the solo form: from the batch size on at which the stage launches' ramps and stage-buffer trips outweigh a lone workgroup's five penalty passes - measured,
-        // profiles/NOTES.md round 6; FRX_EVAL_SOLO=0 never, =1 always, FRX_EVAL_SOLO_MIN_B=n moves the threshold)
-        frx::eval_solo_geometry(ge, spp);
-        p->eval_solo = ge.lds_solo ? 1 : 0; p->eval_solo_min_B = 384; p->eval_solo_max_B = 512;
-        if (const char *es = std::getenv("FRX_EVAL_SOLO")) { if (es[0] == '0') p->eval_solo = 0; else if (es[0] == '1' && ge.lds_solo) p->eval_solo = 2; }
-        if (const char *mb = std::getenv("FRX_EVAL_SOLO_MIN_B")) { const int v = std::atoi(mb); if (v > 0) p->eval_solo_min_B = v; }
-        if (const char *mb = std::getenv("FRX_EVAL_SOLO_MAX_B")) { const int v = std::atoi(mb); if (v > 0) p->eval_solo_max_B = v; }
-        if (const char *tm = std::getenv("FRX_EVAL_TIMEOUT_MS")) { const double v = std::atof(tm); if (v > 0.0) p->eval_fused_ticks = (unsigned long long)(v * 1e5); }
-    }
-    const size_t lds_cap = 160 * 1024;
-    if (ge.knot_threads > 256 || ge.lds_kbwd > lds_cap) {
-        delete p;
-        return fail(FRX_ERR_CAPACITY, "a candidate's knot system does not fit one workgroup: " + std::to_string(ge.lds_kbwd / 1024) + " KB of LDS needed, 160 KB available (" +
-                                          std::to_string(ge.knot_threads) + " knot threads, limit 256; about 128 pieces per candidate fit; the reference caps at 100, cuda_computer.cuh:24)");
-    }
-    // the banded-LU cross-check kernels need the whole band in LDS; fall back to "unavailable" instead of failing create
-    p->banded_ok = !(ge.lds_bwd > lds_cap || ge.lds_fwd > lds_cap);
-    if (!p->banded_ok) { ge.lds_fwd = ge.lds_bwd = 1024; }
-    if (ge.lds_pen > lds_cap) {
-        delete p;
-        return fail(FRX_ERR_CAPACITY, "piece count / half-space count too large for the LDS-resident kernels (160 KiB per CU)");
-    }
-
-#define CR(expr)                                                                                        \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            std::string m_ = std::string(#expr) + ": " + hipGetErrorString(e_);                        \
-            if (p->stream) (void)hipStreamDestroy(p->stream);                                           \
-            delete p;                                                                                   \
-            return fail(e_ == hipErrorOutOfMemory ? FRX_ERR_ALLOC : FRX_ERR_HIP, m_);                   \
-        }                                                                                               \
-    } while (0)
+    frx::ProblemTables tb;
+    if (const int rc = create_tables(p, coarse_n, ini_state, fin_state, h_off, h_rec, v_off, v_rec, tb)) return rc;
+    if (const int rc = create_geometry(p, tb, sw, ndev)) return rc;
     const double ms_host_build = ms_since(t_create0);
-    CR(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    CR((hipError_t)frx::launch_set_limits(p->geo));
-    CR((hipError_t)frx::eval_solo_raise_limit(p->geo));
-    if (p->geo.lds_solo && frx::eval_solo_blocks_per_cu(p->geo) < 1) { p->geo.lds_solo = 0; p->eval_solo = 0; }
-    if (p->geo.ev_G && frx::eval_cluster_blocks_per_cu(p->geo.lds_ev) < 1) { p->geo.ev_G = 0; p->geo.lds_ev = 0; p->eval_fused_G = 0; p->eval_fused = 0; }   // (the runtime's own occupancy answer: a CU must hold a workgroup of the cluster kernel)
-    CR(p->d_cvoff.upload(cvoff)); CR(p->d_poff.upload(p->poff)); CR(p->d_coff.upload(p->coff)); CR(p->d_xoff.upload(p->xoff)); CR(p->d_boff.upload(p->boff));
-    CR(p->d_piece_hbeg.upload(piece_hbeg)); CR(p->d_piece_K.upload(piece_K)); CR(p->d_piece_coarse.upload(piece_coarse)); CR(p->d_piece_iv.upload(piece_iv));
-    CR(p->d_coarse_iv.upload(coarse_iv)); CR(p->d_coarse_fbeg.upload(coarse_fbeg));
-    CR(p->d_wp_vbeg.upload(wp_vbeg)); CR(p->d_wp_nv.upload(wp_nv)); CR(p->d_wp_xbeg.upload(wp_xbeg));
-    CR(p->d_head.upload(head)); CR(p->d_tail.upload(tail)); {
-        // per-piece corridor blocks, padded to Kmax: one contiguous, index-free read per piece in k_penalty
-        const int hs = (p->Kmax + 1) * 4;
-        std::vector<double> hblk((size_t)p->P * hs, 0.0);
-        for (int gp = 0; gp < p->P; gp++) {
-            double *blk = &hblk[(size_t)gp * hs];
-            const int gc = piece_coarse[gp], K = piece_K[gp];
-            blk[0] = horg[3 * (size_t)gc]; blk[1] = horg[3 * (size_t)gc + 1]; blk[2] = horg[3 * (size_t)gc + 2]; blk[3] = (double)K;
-            std::memcpy(blk + 4, &hrec[4 * (size_t)piece_hbeg[gp]], sizeof(double) * 4 * K);
-        }
-        CR(p->d_hblk.upload(hblk));
-    } CR(p->d_vrec.upload(vrec));
-    CR(p->d_x.alloc(p->NX)); CR(p->d_f.alloc(B)); CR(p->d_g.alloc(p->NX));
-    CR(p->d_T.alloc(p->P)); CR(p->d_C.alloc((size_t)p->P * 18)); CR(p->d_band.alloc(p->boff[B])); CR(p->d_out20.alloc((size_t)p->P * 20));
-    CR(p->d_pcrw.alloc((size_t)(p->geo.pcr_steps * 8 + 4) * p->P)); p->geo.pcrw = p->d_pcrw.p;
-    CR(p->d_wq.alloc((size_t)4 * p->P)); CR(hipMemset(p->d_wq.p, 0, sizeof(double) * 4 * p->P));
-    if (p->eval_fused_G) {
-        const size_t n_ll = (size_t)40 * p->P, n_w64 = ((size_t)64 * B + 2) / 2;
-        CR(p->d_ev_ll.alloc(n_ll + n_w64)); CR(hipMemset(p->d_ev_ll.p, 0, sizeof(unsigned long long) * (n_ll + n_w64)));   // (not on the handle's stream: the first evaluation may come on the caller's)
-        p->d_ev_words = (unsigned *)(p->d_ev_ll.p + n_ll);
-        { NumaScope numa_alloc(device); CR(p->h_ev_status.alloc(16)); }
-        p->ev_args.assign(frx::eval_cluster_args_bytes(), 0); CR(p->d_ev_args.alloc(p->ev_args.size()));
-        std::vector<frx::EvalFront> front((size_t)B);                      // from the host copies of the tables uploaded above
-        frx::eval_front_fill(B, p->poff.data(), p->coff.data(), p->xoff.data(), cvoff.data(), p->softT, p->geo.ppw, front.data());
-        CR(p->d_ev_front.upload(front));
-    }
-    {   // pinned staging buffers: pages from the device's NUMA node (NumaScope)
-        NumaScope numa_alloc(device);
-        CR(p->h_x.alloc(p->NX)); CR(p->h_f.alloc(B)); CR(p->h_g.alloc(p->NX));
-        CR(p->h_T.alloc(p->P)); CR(p->h_C.alloc((size_t)p->P * 18)); CR(p->h_out20.alloc((size_t)p->P * 20));
-    }
-#undef CR
 
-    frx::DevProblem &d = p->dp;
-    d.B = B; d.P = p->P; d.kappa = cfg->qd_intervals; d.inv_kappa = 1.0 / cfg->qd_intervals; d.soft = p->softT ? 1 : 0; d.c2 = cfg->c2_diffeo ? 1 : 0;
-    d.rho = p->softT ? cfg->rho : 0.0;                                   // CPU.hpp:1098-1107
-    d.sumT = p->softT ? 1.0 : cfg->total_t;
-    d.pc.ell[0] = cfg->horiz_half_len; d.pc.ell[1] = cfg->horiz_half_len; d.pc.ell[2] = cfg->vert_half_len;
-    d.pc.safeMargin = cfg->safe_margin;
-    d.pc.vMaxSqr = cfg->vel_max * cfg->vel_max;
-    d.pc.thrMinSqr = cfg->thr_acc_min * cfg->thr_acc_min;
-    d.pc.thrMaxSqr = cfg->thr_acc_max * cfg->thr_acc_max;
-    d.pc.bdrMaxSqr = cfg->body_rate_max * cfg->body_rate_max;
-    d.pc.gAcc = cfg->grav_acc;
-    for (int q = 0; q < 4; q++) d.pc.chi[q] = cfg->penalty_pvtb[q];
-    d.cvoff = p->d_cvoff.p; d.poff = p->d_poff.p; d.coff = p->d_coff.p; d.xoff = p->d_xoff.p; d.boff = p->d_boff.p;
-    d.headPVA = p->d_head.p; d.tailPVA = p->d_tail.p;
-    d.piece_hbeg = p->d_piece_hbeg.p; d.piece_K = p->d_piece_K.p; d.piece_coarse = p->d_piece_coarse.p; d.piece_iv = p->d_piece_iv.p;
-    d.coarse_iv = p->d_coarse_iv.p; d.coarse_fbeg = p->d_coarse_fbeg.p;
-    d.wp_vbeg = p->d_wp_vbeg.p; d.wp_nv = p->d_wp_nv.p; d.wp_xbeg = p->d_wp_xbeg.p;
-    d.hblk = p->d_hblk.p; d.vrec = p->d_vrec.p; d.wq_glob = p->d_wq.p; d.stamps = nullptr; d.cand_active = nullptr; d.piece_active = nullptr;
-    if (p->eval_fused_G) {                                                  // (the first evaluation may be captured: the device copy of its arguments is complete before create returns)
-        frx::eval_cluster_args(p->dp, p->geo, p->d_T.p, p->d_C.p, p->d_ev_ll.p, p->d_ev_words, p->d_ev_front.p, p->ev_args.data());
-        const hipError_t e_ = hipMemcpy(p->d_ev_args.p, p->ev_args.data(), p->ev_args.size(), hipMemcpyHostToDevice);
-        if (e_ != hipSuccess) { const std::string m_ = std::string("upload of the evaluation arguments: ") + hipGetErrorString(e_); (void)hipStreamDestroy(p->stream); delete p; return fail(FRX_ERR_HIP, m_); }
-    }
-    if (std::getenv("FRX_SETUP_TIMING")) fprintf(stderr, "[frx setup] frx_problem_create: B = %d, host descriptors %.3f ms, device allocations + uploads %.3f ms\n", B, ms_host_build, ms_since(t_create0) - ms_host_build);
-    *out = p;
+    hipError_t e;
+    if ((e = create_stream_and_limits(p))) return create_hip_error(e, "stream and LDS limits");
+    if ((e = upload_tables(p, tb))) return create_hip_error(e, "upload of the descriptor tables");
+    if ((e = allocate_work_space(p, tb))) return create_hip_error(e, "device work space");
+    if ((e = allocate_eval_cluster(p, tb))) return create_hip_error(e, "buffers of the one-launch evaluation");
+    if ((e = allocate_staging(p, tb))) return create_hip_error(e, "pinned staging buffers");
+    adopt_tables(p, tb);
+    fill_dev_problem(p);
+    if ((e = upload_eval_cluster_args(p))) return create_hip_error(e, "upload of the evaluation arguments");
+    if (sw.setup_timing) fprintf(stderr, "[frx setup] frx_problem_create: B = %d, host descriptors %.3f ms, device allocations + uploads %.3f ms\n", B, ms_host_build, ms_since(t_create0) - ms_host_build);
+    *out = own.release();
     return FRX_OK;
 }
 

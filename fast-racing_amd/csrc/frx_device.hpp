@@ -12,6 +12,10 @@
 
 namespace frx {
 
+// LDS of the banded-LU kernels, the sums of their carve-ups (k_forward: band | rhs 6 maxN x 3 | Tf | Tc; k_backward: band | gd | cL | Tf | gT | gCo)
+constexpr size_t banded_fwd_lds_bytes(int maxN, int maxCN) { return sizeof(double) * ((size_t)6 * maxN * (FRX_BAND_W + 3) + maxN + maxCN); }
+constexpr size_t banded_bwd_lds_bytes(int maxN, int maxCN) { return sizeof(double) * ((size_t)6 * maxN * (FRX_BAND_W + 6) + 2 * (size_t)maxN + maxCN); }
+
 struct DevProblem {
     int B, P, kappa, soft, c2;
     double rho, sumT;

@@ -184,6 +184,7 @@ FRX_KERNEL_LINKAGE __global__ __launch_bounds__(64) void k_forward(DevProblem dp
     const int p0 = dp.poff[b], N = dp.poff[b + 1] - p0, n6 = 6 * N;
     const int c0 = dp.coff[b], cN = dp.coff[b + 1] - c0;
     const int x0 = dp.xoff[b];
+    // (the carve-up below sums to banded_fwd_lds_bytes, frx_device.hpp)
     double *band = sm;
     double *rhs = band + (size_t)6 * maxN * FRX_BAND_W;
     double *Tf = rhs + (size_t)6 * maxN * 3;
@@ -778,6 +779,7 @@ FRX_KERNEL_LINKAGE __global__ __launch_bounds__(64) void k_backward(DevProblem d
     const int p0 = dp.poff[b], N = dp.poff[b + 1] - p0, n6 = 6 * N;
     const int c0 = dp.coff[b], cN = dp.coff[b + 1] - c0;
     const int x0 = dp.xoff[b];
+    // (the carve-up below sums to banded_bwd_lds_bytes, frx_device.hpp)
     double *band = sm;
     double *gd = band + (size_t)6 * maxN * FRX_BAND_W;
     double *cL = gd + (size_t)6 * maxN * 3;
@@ -1352,6 +1354,7 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
     const int p0 = pre ? pre->p0 : dp.poff[b], N = pre ? pre->N : dp.poff[b + 1] - p0;
     const int c0 = pre ? pre->c0 : dp.coff[b], cN = pre ? pre->cN : dp.coff[b + 1] - c0;
     const int x0 = pre ? pre->x0 : dp.xoff[b];
+    // (the carve-up below sums to knot_fwd_lds_bytes, frx_launch_forms.hpp)
     double *rowbuf = sm;
     static_assert(RB == 0 || (NR == 64 && RB >= 24 * 64 + 2), "a short row buffer: the <= 64-piece path only, progress words included");
     double *KP = rowbuf + (RB > 0 ? (size_t)RB : (size_t)36 * nrow);          // knot positions  [3][nthr+1]
@@ -1792,6 +1795,7 @@ __device__ __forceinline__ void backward_knot_wsp64_stage(const DevProblem &dp, 
     const int p0 = dp.poff[b], N = dp.poff[b + 1] - p0;
     const int c0 = dp.coff[b], cN = dp.coff[b + 1] - c0;
     const int x0 = dp.xoff[b];
+    // (the carve-up below, dsv included, sums to knot_bwd_lds_bytes, frx_launch_forms.hpp)
     double *rowbuf = sm;
     double *KP = rowbuf + (RB > 0 ? (size_t)RB : (size_t)36 * nrow);          // d f / d q_k per axis (for the waypoint layer); RB: see forward_knot_body
     double *KV = KP + 3 * (nrow + 1);                 // duration adjoint of piece k, one row per axis
@@ -2118,6 +2122,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
     const int p0 = dp.poff[b], N = dp.poff[b + 1] - p0;
     const int c0 = dp.coff[b], cN = dp.coff[b + 1] - c0;
     const int x0 = dp.xoff[b];
+    // (the carve-up below, dsv included, sums to knot_bwd_lds_bytes, frx_launch_forms.hpp)
     double *rowbuf = sm;
     double *KP = rowbuf + (size_t)36 * nrow;          // d f / d q_k per axis (for the waypoint layer)
     double *KV = KP + 3 * (nrow + 1);                 // duration adjoint of piece k, one row per axis
@@ -2644,6 +2649,7 @@ __device__ __forceinline__ void backward_knot_body(const DevProblem &dp, const d
     const int p0 = dp.poff[b], N = dp.poff[b + 1] - p0;
     const int c0 = dp.coff[b], cN = dp.coff[b + 1] - c0;
     const int x0 = dp.xoff[b];
+    // (the carve-up below, dsv included, sums to knot_bwd_lds_bytes, frx_launch_forms.hpp)
     double *rowbuf = sm;
     double *KP = rowbuf + (size_t)36 * nrow;          // reused: knot states, then end-of-piece adjoints, then mu
     double *KV = KP + 3 * (nrow + 1);

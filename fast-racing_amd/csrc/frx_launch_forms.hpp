@@ -16,6 +16,70 @@ constexpr size_t pen_wg_bytes(int ppg, int Kmax, int waves, int doubles_per_lane
     return sizeof(double) * ((size_t)ppg * 19 + (size_t)ppg * (Kmax + 1) * 4 + (size_t)64 * waves * doubles_per_lane);
 }
 
+constexpr size_t LDS_PER_CU = (size_t)160 * 1024;                 // what a workgroup can have (gfx950)
+
+// ---- LDS of the knot kernels: each is the sum of what the kernel's carve-up takes from its one dynamic array (frx_kernels.hpp names the function at the carve-up) ----
+constexpr int knot_threads(int maxN) { return 64 * ((maxN + 63) / 64); }                       // rows of the knot system's buffers: maxN rounded up to whole waves
+constexpr int pcr_steps(int maxN) { int n = 0; for (int s = 1; s < maxN - 1; s <<= 1) n++; return n; }   // ceil(log2(maxN - 1)), 0 up to two pieces
+// forward_knot_body: row buffer 36 nt | KP KV KA 3 x 3 (nt + 1) | Tf nt | Tc maxCN | xs maxXb | vs maxVb | the saved multipliers (8 steps + 5) nt
+constexpr size_t knot_fwd_lds_bytes(int knot_threads, int maxCN, int maxXb, int maxVb, int pcr_steps) {
+    const size_t nt = knot_threads;
+    return sizeof(double) * (36 * nt + 9 * (nt + 1) + nt + maxCN + maxXb + maxVb + (size_t)(pcr_steps * 8 + 5) * nt);
+}
+// the backward_knot bodies: as above with gT nt beside Tf, gCo for Tc, the cross-wave partials red 2 x 4 + 2 and the search direction dsv maxXb behind the multipliers
+constexpr size_t knot_bwd_lds_bytes(int knot_threads, int maxCN, int maxXb, int maxVb, int pcr_steps) {
+    const size_t nt = knot_threads;
+    return sizeof(double) * (36 * nt + 9 * (nt + 1) + 2 * nt + maxCN + 2 * 4 + 2 + 2 * maxXb + maxVb + (size_t)(pcr_steps * 8 + 5) * nt);
+}
+// (the banded-LU pair's sizes stand beside the band width they depend on: banded_fwd_lds_bytes / banded_bwd_lds_bytes, frx_device.hpp)
+
+// ---- what a handle's geometry admits (frx_problem_create turns a refusal into its message) ----
+enum GeomRefusal { GEOM_FITS, GEOM_KNOT_CAPACITY, GEOM_PENALTY_CAPACITY };
+struct GeomVerdict { GeomRefusal refusal; bool banded_ok; };
+// the knot system of the largest candidate must fit one workgroup, the penalty workgroup one CU; the banded-LU cross-check kernels need the whole band in LDS and
+// are "unavailable" instead of failing create
+constexpr GeomVerdict geometry_verdict(int knot_threads, size_t lds_kbwd, size_t lds_fwd, size_t lds_bwd, size_t lds_pen) {
+    return {knot_threads > 256 || lds_kbwd > LDS_PER_CU ? GEOM_KNOT_CAPACITY : lds_pen > LDS_PER_CU ? GEOM_PENALTY_CAPACITY : GEOM_FITS,
+            !(lds_bwd > LDS_PER_CU || lds_fwd > LDS_PER_CU)};
+}
+
+// ---- stage kernel k_penalty: waves per workgroup and the whole pieces they own ----
+// A workgroup of W waves owns floor(64 W / lpp) whole pieces; W in 1..4 for the best lane utilisation (the fewest waves among equals) - kappa = 16: 51/64 lanes with
+// one wave, 255/256 with four; stock kappa = 48: 49/64 and 245/256.  Measured (profiles/r03_penalty_waves_per_workgroup.jsonl, kappa = 16): 1024 candidates
+// 40.3 -> 35.9 us, 4096 candidates 153 -> 132 us (kappa = 48, 1024 candidates: 116 -> 95 us); but a launch that fits the chip's SIMDs in one go is ONE wave's latency,
+// and there one-wave workgroups (no barrier, twice the CUs in use) win: 4.79 against 5.17 us at the headline batch.  forced_waves: FRX_PENALTY_WAVES as a number,
+// 1..4 overrides, anything else does not.
+struct PenaltyWaves { int pen_w, ppg; };
+inline PenaltyWaves penalty_waves(int lpp, int Kmax, int P, int simds, int forced_waves) {
+    const int ppw = 64 / lpp;
+    int best_w = 1; double best_u = 0.0;
+    for (int w = 1; w <= 4; w++) {
+        const double u = (double)((64 * w) / lpp * lpp) / (64.0 * w);
+        if (u > best_u + 1e-9) { best_u = u; best_w = w; }
+    }
+    if ((P + ppw - 1) / ppw <= simds) best_w = 1;
+    if (forced_waves >= 1 && forced_waves <= 4) best_w = forced_waves;
+    //  W is chosen for lane utilisation, but the workgroup's LDS grows with it (ppg corridor blocks of Kmax + 1 records): step W down
+    // until the block fits the CU - a corridor with many half-spaces runs on fewer waves instead of failing create
+    while (best_w > 1 && pen_wg_bytes((64 * best_w) / lpp, Kmax, best_w, 21) > LDS_PER_CU) best_w--;
+    return {best_w, (64 * best_w) / lpp};
+}
+
+// ---- which handles take the one-launch and the solo evaluation ----
+// One launch per evaluation when every cluster of the batch gets its CUs at once (G workgroups per candidate, 0 = the geometry does not apply).  fused_char: first
+// character of FRX_EVAL_FUSED, 0 when unset.   ranks of one node that SHARE a device (more local ranks than devices): their grids would compete for the CUs
+// a cluster's leader assumes - off unless asked for (FRX_EVAL_FUSED=1); a lone process, or one rank per device, takes the form
+constexpr bool eval_cluster_admitted(int G, int B, int cus, char fused_char, int local_ranks, int ndev) {
+    return G && (long long)B * G <= cus && fused_char != '0' && !(local_ranks > ndev && fused_char != '1');
+}
+// The solo form: from the batch size on at which the stage launches' ramps and stage-buffer trips outweigh a lone workgroup's five penalty passes - measured,
+// profiles/NOTES.md round 6.  solo_char: first character of FRX_EVAL_SOLO ('0' never, '1' always), 0 when unset; min_B / max_B: FRX_EVAL_SOLO_MIN_B / _MAX_B as
+// numbers, > 0 moves the threshold.  eval_solo as frx_problem holds it: 0 never, 1 inside [min_B, max_B], 2 always.
+struct SoloChoice { int eval_solo, min_B, max_B; };
+constexpr SoloChoice eval_solo_choice(bool lds_solo, char solo_char, int min_B, int max_B) {
+    return {solo_char == '0' ? 0 : solo_char == '1' && lds_solo ? 2 : lds_solo ? 1 : 0, min_B > 0 ? min_B : 384, max_B > 0 ? max_B : 512};
+}
+
 // ---- the dynamic-LDS limit of every kernel (raise_lds_limit, frx_device.hip) ----
 // What is held per (device, function), and the rule: the limit only grows.  set(fn, bytes) makes the call (0 = done) and is only asked for a need above what is
 // held; a need already held, or none at all, is no call.  A failed call leaves the table as it was.

@@ -328,6 +328,58 @@ extern "C" void hostcheck_resident_plan_rows(long long n, const int *rows, long 
 extern "C" int hostcheck_resident_capacity(int maxXb, int cus) { return frx::resident_capacity(maxXb, cus); }
 extern "C" unsigned long long hostcheck_round_command_word(unsigned long long seq, int flags, int slot, int bound, double step) { return frx::round_command_word(seq, flags, slot, bound, step); }
 
+// ---- what frx_problem_create decides on the host (fast-racing_amd/csrc/frx_problem_tables.hpp and the sizes of frx_launch_forms.hpp), for tests/test_problem_tables_cpu.py ----
+#include "../../fast-racing_amd/csrc/frx_problem_tables.hpp"
+namespace { frx::ProblemTables g_tables; }
+// Fills the tables as create does; the tables stay here for hostcheck_problem_tables_get.  Returns create's code; *why: the TablesRefusal;
+// scalars9: P, Pc, NX, Kmax, maxN, maxCN, sumKfine, maxXb, maxVb
+extern "C" int hostcheck_problem_tables_fill(double rho, double grid_res, double vel_max, double safe_margin, int B, const int *coarse_n, const double *ini_state,
+                                             const double *fin_state, const int *h_off, const double *h_rec, const int *v_off, const double *v_rec, int *why, int *scalars9) {
+    frx_config cfg = {};
+    cfg.rho = rho; cfg.grid_res = grid_res; cfg.vel_max = vel_max; cfg.safe_margin = safe_margin;
+    std::vector<frx::HostCand> cand;
+    frx::TablesRefusal w;
+    const int rc = frx::problem_tables_fill(cfg, rho > 0, B, coarse_n, ini_state, fin_state, h_off, h_rec, v_off, v_rec, cand, g_tables, &w);
+    *why = (int)w;
+    const frx::ProblemTables &t = g_tables;
+    const int s[9] = {t.P, t.Pc, t.NX, t.Kmax, t.maxN, t.maxCN, t.sumKfine, t.maxXb, t.maxVb};
+    for (int i = 0; i < 9; i++) scalars9[i] = s[i];
+    return rc;
+}
+// table `which` of the last fill, in the order ProblemTables declares them (0..14 ints: poff coff xoff boff cvoff dimT piece_hbeg piece_K piece_coarse piece_iv coarse_iv
+// coarse_fbeg wp_vbeg wp_nv wp_xbeg; 15..20 doubles: hrec horg vrec head tail hblk): returns its length, and copies it when out has room for cap elements
+extern "C" long long hostcheck_problem_tables_get(int which, void *out, long long cap) {
+    const frx::ProblemTables &t = g_tables;
+    const std::vector<int> *iv[15] = {&t.poff, &t.coff, &t.xoff, &t.boff, &t.cvoff, &t.dimT, &t.piece_hbeg, &t.piece_K, &t.piece_coarse, &t.piece_iv, &t.coarse_iv,
+                                      &t.coarse_fbeg, &t.wp_vbeg, &t.wp_nv, &t.wp_xbeg};
+    const std::vector<double> *dv[6] = {&t.hrec, &t.horg, &t.vrec, &t.head, &t.tail, &t.hblk};
+    if (which < 0 || which > 20) return -1;
+    if (which < 15) { const std::vector<int> &v = *iv[which]; if ((long long)v.size() <= cap && !v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(int)); return (long long)v.size(); }
+    const std::vector<double> &v = *dv[which - 15];
+    if ((long long)v.size() <= cap && !v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(double));
+    return (long long)v.size();
+}
+// launch_geometry_fill on bare maxima: in8 = maxN, maxCN, Kmax, P, maxXb, maxVb, qd_intervals, simds; forced: FRX_PENALTY_WAVES as a number.
+// out16 = lpp ppw pen_w ppg lds_fwd lds_bwd lds_pen lds_pen2 solver knot_threads pcr_steps lds_kfwd lds_kbwd, the verdict's refusal and banded_ok, maxXb
+extern "C" void hostcheck_launch_geometry(const int *in8, int forced, long long *out16) {
+    frx::ProblemTables t;
+    t.maxN = in8[0]; t.maxCN = in8[1]; t.Kmax = in8[2]; t.P = in8[3]; t.maxXb = in8[4]; t.maxVb = in8[5];
+    frx::LaunchGeom g = {};
+    frx::launch_geometry_fill(g, t, in8[6], in8[7], forced);
+    const frx::GeomVerdict v = frx::geometry_verdict(g.knot_threads, g.lds_kbwd, g.lds_fwd, g.lds_bwd, g.lds_pen);
+    const long long o[16] = {g.lpp, g.ppw, g.pen_w, g.ppg, (long long)g.lds_fwd, (long long)g.lds_bwd, (long long)g.lds_pen, (long long)g.lds_pen2, g.solver, g.knot_threads,
+                             g.pcr_steps, (long long)g.lds_kfwd, (long long)g.lds_kbwd, (long long)v.refusal, v.banded_ok, g.maxXb};
+    for (int i = 0; i < 16; i++) out16[i] = o[i];
+}
+extern "C" int hostcheck_knot_threads(int maxN) { return frx::knot_threads(maxN); }
+extern "C" int hostcheck_pcr_steps(int maxN) { return frx::pcr_steps(maxN); }
+extern "C" void hostcheck_penalty_waves(int lpp, int Kmax, int P, int simds, int forced, int *out2) { const frx::PenaltyWaves w = frx::penalty_waves(lpp, Kmax, P, simds, forced); out2[0] = w.pen_w; out2[1] = w.ppg; }
+extern "C" int hostcheck_eval_cluster_admitted(int G, int B, int cus, int fused_char, int local_ranks, int ndev) { return frx::eval_cluster_admitted(G, B, cus, (char)fused_char, local_ranks, ndev); }
+extern "C" void hostcheck_eval_solo_choice(int lds_solo, int solo_char, int min_B, int max_B, int *out3) {
+    const frx::SoloChoice c = frx::eval_solo_choice(lds_solo != 0, (char)solo_char, min_B, max_B);
+    out3[0] = c.eval_solo; out3[1] = c.min_B; out3[2] = c.max_B;
+}
+
 // ---- the mailbox protocol against a thread that plays the clusters (resident_mailbox_main.cpp), for tests/test_resident_mailbox_cpu.py ----
 #define HOSTCHECK_LIBRARY
 #include "resident_mailbox_main.cpp"
