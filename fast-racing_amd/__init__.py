@@ -79,7 +79,7 @@ DEBUG_SYMBOLS = [
     "frx_debug_trace", "frx_resident_profile", "frx_debug_direction_log", "frx_debug_direction_log_read", "frx_debug_set_resident_retry",
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
     "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_eval_geometry", "frx_debug_eval_front", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
-    "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device", "frx_debug_dv_layout", "frx_debug_dv_round", "frx_debug_fold_rows",
+    "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device", "frx_debug_dv_layout", "frx_debug_dv_round", "frx_debug_fold_rows", "frx_debug_lane_exchange",
 ]
 
 # frx_trajectory_check (include/frx.h): fields of a row and flag bits
@@ -195,6 +195,7 @@ def lib():
         L.frx_trajectory_clearance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_debug_set_clear_chunk.argtypes = [C.c_void_p, C.c_int]
         L.frx_debug_fold_rows.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.frx_debug_lane_exchange.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_corridor_generate_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_corridor_generate_batch_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
@@ -240,6 +241,17 @@ def shader_clock(device: int = 0, ms: float = 2.0):
     a, b, c = C.c_double(), C.c_double(), C.c_double()
     _check(lib().frx_debug_shader_clock(device, C.c_double(ms), C.byref(a), C.byref(b), C.byref(c)))
     return a.value, b.value, c.value
+
+
+def lane_exchange(stride: int, values, device: int = 0):
+    """frx_debug_lane_exchange: one wave's neighbour exchange by `stride` lanes as the one-launch evaluation does it (lane_exchange, csrc/frx_wave.hpp).
+    values: 64 words of 64 bits (uint64 patterns, moved as they are) -> (below, above) with below[i] = values[i - stride], above[i] = values[i + stride];
+    a lane without a source lane holds anything."""
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    assert v.shape == (64,)
+    below, above = np.zeros(64, dtype=np.uint64), np.zeros(64, dtype=np.uint64)
+    _check(lib().frx_debug_lane_exchange(device, int(stride), v.ctypes.data, below.ctypes.data, above.ctypes.data))
+    return below, above
 
 
 def gcopter_lbfgs_params(rel_cost_tol: float, max_iterations: int = 0) -> LbfgsParams:

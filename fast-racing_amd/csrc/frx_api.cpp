@@ -1068,6 +1068,20 @@ int frx_debug_shader_clock(int device, double ms, double *mhz_min, double *mhz_m
     if (mhz_max) *mhz_max = hi;
     return FRX_OK;
 }
+int frx_debug_lane_exchange(int device, int stride, const void *in64, void *below64, void *above64) {
+    if (!in64 || !below64 || !above64) return fail(FRX_ERR_INVALID_ARG, "frx_debug_lane_exchange: null buffer");
+    if (stride != 1 && stride != 2 && stride != 4 && stride != 8 && stride != 16 && stride != 32) return fail(FRX_ERR_INVALID_ARG, "frx_debug_lane_exchange: stride in {1, 2, 4, 8, 16, 32}");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> buf;
+    if (buf.alloc(3 * 64) != hipSuccess) return fail(FRX_ERR_ALLOC, "lane exchange probe buffers");
+    HIP_TRY(hipMemset(buf.p, 0, sizeof(double) * 3 * 64));
+    HIP_TRY(hipMemcpy(buf.p, in64, sizeof(double) * 64, hipMemcpyHostToDevice));
+    HIP_TRY((hipError_t)frx::launch_lane_exchange_probe(stride, buf.p, buf.p + 64, buf.p + 128, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(below64, buf.p + 64, sizeof(double) * 64, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(above64, buf.p + 128, sizeof(double) * 64, hipMemcpyDeviceToHost));
+    return FRX_OK;
+}
 int frx_debug_compact_from_history(int m, int n, int hs, int bound, int newest, const double *S, const double *Y, double *rinv129, double *yy, double *vd) {
     if (!S || !Y || !rinv129 || !yy || !vd || m < 1 || m > 128 || n < 1 || hs < n || bound < 0 || bound > m || newest < 0 || newest >= m) return fail(FRX_ERR_INVALID_ARG, "frx_debug_compact_from_history: argument out of range");
     frx::compact_from_history(m, n, (size_t)hs, bound, newest, S, Y, 129, rinv129, yy, vd);

@@ -99,6 +99,7 @@ int launch_eval_cluster(const LaunchGeom &g, int B, const void *args_host, const
                         unsigned long long timeout_ticks, void *stream, unsigned *status_host = nullptr);
 // workgroups of k_eval_cluster a CU holds with lds_bytes of dynamic LDS (occupancy query of the runtime; 0 on error)
 int eval_cluster_blocks_per_cu(size_t lds_bytes);
+int launch_lane_exchange_probe(int stride, const double *in, double *below, double *above, void *stream);   // one wave of lane_exchange<stride> (frx_wave.hpp) on 64 device doubles; stride in {1, 2, 4, 8, 16, 32}
 int eval_cluster_raise_limit(size_t lds_bytes);                 // raises k_eval_cluster's dynamic-LDS limit on the current device (never lowers it)
 
 // One launch per evaluation for LARGE batches (frx_solo_kernel.hpp): one workgroup per candidate runs forward map, penalty integral and adjoint back to back.

@@ -137,4 +137,22 @@ int launch_eval_cluster(const LaunchGeom &g, int B, const void *args_host, const
         return (int)hipGetLastError();
     });
 }
+
+// Tests (frx_debug_lane_exchange): lane_exchange<S> of frx_wave.hpp on one wave, as compiled into this translation unit - in[64] -> below[64], above[64], 64-bit
+// patterns moved as they are (the kernel sees doubles, the test compares bits).
+template <int S> __global__ __launch_bounds__(64) void k_lane_exchange_probe(const double *__restrict__ in, double *__restrict__ below, double *__restrict__ above) {
+    const int lane = threadIdx.x;
+    double lo, hi;
+    lane_exchange<S>(in[lane], lo, hi);
+    below[lane] = lo; above[lane] = hi;
+}
+int launch_lane_exchange_probe(int stride, const double *in, double *below, double *above, void *stream) {
+    switch (stride) {
+#define FRX_LX_PROBE(S) case S: hipLaunchKernelGGL(k_lane_exchange_probe<S>, dim3(1), dim3(64), 0, (hipStream_t)stream, in, below, above); break;
+    FRX_LX_PROBE(1) FRX_LX_PROBE(2) FRX_LX_PROBE(4) FRX_LX_PROBE(8) FRX_LX_PROBE(16) FRX_LX_PROBE(32)
+#undef FRX_LX_PROBE
+    default: return (int)hipErrorInvalidValue;
+    }
+    return (int)hipGetLastError();
+}
 } // namespace frx

@@ -1077,6 +1077,21 @@ __device__ __forceinline__ void pcr_axis_step(double *rsb, int nrow, int kk, int
     r0 = n0; r1 = n1;
     if (act) { RS(buf ^ 1, ax, kk) = r0; RS(buf ^ 1, 3 + ax, kk) = r1; }
 }
+// The neighbours k -+ (1 << st) of (r0, r1) for one step of a lane = knot reduction, through lane_exchange (frx_wave.hpp) instead of four shuffles: the adjoint solve
+// of the one-launch evaluation's leader, whose six steps are unrolled - the stride is a compile-time constant of each case and the switch folds away.  (Under a step
+// counted at run time - the axis waves' loop of forward_knot_body - the switch is a branch into six copies of the step's exchange, each run once per launch:
+// measured 0.3 us SLOWER per launch there, with either exchange inside the copies, and left as the one rolled step on shuffles; profiles/NOTES.md.)
+// Same values as the shuffles in every lane that has the neighbour; the other lanes are masked by the caller (inlo / inhi).  All 64 lanes enabled.
+__device__ __forceinline__ void pcr_neighbours_reg(int st, double r0, double r1, double &l0r, double &l1r, double &h0r, double &h1r) {
+    switch (st) {
+    case 0: lane_exchange<1>(r0, l0r, h0r); lane_exchange<1>(r1, l1r, h1r); break;
+    case 1: lane_exchange<2>(r0, l0r, h0r); lane_exchange<2>(r1, l1r, h1r); break;
+    case 2: lane_exchange<4>(r0, l0r, h0r); lane_exchange<4>(r1, l1r, h1r); break;
+    case 3: lane_exchange<8>(r0, l0r, h0r); lane_exchange<8>(r1, l1r, h1r); break;
+    case 4: lane_exchange<16>(r0, l0r, h0r); lane_exchange<16>(r1, l1r, h1r); break;
+    default: lane_exchange<32>(r0, l0r, h0r); lane_exchange<32>(r1, l1r, h1r); break;      // (step 5: a 64-lane reduction has no seventh)
+    }
+}
 // Right-hand sides alone with the multipliers in pw (the adjoint solve of <= 64 pieces; all 256 threads call it): RS(0, ..) holds the
 // right-hand side, the solution goes to KV / KA.  Lane = knot, so the neighbours k -+ s are lane shifts: the exchange goes through
 // the LDS crossbar (ds_bpermute, no memory, no barrier) and the three axis waves run their steps without meeting anyone.
@@ -2399,11 +2414,15 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
                 if (st < nst) {
                     const int s = 1 << st;
                     const bool inlo = act && kk - s >= 1, inhi = act && kk + s <= N - 1;
-                    const double l0r = __shfl_up(r0, s, 64), l1r = __shfl_up(r1, s, 64), h0r = __shfl_down(r0, s, 64), h1r = __shfl_down(r1, s, 64);
+                    double l0r, l1r, h0r, h1r;
+                    if constexpr (HOTR) pcr_neighbours_reg(st, r0, r1, l0r, l1r, h0r, h1r);    // (EvalHandoff, transposed: the exchange in registers where a stride has such a form)
+                    else { l0r = __shfl_up(r0, s, 64); l1r = __shfl_up(r1, s, 64); h0r = __shfl_down(r0, s, 64); h1r = __shfl_down(r1, s, 64); }
                     const double l0 = inlo ? l0r : 0.0, l1 = inlo ? l1r : 0.0, h0 = inhi ? h0r : 0.0, h1 = inhi ? h1r : 0.0;
                     const double n0 = r0 - (ab[st][0] * l0 + ab[st][1] * l1) - (ab[st][4] * h0 + ab[st][5] * h1);    // pcr_rhs_step
                     const double n1 = r1 - (ab[st][2] * l0 + ab[st][3] * l1) - (ab[st][6] * h0 + ab[st][7] * h1);
                     r0 = n0; r1 = n1;
+                    // (EvalHandoff's stamps: 34 + st = axis wave 1 has step st of its solve - the 100 MHz counter, as 74)
+                    if constexpr (HOST && !CHN) { if (ho->st && k == 64) { asm volatile("" :: "v"(r0), "v"(r1)); ho->st[34 + st] = (long long)wall_clock64(); } }
                 }
             if (act) { muv = Di[0] * r0 + Di[1] * r1; mua = Di[2] * r0 + Di[3] * r1; }
         } else {

@@ -77,6 +77,43 @@ __device__ __forceinline__ double lane_down1(double v) {          // lane i <- l
     return __hiloint2double(hi, lo);
 }
 
+// Neighbour exchange by S lanes in BOTH directions at once: from_below[i] = v[i - S], from_above[i] = v[i + S] - the exchange of one step of the
+// parallel cyclic reduction, whose chain otherwise waits for four 64-bit shuffles per step (8 ds_bpermute_b32, their lane addresses, an lgkmcnt wait).
+// The two 32-bit halves move unchanged.  A lane WITHOUT a source lane holds anything afterwards: the caller masks it.  All 64 lanes must be enabled.
+//   S = 1, 2   wave_shr:1 / wave_shl:1 DPP moves, chained for 2
+//   S = 16     v_permlane16_swap(v, v) = rows (0,0,2,2) and (1,1,3,3); v_permlane32_swap of the two = rows (0,0,1,1) and (2,2,3,3); one select each
+//   S = 32     v_permlane32_swap(v, v) = (lower half twice, upper half twice): both directions, no select
+//   S = 4, 8   the shuffles: four chained wave shifts measured level with them on the solve's step stamps, eight slower (profiles/NOTES.md)
+// FRX_LX_REG_STRIDES (a build's -D, for measuring one form against the other): the strides that take their register form; 4 and 8 in it = chained wave shifts.
+#ifndef FRX_LX_REG_STRIDES
+#define FRX_LX_REG_STRIDES (1 | 2 | 16 | 32)
+#endif
+template <int S> __device__ __forceinline__ void lane_exchange(double v, double &from_below, double &from_above) {
+    static_assert(S == 1 || S == 2 || S == 4 || S == 8 || S == 16 || S == 32, "a stride of the 64-lane reduction");
+    if constexpr (S <= 8 && (FRX_LX_REG_STRIDES & S)) {
+        from_below = lane_up1(v); from_above = lane_down1(v);
+#pragma unroll
+        for (int i = 1; i < S; i++) { from_below = lane_up1(from_below); from_above = lane_down1(from_above); }
+    } else if constexpr (S == 16 && (FRX_LX_REG_STRIDES & 16)) {
+        const unsigned row = (threadIdx.x >> 4) & 3;
+        unsigned w[2] = {(unsigned)__double2loint(v), (unsigned)__double2hiint(v)}, lo[2], hi[2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const auto r = __builtin_amdgcn_permlane16_swap(w[h], w[h], false, false);     // r[0] = rows (0,0,2,2), r[1] = rows (1,1,3,3)
+            const auto q = __builtin_amdgcn_permlane32_swap(r[0], r[1], false, false);     // q[0] = rows (0,0,1,1), q[1] = rows (2,2,3,3)
+            lo[h] = row == 3 ? r[0] : q[0];                                                // rows (-,0,1,2)
+            hi[h] = row == 0 ? r[1] : q[1];                                                // rows (1,2,3,-)
+        }
+        from_below = __hiloint2double((int)lo[1], (int)lo[0]); from_above = __hiloint2double((int)hi[1], (int)hi[0]);
+    } else if constexpr (S == 32 && (FRX_LX_REG_STRIDES & 32)) {
+        const auto a = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(v), (unsigned)__double2loint(v), false, false);
+        const auto b = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(v), (unsigned)__double2hiint(v), false, false);
+        from_below = __hiloint2double((int)b[0], (int)a[0]); from_above = __hiloint2double((int)b[1], (int)a[1]);
+    } else {
+        from_below = __shfl_up(v, S, 64); from_above = __shfl_down(v, S, 64);
+    }
+}
+
 // sum over the 4 lanes of a quad, result in every lane of the quad (two quad permutes; replaces two ds_bpermute round trips)
 __device__ __forceinline__ double quad_sum(double v) {
     v += dpp_mov<0xB1>(v);          // quad_perm [1,0,3,2]

@@ -150,6 +150,10 @@ int frx_debug_map_blocked_device(int device, const frx_voxel_map *map, int n_pai
  * milliseconds): shader cycles per tick of the constant 100 MHz counter, as MHz - minimum, mean and maximum over the CUs' workgroups.  A round of the resident kernel
  * is a chain of dependent instructions: its time is cycles / this clock, which is what differs between the boxes of a pool running the same code object. */
 int frx_debug_shader_clock(int device, double ms, double *mhz_min, double *mhz_mean, double *mhz_max);
+/* Tests: the neighbour exchange of the one-launch evaluation's reduction steps (lane_exchange<stride>, fast-racing_amd/csrc/frx_wave.hpp) on one wave of the device:
+ * in64[64] -> below64[i] = in64[i - stride], above64[i] = in64[i + stride], stride in {1, 2, 4, 8, 16, 32}; 64-bit words moved as they are (host buffers).  A lane
+ * without a source lane holds anything. */
+int frx_debug_lane_exchange(int device, int stride, const void *in64, void *below64, void *above64);
 /* where the resident plan's mailboxes live: out4 = {NUMA node of the command mailbox's page, of the result mailbox's page, the device's NUMA node, the caller's CPU}; -1 = unknown */
 int frx_debug_mailbox_numa(const frx_problem *p, int *out4);
 
