@@ -17,6 +17,7 @@
 #include "frx_host_setup.hpp"
 #include "frx_internal.hpp"
 #include "frx_lbfgs.hpp"
+#include "frx_plan_route.hpp"
 
 // records the text frx_last_error() returns on this thread (one definition of the thread-local string: frx_api.cpp)
 inline int fail(int code, const std::string &msg) { return frx::set_error(code, msg); }
@@ -165,7 +166,7 @@ struct frx_problem {
     bool banded_ok = true;
     bool penalty_only = false;              // frx_penalty_problem_create: the inner boundary alone (no variables, no waypoint polytopes: only frx_penalty_eval[_device] apply)
     int lbfgs_mode = 0;                     // 0 = device vectors (default), 1 = host vectors
-    double stats[4] = {0, 0, 0, 0};
+    frx::PlanTimes stats;                   // frx_optimize_stats: what the last plan took
 };
 
 namespace frx {

@@ -1,6 +1,8 @@
 // The plan drivers behind frx_optimize: host vectors (drive_batch), device vectors with one launch per stage (optimize_device_vectors), and the resident round
-// kernel (optimize_resident: one launch per plan, frx_resident_plan.hpp decides its geometry, frx_resident_mailbox.hpp talks to its clusters), with the take-over
-// between the last two.  Host-only translation unit (g++), built with the CPU oracle's floating-point flags like the rest of the host side.
+// kernel (optimize_resident: one launch per plan, frx_resident_plan.hpp decides its geometry, frx_resident_mailbox.hpp talks to its clusters).  Which of them a plan
+// takes, the second chance of failed candidates and the take-over between the last two are decided in frx_plan_route.hpp, from the environment as read once per
+// frx_optimize call (plan_switches_from_env); this file plays the drivers.  Host-only translation unit (g++), built with the CPU oracle's floating-point flags like
+// the rest of the host side.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -26,6 +28,7 @@
 #include "frx_handle.hpp"
 #include "frx_host_pool.hpp"
 #include "frx_compact.hpp"
+#include "frx_plan_route.hpp"
 #include "frx_resident_plan.hpp"
 #include "frx_resident_mailbox.hpp"
 
@@ -49,7 +52,7 @@ static int wait_stream(hipStream_t stream, double timeout_ms, const char *what) 
 // The batched driver shared by frx_optimize (device evaluator) and frx_lbfgs_minimize_batch (callback evaluator).
 template <class EvalAll>
 static int drive_batch(int count, const int *x_off, double *x, double *g, double *f, const frx_lbfgs_params &pm, int n_threads,
-                       int *status, int *iters, int *evals, double *f_out, double *stats, EvalAll &&eval_all) {
+                       int *status, int *iters, int *evals, double *f_out, frx::PlanTimes *stats, EvalAll &&eval_all) {
     std::vector<frx::Solver> sv(count);
     frx::SpinPool pool(std::min(n_threads, count));
     // allocation + first touch of each solver's history by its owning (pinned) worker
@@ -73,7 +76,7 @@ static int drive_batch(int count, const int *x_off, double *x, double *g, double
         t_host += ms_since(th);
         rounds++;
     }
-    if (stats) { stats[0] = ms_since(t0); stats[1] = t_eval; stats[2] = t_host; stats[3] = (double)rounds; }
+    if (stats) *stats = {ms_since(t0), t_eval, t_host, (double)rounds};
     for (int i = 0; i < count; i++) {
         if (status) status[i] = sv[i].status();
         if (iters) iters[i] = sv[i].iterations();
@@ -83,20 +86,144 @@ static int drive_batch(int count, const int *x_off, double *x, double *g, double
     return FRX_OK;
 }
 
-// Stragglers of a per-stage batch that continue on the resident round kernel.  A per-stage round costs four launches whose first is a
-// one-CU recursion over the candidate's history (~85 us per round however few candidates are left), a resident round ~25 us - and a batch waits for its
-// slowest candidate (one infeasible scenario that wanders 16 673 evaluations held 511 finished ones hostage for a second, profiles/r04_bench_montecarlo4096.json).
-// When no more than `capacity` candidates are still running, optimize_device_vectors stops and hands them over AS THEY ARE: their solver state machines
-// (the host's side of the plan: line search, stop tests, counters), their pending commands, and where their history stands on the device.
-struct TakeOver {
-    int capacity = 0;                     // in: hand over when at most this many candidates are still running (0: never)
-    long not_before = 1;                  // in: ... and this many rounds have run (FRX_MIGRATE_AT: tests force an early hand-over)
-    std::vector<int> cand;                // out: the candidates, in cluster order
-    std::vector<frx::SolverDV> sv;        // out: their solvers (pending command inside)
-    std::vector<int> newest, bound;       // out: newest slot / number of pairs of their history rows on the device
-    std::vector<double> f_last;           // out: objective value of their last evaluation
-    double ms = 0.0, ms_dev = 0.0, ms_host = 0.0; long rounds = 0;   // out: what the per-stage part took
+using frx::TakeOver;
+
+// the environment of THIS frx_optimize call (tests and A/B runs change it between two plans of one process)
+static frx::PlanSwitches plan_switches_from_env() {
+    frx::PlanSwitches sw;
+    sw.lbfgs_host = frx::env_is("FRX_LBFGS", 'h');
+    sw.resident_off = frx::env_off("FRX_RESIDENT");
+    if (const char *e = std::getenv("FRX_RESIDENT_RETRY")) sw.resident_retry = (unsigned char)e[0];
+    sw.takeover_off = frx::env_off("FRX_TAKEOVER");
+    sw.resident_queue_off = frx::env_off("FRX_RESIDENT_QUEUE");
+    if (const char *e = std::getenv("FRX_HOST_THREADS")) { sw.host_threads_set = true; sw.host_threads = std::atoi(e); }
+    sw.zero_copy = !frx::env_off("FRX_ZERO_COPY");
+    sw.round_timeout_ms = round_timeout_ms();
+    if (const char *e = std::getenv("FRX_DV_GEOM")) { sw.dv_geom_set = true; sw.dv_geom = e; }
+    sw.dv_tight = !frx::env_off("FRX_DV_TIGHT");
+    sw.mailbox = !frx::env_off("FRX_MAILBOX");
+    if (const char *e = std::getenv("FRX_SKIP_INACTIVE")) sw.skip_inactive = e[0] != '0';
+    if (const char *e = std::getenv("FRX_DEBUG_DROP_ROUND")) sw.drop_round = std::atol(e);
+    sw.trace = std::getenv("FRX_TRACE") != nullptr;
+    return sw;
+}
+
+// ---- device vectors, one launch per stage ----
+
+// vectors, history and the command / result mailboxes of the per-stage rounds at history length m and row stride HS, the history zeroed; 1: the history does not fit
+static int reserve_dv_buffers(frx_problem *p, int m, size_t HS) {
+    if (p->dv_mem == m && p->dv_hs == HS) return FRX_OK;
+    const int B = p->B;
+    hipError_t e;
+    p->dv_mem = 0; p->dv_hs = 0;
+    const size_t hist = (size_t)m * B * HS;
+    NumaScope numa_alloc(p->device);                                          // command / result mailboxes of the per-stage rounds: pages from the device's NUMA node
+    if ((e = p->d_xp.reserve(p->NX)) != hipSuccess || (e = p->d_gp.reserve(p->NX)) != hipSuccess || (e = p->d_dir.reserve(p->NX)) != hipSuccess ||
+        (e = p->d_S.reserve(hist)) != hipSuccess || (e = p->d_Y.reserve(hist)) != hipSuccess ||
+        (e = p->d_ys.reserve((size_t)B * m)) != hipSuccess || (e = p->d_gt.reserve((size_t)B * m * 4)) != hipSuccess || (e = p->h_cmd.reserve(B)) != hipSuccess || (e = p->h_res.reserve(B)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (e == hipErrorOutOfMemory) {                                       // the history does not fit: the host-vector solver needs no device history
+            p->d_S.release(); p->d_Y.release();
+            return 1;
+        }
+        return fail(FRX_ERR_ALLOC, std::string("device-vector L-BFGS buffers: ") + hipGetErrorString(e));
+    }
+    // zero padding of the history slices is relied upon by the unconditional 16-byte loads of k_lbfgs_pre; on the handle's
+    // stream, like every consumer (the stream is non-blocking: the null stream would not order against it)
+    if ((e = hipMemsetAsync(p->d_S.p, 0, sizeof(double) * hist, p->stream)) != hipSuccess || (e = hipMemsetAsync(p->d_Y.p, 0, sizeof(double) * hist, p->stream)) != hipSuccess)
+        return fail(FRX_ERR_HIP, hipGetErrorString(e));
+    p->dv_mem = m; p->dv_hs = HS;
+    return FRX_OK;
+}
+
+// the tap, the inactive-skip flags and the mailbox are the handle's only while a per-stage plan runs: cleared on every exit
+struct TapGuard { frx_problem *q; ~TapGuard() { q->tap = frx::TapLaunch(); q->dp.cand_active = nullptr; q->dp.piece_active = nullptr; } };
+
+// With the knot/PCR kernels the reductions the line search needs ride on k_backward_knot (LineSearchTap; the banded-LU kernels keep the separate k_lbfgs_post):
+// arms the tap, the flags that let the objective kernels skip inactive candidates, and (mailbox) the round's completion post in mapped memory
+static int arm_tap(frx_problem *p, const frx::PlanSwitches &sw, bool mailbox, frx::DvLaunch &dv) {
+    const int B = p->B;
+    hipError_t e;
+    if (!p->d_flags.p && (e = p->d_flags.alloc(B)) != hipSuccess) return fail(FRX_ERR_ALLOC, hipGetErrorString(e));
+    dv.dflags = p->d_flags.p;
+    p->tap.d = p->d_dir.p; p->tap.flags = p->d_flags.p; p->tap.res = p->h_res.p;
+    if (frx::skip_inactive(sw.skip_inactive, B)) {
+        if (!p->d_pflags.p && (e = p->d_pflags.alloc(p->P)) != hipSuccess) return fail(FRX_ERR_ALLOC, hipGetErrorString(e));
+        dv.pflags = p->d_pflags.p; dv.poff = p->d_poff.p;
+        p->dp.cand_active = p->d_flags.p; p->dp.piece_active = p->d_pflags.p;
+    }
+    if (!mailbox) return FRX_OK;
+    NumaScope numa_alloc(p->device);
+    if (!p->d_arrive.p && ((e = p->d_arrive.alloc(1)) != hipSuccess || (e = p->h_flag.alloc(1)) != hipSuccess)) return fail(FRX_ERR_ALLOC, hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(p->d_arrive.p, 0, sizeof(unsigned), p->stream));
+    p->h_flag.p[0] = 0;
+    p->tap.arrive = p->d_arrive.p; p->tap.flag = p->h_flag.p; p->tap.round = 0;
+    return FRX_OK;
+}
+
+// Completion of a round: the last workgroup of k_backward_knot posts the round number in mapped memory (LineSearchTap).  The spin is bounded: a stream that drains
+// without the post (arrival counter out of step, e.g. a launch that never happened) is reported at once, anything else after the deadline; the counters are
+// re-initialised by the next plan.
+static int wait_round_post(frx_problem *p, double timeout_ms) {
+    const auto tw = clk::now();
+    for (unsigned spins = 1;; spins++) {
+        if (*(volatile unsigned *)p->h_flag.p == p->tap.round) return FRX_OK;
+        if ((spins & 0x3FFF) == 0) {
+            const hipError_t q = hipStreamQuery(p->stream);
+            if (q == hipSuccess) {
+                if (*(volatile unsigned *)p->h_flag.p == p->tap.round) return FRX_OK;
+                return fail(FRX_ERR_TIMEOUT, "round " + std::to_string(p->tap.round) + ": the stream drained but completion was never posted (arrival counter out of step)");
+            }
+            if (q != hipErrorNotReady) return fail(FRX_ERR_HIP, std::string("device round failed: ") + hipGetErrorString(q));
+            if (ms_since(tw) > timeout_ms) return fail(FRX_ERR_TIMEOUT, "round " + std::to_string(p->tap.round) + " did not complete within FRX_ROUND_TIMEOUT_MS");
+        }
+        __builtin_ia32_pause();
+    }
+}
+// the end of a round: its post when there is one, else the drained stream; after an error a bounded drain, the first error kept
+static int wait_round(frx_problem *p, bool posted, double timeout_ms) {
+    const int rc = posted ? wait_round_post(p, timeout_ms) : wait_stream(p->stream, timeout_ms, "device round");
+    if (rc == FRX_OK) return rc;
+    const std::string keep = frx_last_error();
+    (void)wait_stream(p->stream, timeout_ms, "device round");
+    return fail(rc, keep);
+}
+
+// a per-stage plan's host state: a solver per candidate, and where every candidate's history stands on the device (for a hand-over)
+struct DvPlan {
+    std::vector<frx::SolverDV> sv;
+    std::vector<int> newest, bound;
+    std::vector<double> f_last;
+    explicit DvPlan(int B) : sv(B), newest(B, 0), bound(B, 0), f_last(B, 0.0) {}
 };
+
+// the round's results to the solvers, which write their next commands (FRX_TRACE: candidate 0's row)
+static void feed_round(frx_problem *p, DvPlan &pl, bool tracing) {
+    for (int b = 0; b < p->B; b++) {
+        frx::DvCommand &c = p->h_cmd.p[b];
+        const bool evaluated = (c.flags & frx::DV_EVAL) != 0;
+        if (!evaluated) { c.flags = 0; continue; }                         // a RESTORE has been executed
+        if (tracing && b == 0) { const frx::DvResult &r = p->h_res.p[b]; const double row[7] = {(double)c.flags, c.step, r.f, r.dg, r.dginit, r.xx, r.gg}; p->trace.insert(p->trace.end(), row, row + 7); }
+        pl.f_last[b] = p->h_res.p[b].f;
+        if (pl.sv[b].saw_nonfinite(p->h_res.p[b].f)) pl.sv[b].give_up(frx::LBERR_ROUNDING); else pl.sv[b].feed(p->h_res.p[b]);
+    }
+}
+
+// the plan's results from the staged x and the solvers - or, of a candidate that is handed over (take: still running), its solver, pending command and history position
+static void collect_or_hand_over(const frx_problem *p, const DvPlan &pl, const std::vector<char> *only, TakeOver *take, const frx::PlanArrays &out) {
+    for (int b = 0; b < p->B; b++) {
+        if (only && !(*only)[b]) continue;
+        if (take && p->h_cmd.p[b].flags != 0) {
+            take->cand.push_back(b); take->sv.push_back(pl.sv[b]); take->newest.push_back(pl.newest[b]); take->bound.push_back(pl.bound[b]); take->f_last.push_back(pl.f_last[b]);
+            continue;
+        }
+        std::memcpy(out.x + p->xoff[b], p->h_x.p + p->xoff[b], sizeof(double) * (p->xoff[b + 1] - p->xoff[b]));
+        out.status[b] = pl.sv[b].status();
+        if (out.iters) out.iters[b] = pl.sv[b].iterations();
+        if (out.evals) out.evals[b] = pl.sv[b].evaluations();
+        if (out.objective) out.objective[b] = pl.sv[b].value();
+    }
+}
 
 // Device-vector optimisation: the host runs one SolverDV (scalars + decisions) per candidate, the device owns every
 // vector.  A round = k_lbfgs_pre (history update + two-loop recursion for candidates that just accepted a step, then the
@@ -104,157 +231,67 @@ struct TakeOver {
 // come back per candidate, through mapped host memory.
 // `only` (optional, [B]): candidates with only[b] == 0 take no part - their x, status, counters and objective are left untouched
 // (used to re-run, on this path, candidates that failed on the resident kernel).
-// `take` (optional): see TakeOver; returns 2 when the candidates still running were handed over.
-static int optimize_device_vectors(frx_problem *p, const frx_lbfgs_params &pm, double *x, int *status, int *iters, int *evals,
-                                   double *objective, const std::vector<char> *only = nullptr, TakeOver *take = nullptr) {
+// `take` (optional): see TakeOver; returns 2 when the candidates still running were handed over.  1: the caller falls back to host vectors.
+static int optimize_device_vectors(frx_problem *p, const frx_lbfgs_params &pm, const frx::PlanSwitches &sw, const frx::PlanArrays &out,
+                                   const std::vector<char> *only = nullptr, TakeOver *take = nullptr) {
     const int B = p->B, m = pm.mem_size;
-    // k_lbfgs_pre geometry (frx::dv_geometry).  FRX_DV_GEOM=E,W,PF,BLK overrides (experiments).
-    int E = 0, W = 0, PF = 0, BLK = 4;
-    frx::dv_geometry(p->geo.maxXb, &E, &W, &PF);
-    if (const char *gs = std::getenv("FRX_DV_GEOM")) {
-        int e, w, pf, blk;
-        if (std::sscanf(gs, "%d,%d,%d,%d", &e, &w, &pf, &blk) == 4 && p->geo.maxXb <= 64 * w * e) { E = e; W = w; PF = pf; BLK = blk; }
-    }
-    if (E == 0 || m > 512 || m < 1) return 1;                                  // caller falls back to host vectors
-    // rows as long as the longest candidate's vector needs (FRX_DV_TIGHT=0: the full 64 W E of round 5 - A/B)
-    const size_t HS = frx::dv_row_stride(p->geo.maxXb, E, W, !frx::env_off("FRX_DV_TIGHT"));
-    hipError_t e;
-    if (p->dv_mem != m || p->dv_hs != HS) {
-        p->dv_mem = 0; p->dv_hs = 0;
-        const size_t hist = (size_t)m * B * HS;
-        NumaScope numa_alloc(p->device);                                          // command / result mailboxes of the per-stage rounds: pages from the device's NUMA node
-        if ((e = p->d_xp.reserve(p->NX)) != hipSuccess || (e = p->d_gp.reserve(p->NX)) != hipSuccess || (e = p->d_dir.reserve(p->NX)) != hipSuccess ||
-            (e = p->d_S.reserve(hist)) != hipSuccess || (e = p->d_Y.reserve(hist)) != hipSuccess ||
-            (e = p->d_ys.reserve((size_t)B * m)) != hipSuccess || (e = p->d_gt.reserve((size_t)B * m * 4)) != hipSuccess || (e = p->h_cmd.reserve(B)) != hipSuccess || (e = p->h_res.reserve(B)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (e == hipErrorOutOfMemory) {                                       // the history does not fit: the host-vector solver needs no device history
-                p->d_S.release(); p->d_Y.release();
-                return 1;
-            }
-            return fail(FRX_ERR_ALLOC, std::string("device-vector L-BFGS buffers: ") + hipGetErrorString(e));
-        }
-        // zero padding of the history slices is relied upon by the unconditional 16-byte loads of k_lbfgs_pre; on the handle's
-        // stream, like every consumer (the stream is non-blocking: the null stream would not order against it)
-        if ((e = hipMemsetAsync(p->d_S.p, 0, sizeof(double) * hist, p->stream)) != hipSuccess || (e = hipMemsetAsync(p->d_Y.p, 0, sizeof(double) * hist, p->stream)) != hipSuccess)
-            return fail(FRX_ERR_HIP, hipGetErrorString(e));
-        p->dv_mem = m; p->dv_hs = HS;
-    }
+    const frx::DvPreGeometry geom = frx::dv_pre_geometry(p->geo.maxXb, sw);
+    if (geom.E == 0 || m > 512 || m < 1) return 1;
+    const size_t HS = frx::dv_row_stride(p->geo.maxXb, geom.E, geom.W, sw.dv_tight);   // rows as long as the longest candidate's vector needs
+    const int rc_buf = reserve_dv_buffers(p, m, HS);
+    if (rc_buf != FRX_OK) return rc_buf;
     frx::DvLaunch dv;
     dv.xoff = p->d_xoff.p; dv.x = p->d_x.p; dv.g = p->d_g.p; dv.xp = p->d_xp.p; dv.gp = p->d_gp.p; dv.d = p->d_dir.p;
-    dv.S = p->d_S.p; dv.Y = p->d_Y.p; dv.ys = p->d_ys.p; dv.gt = p->d_gt.p; dv.ld = (size_t)p->NX; dv.hs = HS; dv.m = m; dv.B = B; dv.E = E; dv.W = W; dv.PF = PF; dv.BLK = BLK;
-    std::memcpy(p->h_x.p, x, sizeof(double) * p->NX);
+    dv.S = p->d_S.p; dv.Y = p->d_Y.p; dv.ys = p->d_ys.p; dv.gt = p->d_gt.p; dv.ld = (size_t)p->NX; dv.hs = HS; dv.m = m; dv.B = B; dv.E = geom.E; dv.W = geom.W; dv.PF = geom.PF; dv.BLK = geom.BLK;
+    std::memcpy(p->h_x.p, out.x, sizeof(double) * p->NX);
     HIP_TRY(hipMemcpyAsync(p->d_x.p, p->h_x.p, sizeof(double) * p->NX, hipMemcpyHostToDevice, p->stream));
     HIP_TRY(hipMemsetAsync(p->d_ys.p, 0, sizeof(double) * (size_t)B * m, p->stream));
     HIP_TRY(hipMemsetAsync(p->d_gt.p, 0, sizeof(double) * (size_t)B * m * 4, p->stream));
-    std::vector<frx::SolverDV> sv(B);
+    DvPlan pl(B);
     for (int b = 0; b < B; b++) {
-        sv[b].start(p->xoff[b + 1] - p->xoff[b], pm, p->h_cmd.p + b);
-        if (only && !(*only)[b]) sv[b].give_up(0);                              // not part of this run
+        pl.sv[b].start(p->xoff[b + 1] - p->xoff[b], pm, p->h_cmd.p + b);
+        if (only && !(*only)[b]) pl.sv[b].give_up(0);                          // not part of this run
     }
-    const double timeout_ms = round_timeout_ms();
-    // with the knot/PCR kernels the reductions the line search needs ride on k_backward_knot (LineSearchTap); the banded-LU
-    // kernels keep the separate k_lbfgs_post
-    const bool fused_post = p->geo.solver == frx::SOLVER_KNOT_PCR;
-    struct TapGuard { frx_problem *q; ~TapGuard() { q->tap = frx::TapLaunch(); q->dp.cand_active = nullptr; q->dp.piece_active = nullptr; } } tap_guard{p};
-    const bool mailbox = fused_post && !frx::env_off("FRX_MAILBOX");
-    if (fused_post) {
-        if (!p->d_flags.p && (e = p->d_flags.alloc(B)) != hipSuccess) return fail(FRX_ERR_ALLOC, hipGetErrorString(e));
-        dv.dflags = p->d_flags.p;
-        p->tap.d = p->d_dir.p; p->tap.flags = p->d_flags.p; p->tap.res = p->h_res.p;
-        // large batches: the objective kernels skip candidates that are not being evaluated this round (finished ones above all)
-        const char *sk = std::getenv("FRX_SKIP_INACTIVE");
-        if (sk ? sk[0] != '0' : B > 64) {
-            if (!p->d_pflags.p && (e = p->d_pflags.alloc(p->P)) != hipSuccess) return fail(FRX_ERR_ALLOC, hipGetErrorString(e));
-            dv.pflags = p->d_pflags.p; dv.poff = p->d_poff.p;
-            p->dp.cand_active = p->d_flags.p; p->dp.piece_active = p->d_pflags.p;
-        }
-    }
-    if (mailbox) {
-        NumaScope numa_alloc(p->device);
-        if (!p->d_arrive.p && ((e = p->d_arrive.alloc(1)) != hipSuccess || (e = p->h_flag.alloc(1)) != hipSuccess)) return fail(FRX_ERR_ALLOC, hipGetErrorString(e));
-        HIP_TRY(hipMemsetAsync(p->d_arrive.p, 0, sizeof(unsigned), p->stream));
-        p->h_flag.p[0] = 0;
-        p->tap.arrive = p->d_arrive.p; p->tap.flag = p->h_flag.p; p->tap.round = 0;
-    }
-    // completion of a round: the last workgroup of k_backward_knot posts the round number in mapped memory (LineSearchTap).
-    // The spin is bounded: a stream that drains without the post (arrival counter out of step, e.g. a launch that never
-    // happened) is reported at once, anything else after the deadline; the counters are re-initialised by the next call.
-    auto wait_round = [&](bool evaluated) -> int {
-        if (!mailbox || !evaluated) return wait_stream(p->stream, timeout_ms, "device round");
-        const auto tw = clk::now();
-        for (unsigned spins = 1;; spins++) {
-            if (*(volatile unsigned *)p->h_flag.p == p->tap.round) return FRX_OK;
-            if ((spins & 0x3FFF) == 0) {
-                const hipError_t q = hipStreamQuery(p->stream);
-                if (q == hipSuccess) {
-                    if (*(volatile unsigned *)p->h_flag.p == p->tap.round) return FRX_OK;
-                    return fail(FRX_ERR_TIMEOUT, "round " + std::to_string(p->tap.round) + ": the stream drained but completion was never posted (arrival counter out of step)");
-                }
-                if (q != hipErrorNotReady) return fail(FRX_ERR_HIP, std::string("device round failed: ") + hipGetErrorString(q));
-                if (ms_since(tw) > timeout_ms) return fail(FRX_ERR_TIMEOUT, "round " + std::to_string(p->tap.round) + " did not complete within FRX_ROUND_TIMEOUT_MS");
-            }
-            __builtin_ia32_pause();
-        }
-    };
-    // fault injection (tests): FRX_DEBUG_DROP_ROUND=k leaves k_backward_knot out of round k, so that round's completion is never posted
-    const long drop_round = [] { const char *e = std::getenv("FRX_DEBUG_DROP_ROUND"); return e ? std::atol(e) : -1L; }();
+    const bool fused_post = p->geo.solver == frx::SOLVER_KNOT_PCR, mailbox = fused_post && sw.mailbox;
+    TapGuard tap_guard{p};
+    if (fused_post) { const int rc_tap = arm_tap(p, sw, mailbox, dv); if (rc_tap != FRX_OK) return rc_tap; }
     double t_dev = 0.0, t_host = 0.0;
     long rounds = 0;
-    const bool tracing = std::getenv("FRX_TRACE") != nullptr;
     p->trace.clear();
-    std::vector<int> h_newest(B, 0), h_bound(B, 0);                            // where every candidate's history stands on the device (for a hand-over)
-    std::vector<double> h_flast(B, 0.0);
     bool handed_over = false;
     const auto t0 = clk::now();
     for (;;) {
-        bool any_eval = false, any_cmd = false;
+        bool any_eval = false;
         int running = 0;
-        for (int b = 0; b < B; b++) { any_eval |= (p->h_cmd.p[b].flags & frx::DV_EVAL) != 0; any_cmd |= p->h_cmd.p[b].flags != 0; running += p->h_cmd.p[b].flags != 0; }
-        if (!any_cmd) break;
+        for (int b = 0; b < B; b++) { any_eval |= (p->h_cmd.p[b].flags & frx::DV_EVAL) != 0; running += p->h_cmd.p[b].flags != 0; }
+        if (running == 0) break;
         if (take && take->capacity > 0 && running <= take->capacity && rounds >= take->not_before) { handed_over = true; break; }   // the rest continues on the resident kernel
         for (int b = 0; b < B; b++)
-            if (p->h_cmd.p[b].flags & frx::DV_ADVANCE) { h_newest[b] = p->h_cmd.p[b].slot; h_bound[b] = p->h_cmd.p[b].bound; }    // the pair this round stores
+            if (p->h_cmd.p[b].flags & frx::DV_ADVANCE) { pl.newest[b] = p->h_cmd.p[b].slot; pl.bound[b] = p->h_cmd.p[b].bound; }  // the pair this round stores
         auto td = clk::now();
         HIP_TRY((hipError_t)frx::launch_lbfgs_pre(dv, p->h_cmd.p, p->h_res.p, p->stream));
         if (any_eval) {
             if (mailbox) p->tap.round++;
-            if (rounds == drop_round) HIP_TRY((hipError_t)frx::launch_eval(p, p->d_x.p, p->d_f.p, p->d_g.p, p->stream, false));
+            // (fault injection, tests: FRX_DEBUG_DROP_ROUND=k leaves k_backward_knot out of round k, so that round's completion is never posted)
+            if (rounds == sw.drop_round) HIP_TRY((hipError_t)frx::launch_eval(p, p->d_x.p, p->d_f.p, p->d_g.p, p->stream, false));
             else HIP_TRY((hipError_t)frx::launch_eval(p, p->d_x.p, p->d_f.p, p->d_g.p, p->stream, true));
             if (!fused_post) HIP_TRY((hipError_t)frx::launch_lbfgs_post(dv, p->d_f.p, p->h_cmd.p, p->h_res.p, p->stream));
         }
-        { const int wrc = wait_round(any_eval); if (wrc != FRX_OK) { const std::string keep = frx_last_error(); (void)wait_stream(p->stream, timeout_ms, "device round"); return fail(wrc, keep); } }   // bounded drain, first error kept
+        const int rc_wait = wait_round(p, mailbox && any_eval, sw.round_timeout_ms);
+        if (rc_wait != FRX_OK) return rc_wait;
         t_dev += ms_since(td);
         auto th = clk::now();
-        for (int b = 0; b < B; b++) {
-            frx::DvCommand &c = p->h_cmd.p[b];
-            const bool evaluated = (c.flags & frx::DV_EVAL) != 0;
-            if (!evaluated) { c.flags = 0; continue; }                         // a RESTORE has been executed
-            if (tracing && b == 0) { const frx::DvResult &r = p->h_res.p[b]; const double row[7] = {(double)c.flags, c.step, r.f, r.dg, r.dginit, r.xx, r.gg}; p->trace.insert(p->trace.end(), row, row + 7); }
-            h_flast[b] = p->h_res.p[b].f;
-            if (sv[b].saw_nonfinite(p->h_res.p[b].f)) sv[b].give_up(frx::LBERR_ROUNDING); else sv[b].feed(p->h_res.p[b]);
-        }
+        feed_round(p, pl, sw.trace);
         t_host += ms_since(th);
         rounds++;
     }
-    p->stats[0] = ms_since(t0); p->stats[1] = t_dev; p->stats[2] = t_host; p->stats[3] = (double)rounds;
+    p->stats = {ms_since(t0), t_dev, t_host, (double)rounds};
     HIP_TRY(hipMemcpyAsync(p->h_x.p, p->d_x.p, sizeof(double) * p->NX, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
-    if (handed_over) { take->ms = p->stats[0]; take->ms_dev = t_dev; take->ms_host = t_host; take->rounds = rounds; }
-    for (int b = 0; b < B; b++) {
-        if (only && !(*only)[b]) continue;
-        if (handed_over && p->h_cmd.p[b].flags != 0) {                          // still running: the solver, its pending command and the history's position travel
-            take->cand.push_back(b); take->sv.push_back(sv[b]); take->newest.push_back(h_newest[b]); take->bound.push_back(h_bound[b]); take->f_last.push_back(h_flast[b]);
-            continue;
-        }
-        std::memcpy(x + p->xoff[b], p->h_x.p + p->xoff[b], sizeof(double) * (p->xoff[b + 1] - p->xoff[b]));
-        status[b] = sv[b].status();
-        if (iters) iters[b] = sv[b].iterations();
-        if (evals) evals[b] = sv[b].evaluations();
-        if (objective) objective[b] = sv[b].value();
-    }
+    if (handed_over) take->spent = p->stats;
+    collect_or_hand_over(p, pl, only, handed_over ? take : nullptr, out);
     return handed_over ? 2 : FRX_OK;
 }
-
 
 // ---- the resident round kernel's host side (frx_round_kernel.hpp): ONE launch per plan ----
 
@@ -579,7 +616,8 @@ static int optimize_resident(frx_problem *p, const frx_lbfgs_params &pm, double 
     if (rc < 0) return rc;
     if (rc != FRX_OK || device_status != 0) return 1;
     const long rounds = mb.busiest();
-    p->stats[0] = ms_since(t0); p->stats[1] = p->stats[0] - t_host; p->stats[2] = t_host; p->stats[3] = (double)rounds;
+    const double ms = ms_since(t0);
+    p->stats = {ms, ms - t_host, t_host, (double)rounds};
     if (!take) HIP_TRY(hipMemcpy(x, p->d_x.p, sizeof(double) * p->NX, hipMemcpyDeviceToHost));
     else                                                                              //  a take-over's result: the stragglers' points only - everybody else's x is final already
         for (int b : take->cand) HIP_TRY(hipMemcpy(x + p->xoff[b], p->d_x.p + p->xoff[b], sizeof(double) * (size_t)(p->xoff[b + 1] - p->xoff[b]), hipMemcpyDeviceToHost));
@@ -616,6 +654,55 @@ static int finish_optimize(frx_problem *p, const double *x, double *C, double *T
 }
 
 
+static int eval_failed(hipError_t e) { return fail(FRX_ERR_HIP, std::string("device evaluation failed: ") + hipGetErrorString(e)); }
+
+// One evaluation of the whole batch for the host-vector plan: h_x -> h_f, h_g.  Zero-copy round trip: the kernels read x from and write (f, grad) to mapped,
+// coherent host memory over PCIe (205 KB each way at the headline size), so a round is three launches and one completion poll - no hipMemcpyAsync calls
+// (each costs more host time than the kernels it feeds).  FRX_ZERO_COPY=0 restores copies.
+static int eval_host_vectors(frx_problem *p, bool zero_copy, double timeout_ms) {
+    hipError_t e;
+    // an expired wait of the one-launch form must not end the plan as a silent LBFGSERR_ROUNDING (NaN objectives): the evaluation is repeated
+    // once with the stage kernels, which the handle keeps from then on (eval_cluster_status retires the form)
+    for (int attempt = 0; attempt < 2; attempt++) {
+        const bool fused = p->eval_fused != 0;
+        if (zero_copy) {
+            if ((e = (hipError_t)frx::launch_eval(p, p->h_x.p, p->h_f.p, p->h_g.p, p->stream, true)) != hipSuccess) return eval_failed(e);
+            const int wrc = wait_stream(p->stream, timeout_ms, "device evaluation");
+            if (wrc != FRX_OK) return wrc;
+        } else {
+            if ((e = hipMemcpyAsync(p->d_x.p, p->h_x.p, sizeof(double) * p->NX, hipMemcpyHostToDevice, p->stream)) != hipSuccess) return eval_failed(e);
+            if ((e = (hipError_t)frx::launch_eval(p, p->d_x.p, p->d_f.p, p->d_g.p, p->stream, true)) != hipSuccess) return eval_failed(e);
+            if ((e = hipMemcpyAsync(p->h_f.p, p->d_f.p, sizeof(double) * p->B, hipMemcpyDeviceToHost, p->stream)) != hipSuccess) return eval_failed(e);
+            if ((e = hipMemcpyAsync(p->h_g.p, p->d_g.p, sizeof(double) * p->NX, hipMemcpyDeviceToHost, p->stream)) != hipSuccess) return eval_failed(e);
+            if ((e = hipStreamSynchronize(p->stream)) != hipSuccess) return eval_failed(e);
+        }
+        if (!fused || frx::eval_cluster_status(p, p->h_f.p) == FRX_OK) return FRX_OK;
+    }
+    return FRX_OK;
+}
+
+// the host-vector plan: every vector on the host, the device evaluates (FRX_LBFGS=host, or nothing else could run)
+static int optimize_host_vectors(frx_problem *p, const frx_lbfgs_params &pm, const frx::PlanSwitches &sw, const frx::PlanArrays &out) {
+    std::memcpy(p->h_x.p, out.x, sizeof(double) * p->NX);
+    int nt = std::max(1u, std::min<unsigned>(std::thread::hardware_concurrency(), (unsigned)p->B));
+    if (sw.host_threads_set) nt = std::max(1, std::min(sw.host_threads, p->B));
+    const int rc = drive_batch(p->B, p->xoff.data(), p->h_x.p, p->h_g.p, p->h_f.p, pm, nt, out.status, out.iters, out.evals, out.objective, &p->stats,
+                               [&](int, const int *) { return eval_host_vectors(p, sw.zero_copy, sw.round_timeout_ms); });
+    if (rc == FRX_OK) std::memcpy(out.x, p->h_x.p, sizeof(double) * p->NX);
+    return rc;
+}
+
+// the two device-vector drivers as the route calls them (frx_plan_route.hpp)
+struct DevicePaths {
+    frx_problem *p; const frx_lbfgs_params &pm; const frx::PlanSwitches &sw; const frx::PlanArrays &out;
+    int resident(TakeOver *take) { return optimize_resident(p, pm, out.x, out.status, out.iters, out.evals, out.objective, take); }
+    int per_stage(const std::vector<char> *only, TakeOver *take) { return optimize_device_vectors(p, pm, sw, out, only, take); }
+    unsigned device_status() const { return p->resident_status; }
+    int capacity() const { hipDeviceProp_t prop; return hipGetDeviceProperties(&prop, p->device) == hipSuccess ? frx::resident_capacity(p->geo.maxXb, prop.multiProcessorCount) : -1; }
+    int fail(int code, const char *text) { return ::fail(code, text); }
+};
+
+
 extern "C" {
 
 int frx_optimize(frx_problem *p, const frx_lbfgs_params *params, double *x, double *C, double *T, double *jerk_cost,
@@ -623,156 +710,13 @@ int frx_optimize(frx_problem *p, const frx_lbfgs_params *params, double *x, doub
     if (!p || !params || !x || !status) return fail(FRX_ERR_INVALID_ARG, "null argument");
     if (p->penalty_only) return fail(FRX_ERR_INVALID_ARG, "this handle serves frx_penalty_eval[_device] only (frx_penalty_problem_create)");
     HIP_TRY(hipSetDevice(p->device));
-    // FRX_LBFGS=host keeps every vector on the host (bit-identical to the reference solver given identical f, g);
-    // the default keeps the vectors on the device and only the line-search decisions on the host.
-    const bool want_device_vectors = !frx::env_is("FRX_LBFGS", 'h') && p->lbfgs_mode != 1;
-    int rc_dv = 1;
-    p->taken_over = 0;
-    if (want_device_vectors) {
-        // FRX_RESIDENT=0 keeps the one-launch-per-stage rounds; the default is the resident round kernel whenever the batch fits the
-        // chip (one workgroup per CU, B x G of them), with the per-stage path as fallback when it does not or when the device gives up
-        const bool resident_off = frx::env_off("FRX_RESIDENT");
-        p->resident_used = 0; p->resident_retried = 0;
-        p->resident_failed = 0; p->resident_clusters = 0; for (auto &q : p->spec_counts) q = 0;      //  diagnostics of THIS plan, whichever path it takes
-        const std::vector<double> x_start(x, x + p->NX);
-        // Candidates whose resident plan ended with LBFGSERR_INCREASEGRADIENT are planned again on the per-stage rounds (see below, where the resident plan returns).
-        // `scope` (optional): only these candidates are looked at - the stragglers of a take-over, whose dense state was rebuilt on the host by plain back-substitution
-        // over up to 128 pairs (the long-running, worst-conditioned candidates of a batch; without this their g.d >= 0 would be final on that path alone).
-        // The resident result of a candidate that is planned again is kept: when the per-stage path cannot run (rc2 > 0: its buffers do not fit) or fails
-        // on it as well, it keeps the resident verdict, point and objective instead of ending at its start point.
-        const char *rt_env = std::getenv("FRX_RESIDENT_RETRY");
-        const int retry_mode = rt_env ? (rt_env[0] == '0' ? 0 : rt_env[0] == 't' ? 2 : 1) : (p->resident_retry != 0 ? 1 : 2);   // 2 = targeted (default)
-        auto wants_retry = [&](int st) { return st < 0 && st != frx::LBERR_MAXIMUMITERATION && (retry_mode == 1 || (retry_mode == 2 && st == frx::LBERR_INCREASEGRADIENT)); };
-        auto retry_increase_gradient = [&](const std::vector<int> *scope) -> int {
-            std::vector<char> again(p->B, 0);
-            int n_again = 0;
-            if (scope) { for (int b : *scope) if (wants_retry(status[b])) { again[b] = 1; n_again++; } }
-            else for (int b = 0; b < p->B; b++) if (wants_retry(status[b])) { again[b] = 1; n_again++; }
-            if (n_again == 0) return 0;
-            const std::vector<double> x_res(x, x + p->NX);
-            std::vector<int> st_res(status, status + p->B), it_res, ev_res;
-            std::vector<double> obj_res;
-            if (iters) it_res.assign(iters, iters + p->B);
-            if (evals) ev_res.assign(evals, evals + p->B);
-            if (objective) obj_res.assign(objective, objective + p->B);
-            for (int b = 0; b < p->B; b++) if (again[b]) std::copy(x_start.begin() + p->xoff[b], x_start.begin() + p->xoff[b + 1], x + p->xoff[b]);
-            const int used = p->resident_used, taken = p->taken_over;
-            const double t_res[4] = {p->stats[0], p->stats[1], p->stats[2], p->stats[3]};
-            const int rc2 = optimize_device_vectors(p, *params, x, status, iters, evals, objective, &again);
-            if (rc2 < 0) return rc2;
-            if (rc2 != 0) {
-                std::copy(x_res.begin(), x_res.end(), x);
-                std::copy(st_res.begin(), st_res.end(), status);
-                if (iters) std::copy(it_res.begin(), it_res.end(), iters);
-                if (evals) std::copy(ev_res.begin(), ev_res.end(), evals);
-                if (objective) std::copy(obj_res.begin(), obj_res.end(), objective);
-                n_again = 0;
-            }
-            p->resident_used = used; p->taken_over = taken; p->resident_retried += n_again;
-            if (rc2 == 0) p->stats[0] += t_res[0]; else p->stats[0] = t_res[0];
-            if (scope) { for (int q = 1; q < 4; q++) p->stats[q] = (rc2 == 0 ? p->stats[q] : 0.0) + t_res[q]; }
-            return 0;
-        };
-        bool resident_gave_up = false;
-        if (!resident_off && p->resident_mode != 0 && p->takeover_at <= 0) {      // (frx_debug_set_takeover_at, tests: per-stage rounds first, whatever the batch size)
-            rc_dv = optimize_resident(p, *params, x, status, iters, evals, objective);
-            resident_gave_up = rc_dv != 0 && p->resident_status != 0;
-            if (rc_dv < 0) return rc_dv;
-            if (rc_dv != 0) std::copy(x_start.begin(), x_start.end(), x);
-            else {
-                // A candidate that ends with an L-BFGS error on the resident kernel keeps that verdict, as it would in the reference
-                // (lbfgs_optimize returns the code, SE3GCOPTER::optimize ignores it, CPU.hpp:1249): on the Monte-Carlo and perturbation
-                // shares the resident kernel fails on no more candidates than the CPU oracle does (tests/test_gpu_configs.py) - with ONE
-                // exception.  The resident kernel forms d = -H g in the compact representation (R^-1 maintained incrementally), the
-                // reference by the two-loop recursion; in exact arithmetic H is positive definite in both and d is a descent direction.  A
-                // search that starts with g.d >= 0 (LBFGSERR_INCREASEGRADIENT, lbfgs.hpp:766) can therefore only be the work of rounding in
-                // the direction itself - an ill-conditioned R - and says nothing about the candidate: such candidates, and only those, are
-                // planned again on the per-stage rounds, whose direction kernel IS the two-loop recursion.  Line searches that give up
-                // (-1005, -1007: infeasible corridors, the CPU oracle's verdict as well) are final.  frx_debug_set_resident_retry(p, 1) /
-                // FRX_RESIDENT_RETRY=1 re-run every failed candidate (diagnostic), FRX_RESIDENT_RETRY=0 none.
-                const int rc_retry = retry_increase_gradient(nullptr);
-                if (rc_retry < 0) return rc_retry;
-            }
-        }
-        if (rc_dv != 0) {
-            // A batch too large for the resident kernel's clusters runs as per-stage rounds - until no more candidates are left than the chip has clusters for:
-            // those continue on the resident kernel (TakeOver; FRX_TAKEOVER=0 keeps the per-stage rounds to the end).  Not when the caller switched the
-            // resident kernel or its queue off, and not when the resident kernel has just given up on this device.
-            TakeOver take;
-            {
-                const bool wanted = !frx::env_off("FRX_TAKEOVER") && !resident_off && !frx::env_off("FRX_RESIDENT_QUEUE") && p->resident_mode != 0 && !resident_gave_up;
-                hipDeviceProp_t prop;
-                if (wanted && p->geo.solver == frx::SOLVER_KNOT_PCR && p->geo.knot_threads == 64 && params->mem_size == 128 && hipGetDeviceProperties(&prop, p->device) == hipSuccess) {
-                    bool fits = true;
-                    for (int b = 0; b < p->B; b++) fits = fits && p->xoff[b + 1] - p->xoff[b] >= 2 * params->mem_size;
-                    const int cap = frx::resident_capacity(p->geo.maxXb, prop.multiProcessorCount);   // what optimize_resident will hold when they are handed over
-                    if (fits && cap >= 1 && p->B > cap) take.capacity = cap;
-                    if (p->takeover_at > 0) { take.not_before = p->takeover_at; if (fits && cap >= 1 && p->B <= cap) take.capacity = cap; }   // (tests: a small batch hands over after so many rounds)
-                }
-            }
-            rc_dv = optimize_device_vectors(p, *params, x, status, iters, evals, objective, nullptr, take.capacity > 0 ? &take : nullptr);
-            if (rc_dv < 0) return rc_dv;
-            if (rc_dv == 2) {
-                const double ms_ps = take.ms, dev_ps = take.ms_dev, host_ps = take.ms_host;
-                const long rounds_ps = take.rounds;
-                const int rc3 = optimize_resident(p, *params, x, status, iters, evals, objective, &take);
-                if (rc3 < 0) return rc3;
-                if (rc3 == 0) {
-                    p->taken_over = (int)take.cand.size();
-                    p->stats[0] += ms_ps; p->stats[1] += dev_ps; p->stats[2] += host_ps; p->stats[3] += (double)rounds_ps;
-                    const int rc_retry = retry_increase_gradient(&take.cand);             //  the stragglers get the resident path's targeted second chance
-                    if (rc_retry < 0) return rc_retry;
-                } else {
-                    // the resident kernel could not take them (another process on the device, a geometry it does not cover): their vectors on the device are no
-                    // longer the per-stage path's, so they are planned again from their start points, per stage - slower, never wrong
-                    std::vector<char> again(p->B, 0);
-                    for (int c : take.cand) { again[c] = 1; std::copy(x_start.begin() + p->xoff[c], x_start.begin() + p->xoff[c + 1], x + p->xoff[c]); }
-                    const int rc4 = optimize_device_vectors(p, *params, x, status, iters, evals, objective, &again);
-                    if (rc4 != 0) return rc4 < 0 ? rc4 : fail(FRX_ERR_HIP, "per-stage path unavailable after a failed take-over");
-                    p->resident_used = 0;
-                    p->stats[0] += ms_ps; p->stats[1] += dev_ps; p->stats[2] += host_ps; p->stats[3] += (double)rounds_ps;
-                }
-                rc_dv = 0;
-            }
-        }
-    }
-    if (rc_dv == 0) return finish_optimize(p, x, C, T, jerk_cost);
-    std::memcpy(p->h_x.p, x, sizeof(double) * p->NX);
-    int nt = std::max(1u, std::min<unsigned>(std::thread::hardware_concurrency(), (unsigned)p->B));
-    if (const char *ht = std::getenv("FRX_HOST_THREADS")) nt = std::max(1, std::min(std::atoi(ht), p->B));
-    // Zero-copy round trip: the kernels read x from and write (f, grad) to mapped, coherent host memory over PCIe
-    // (205 KB each way at the headline size), so a round is three launches and one completion poll — no
-    // hipMemcpyAsync calls (each costs more host time than the kernels it feeds).  FRX_ZERO_COPY=0 restores copies.
-    const bool zero_copy = !frx::env_off("FRX_ZERO_COPY");
-    const double timeout_ms = round_timeout_ms();
-    auto eval_all = [&](int, const int *) -> int {
-        hipError_t e;
-        //  an expired wait of the one-launch form must not end the plan as a silent LBFGSERR_ROUNDING (NaN objectives): the evaluation is repeated
-        // once with the stage kernels, which the handle keeps from then on (eval_cluster_status retires the form)
-        for (int attempt = 0; attempt < 2; attempt++) {
-            const bool fused = p->eval_fused != 0;
-            if (zero_copy) {
-                if ((e = (hipError_t)frx::launch_eval(p, p->h_x.p, p->h_f.p, p->h_g.p, p->stream, true)) != hipSuccess) goto bad;
-                const int wrc = wait_stream(p->stream, timeout_ms, "device evaluation");
-                if (wrc != FRX_OK) return wrc;
-            } else {
-                if ((e = hipMemcpyAsync(p->d_x.p, p->h_x.p, sizeof(double) * p->NX, hipMemcpyHostToDevice, p->stream)) != hipSuccess) goto bad;
-                if ((e = (hipError_t)frx::launch_eval(p, p->d_x.p, p->d_f.p, p->d_g.p, p->stream, true)) != hipSuccess) goto bad;
-                if ((e = hipMemcpyAsync(p->h_f.p, p->d_f.p, sizeof(double) * p->B, hipMemcpyDeviceToHost, p->stream)) != hipSuccess) goto bad;
-                if ((e = hipMemcpyAsync(p->h_g.p, p->d_g.p, sizeof(double) * p->NX, hipMemcpyDeviceToHost, p->stream)) != hipSuccess) goto bad;
-                if ((e = hipStreamSynchronize(p->stream)) != hipSuccess) goto bad;
-            }
-            if (!fused || frx::eval_cluster_status(p, p->h_f.p) == FRX_OK) return FRX_OK;
-        }
-        return FRX_OK;
-    bad:
-        return fail(FRX_ERR_HIP, std::string("device evaluation failed: ") + hipGetErrorString(e));
-    };
-    int rc = drive_batch(p->B, p->xoff.data(), p->h_x.p, p->h_g.p, p->h_f.p, *params, nt, status, iters, evals, objective, p->stats,
-                         eval_all);
-    if (rc != FRX_OK) return rc;
-    std::memcpy(x, p->h_x.p, sizeof(double) * p->NX);
-    return finish_optimize(p, x, C, T, jerk_cost);
+    const frx::PlanSwitches sw = plan_switches_from_env();
+    const frx::PlanArrays out{x, status, iters, evals, objective};
+    DevicePaths paths{p, *params, sw, out};
+    int rc = frx::plan_route({sw, p->lbfgs_mode, p->resident_mode, p->resident_retry, p->takeover_at, p->geo.solver, p->geo.knot_threads, params->mem_size, p->B, p->NX, p->xoff.data()}, out,
+                             {p->resident_used, p->resident_retried, p->resident_failed, p->resident_clusters, p->taken_over, p->spec_counts}, p->stats, paths);
+    if (rc > 0) rc = optimize_host_vectors(p, *params, sw, out);
+    return rc != FRX_OK ? rc : finish_optimize(p, x, C, T, jerk_cost);
 }
 
 int frx_problem_set_resident(frx_problem *p, int enable) {
@@ -848,7 +792,7 @@ int frx_debug_taken_over(const frx_problem *p, int *candidates) {
 
 int frx_optimize_stats(const frx_problem *p, double *out4) {
     if (!p || !out4) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    for (int i = 0; i < 4; i++) out4[i] = p->stats[i];
+    out4[0] = p->stats.ms; out4[1] = p->stats.ms_dev; out4[2] = p->stats.ms_host; out4[3] = p->stats.rounds;
     return FRX_OK;
 }
 

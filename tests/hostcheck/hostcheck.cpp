@@ -383,3 +383,6 @@ extern "C" void hostcheck_eval_solo_choice(int lds_solo, int solo_char, int min_
 // ---- the mailbox protocol against a thread that plays the clusters (resident_mailbox_main.cpp), for tests/test_resident_mailbox_cpu.py ----
 #define HOSTCHECK_LIBRARY
 #include "resident_mailbox_main.cpp"
+
+// ---- the route of a plan against drivers played from a script (plan_route_main.cpp), and its decisions, for tests/test_plan_route_cpu.py ----
+#include "plan_route_main.cpp"

@@ -306,6 +306,37 @@ def test_resident_kernel_handles_failing_and_finishing_candidates(frx, sc, ob):
     prob.close()
 
 
+def test_failed_candidates_get_a_second_chance_on_the_per_stage_rounds(frx, sc, monkeypatch):
+    """frx_debug_set_resident_retry: every candidate the resident kernel failed on is planned again on the per-stage rounds, from its start point, and the others keep
+    their resident result bit for bit.  The same three candidates as above; 1500 iterations let the infeasible one reach its own verdict on the resident kernel
+    (a failed line search after 703 iterations; the iteration limit is never retried) and keep the three plans at half a second.  The per-stage rounds treat
+    candidates independently, so the one planned again ends exactly as it does in a per-stage plan of the whole batch."""
+    cands = [sc.make_candidate(170, 64, 16), sc.make_candidate(3, 64, 16), sc.make_candidate(5, 64, 16)]
+    prob = frx.Problem(cands, sc.ZHANGJIAJIE, qd_intervals=16)
+    x0, tol, cap = prob.initial_guess(), sc.ZHANGJIAJIE["opt_rel_tol"], 1500
+    monkeypatch.setenv("FRX_RESIDENT_RETRY", "0")                         # no second chance, not even the targeted one: the resident kernel's own verdicts
+    first = _plan(prob, tol, True, x0=x0, max_iterations=cap)
+    monkeypatch.delenv("FRX_RESIDENT_RETRY")
+    prob.set_resident_retry(True)
+    second = _plan(prob, tol, True, x0=x0, max_iterations=cap)
+    prob.set_resident_retry(False)
+    per_stage = _plan(prob, tol, False, x0=x0, max_iterations=cap)
+    again = [b for b in range(3) if first["status"][b] < 0 and first["status"][b] != -1004]
+    print(json.dumps({"first": first["status"].tolist(), "second": second["status"].tolist(), "per_stage": per_stage["status"].tolist(), "planned_again": again,
+                      "evals": [first["evals"].tolist(), second["evals"].tolist(), per_stage["evals"].tolist()], "ms": [first["ms_total"], second["ms_total"], per_stage["ms_total"]]}))
+    assert first["resident"] >= 2 and first["device_status"] == 0 and first["resident_retried"] == 0 and per_stage["resident"] == 0
+    assert first["status"][0] not in (0, -1004) and 0 in again                                                 # the test is about a candidate that IS planned again
+    assert second["resident_retried"] == len(again) >= 1
+    assert second["resident"] == first["resident"] and second["taken_over"] == first["taken_over"] == 0 and second["device_status"] == 0
+    seg = lambda r, b: r["x"][prob.x_off[b]:prob.x_off[b + 1]]
+    for b in range(3):
+        ref = per_stage if b in again else first
+        assert np.array_equal(seg(second, b), seg(ref, b)) and second["status"][b] == ref["status"][b] and second["evals"][b] == ref["evals"][b], b
+        if b not in again:
+            assert second["iters"][b] == first["iters"][b] and second["objective"][b] == first["objective"][b], b
+    prob.close()
+
+
 def test_size_classes_of_the_kernel_agree(frx, sc, monkeypatch):
     """A batch that leaves the chip room (<= 16 headline candidates) runs with 28 history elements per thread on twelve history workgroups, a full
     batch with 56 on six: two summation orders of the same direction - same verdicts, objectives as close as two independent runs are."""
