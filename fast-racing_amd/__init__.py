@@ -71,6 +71,7 @@ ABI_SYMBOLS = [
     "frx_gate_from_corners", "frx_trajectory_gates", "frx_trajectory_gates_device", "frx_gate_flags",
     "frx_trajectory_contain", "frx_trajectory_contain_device", "frx_contain_fold",
     "frx_trajectory_clearance", "frx_trajectory_clearance_workspace", "frx_trajectory_clearance_device",
+    "frx_trajectory_clearance_exact", "frx_trajectory_clearance_exact_workspace", "frx_trajectory_clearance_exact_device", "frx_clearance_exact_fold",
     "frx_corridor_generate_batch", "frx_corridor_generate_batch_device",
     "frx_enumerate_vertices_batch", "frx_enumerate_vertices_batch_device", "frx_corridor_slots_to_tasks_device",
 ]
@@ -80,6 +81,7 @@ DEBUG_SYMBOLS = [
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
     "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_eval_geometry", "frx_debug_eval_front", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
     "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device", "frx_debug_dv_layout", "frx_debug_dv_round", "frx_debug_fold_rows", "frx_debug_lane_exchange",
+    "frx_debug_set_clear_exact", "frx_debug_clear_exact_counts",
 ]
 
 # frx_trajectory_check (include/frx.h): fields of a row and flag bits
@@ -99,6 +101,8 @@ CLEAR_FIELDS = ("ell", "dist", "worst_t", "worst_i")
 CLEAR_MAX_POINTS = 1 << 24
 CLEAR_FLAG_COLLISION, CLEAR_FLAG_NONFINITE = 1, 2
 CLEAR_TILE, CLEAR_PASS = 64, 1024
+# frx_trajectory_clearance_exact (include/frx.h): fields of a row; its flags are the CLEAR_FLAG_* bits
+CLEAR_EXACT_FIELDS = ("ell", "dist", "t_ell", "i_ell", "t_dist", "i_dist")
 # frx_trajectory_sample (include/frx.h): doubles of a row and the named parts of it (FRX_SAMPLE_*)
 SAMPLE_FIELDS = 20
 SAMPLE_VIEWS = dict(pos=slice(0, 3), vel=slice(3, 6), acc=slice(6, 9), jerk=slice(9, 12), thrust=12, quat=slice(13, 17), omega=slice(17, 20))
@@ -194,6 +198,12 @@ def lib():
         L.frx_trajectory_clearance_workspace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.frx_trajectory_clearance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_debug_set_clear_chunk.argtypes = [C.c_void_p, C.c_int]
+        L.frx_trajectory_clearance_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_trajectory_clearance_exact_workspace.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
+        L.frx_trajectory_clearance_exact_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_clearance_exact_fold.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.frx_debug_set_clear_exact.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.frx_debug_clear_exact_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_debug_fold_rows.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6
         L.frx_debug_lane_exchange.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.frx_corridor_generate_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
@@ -593,6 +603,22 @@ def contain_fold(piece_rows, T, piece_off):
     return cand, flags
 
 
+def clearance_exact_fold(piece_rows, T, piece_off):
+    """Candidate rows (B, 6) and CLEAR_FLAG_* words (B,) uint32 from the piece rows (P, 6) of trajectory_clearance_exact_device (frx_clearance_exact_fold, host
+    only): candidate b owns the pieces piece_off[b] .. piece_off[b + 1] - 1.  A candidate without pieces keeps a row of zeros."""
+    piece_off = np.ascontiguousarray(piece_off, dtype=np.int32).reshape(-1)
+    rows = np.ascontiguousarray(piece_rows, dtype=np.float64).reshape(-1, len(CLEAR_EXACT_FIELDS))
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+    B = piece_off.size - 1
+    if B >= 1 and (rows.shape[0] < int(piece_off.max()) or T.size < int(piece_off.max())):
+        raise ValueError(f"clearance_exact_fold: {rows.shape[0]} rows and {T.size} durations for piece_off up to {int(piece_off.max())}")
+    cand = np.zeros((max(B, 0), len(CLEAR_EXACT_FIELDS))); flags = np.zeros(max(B, 0), np.uint32)
+    pad = np.zeros(1)
+    _check(lib().frx_clearance_exact_fold(B, piece_off.ctypes.data, (T if T.size else pad).ctypes.data, (rows if rows.size else pad).ctypes.data,
+                                          cand.ctypes.data, flags.ctypes.data))
+    return cand, flags
+
+
 def traj_to_msg(T, Cf):
     """PolynomialTrajectory array fields of one trajectory: (coef_x, coef_y, coef_z, time, order)."""
     n = len(T)
@@ -919,6 +945,37 @@ class Problem:
         """frx_trajectory_clearance_device: the piece rows (P x 4 doubles at out_ptr) as pure launches on `stream`, device pointers (work_ptr: the scratch
         trajectory_clearance_workspace asks for, 0 when that is 0), no copy, no synchronisation, no allocation."""
         _check(lib().frx_trajectory_clearance_device(self.h, T_ptr, C_ptr, int(intervals), int(n_obs), obs_ptr, work_ptr or None, out_ptr, stream))
+
+    def trajectory_clearance_exact(self, T, Cf, obs):
+        """Exact clearance certificate of the batch (T, C) against the obstacle cloud obs (n_obs, 3) (frx_trajectory_clearance_exact; nothing is sampled):
+        dict(piece (P, 6), cand (B, 6), flags (B,) uint32 of CLEAR_FLAG_*) plus the candidate rows' fields by name (CLEAR_EXACT_FIELDS)."""
+        T, Cf = self._traj_TC("trajectory_clearance_exact", T, Cf)
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != 3:
+            raise ValueError(f"trajectory_clearance_exact: obs must have shape (n_obs, 3), got {obs.shape}")
+        return self._traj_folded(CLEAR_EXACT_FIELDS, "cand", lib().frx_trajectory_clearance_exact, T.ctypes.data, Cf.ctypes.data, obs.shape[0], obs.ctypes.data)
+
+    def trajectory_clearance_exact_workspace(self, n_obs: int) -> int:
+        """frx_trajectory_clearance_exact_workspace: bytes of scratch trajectory_clearance_exact_device needs for a cloud of n_obs points."""
+        n = C.c_size_t(0)
+        _check(lib().frx_trajectory_clearance_exact_workspace(self.h, int(n_obs), C.byref(n)))
+        return int(n.value)
+
+    def trajectory_clearance_exact_device(self, T_ptr: int, C_ptr: int, obs_ptr: int, n_obs: int, work_ptr: int, out_ptr: int, stream: int = 0):
+        """frx_trajectory_clearance_exact_device: the piece rows (P x 6 doubles at out_ptr) as pure launches on `stream`, device pointers (work_ptr: the
+        scratch trajectory_clearance_exact_workspace asks for), no copy, no synchronisation, no allocation; clearance_exact_fold gives the candidate rows."""
+        _check(lib().frx_trajectory_clearance_exact_device(self.h, T_ptr, C_ptr, int(n_obs), obs_ptr, work_ptr or None, out_ptr, stream))
+
+    def set_clear_exact(self, chunk_points: int = 0, cull_on: bool = True):
+        """Tests (frx_debug_set_clear_exact): cloud points per chunk of every later exact clearance call on the handle (0 = the library's own split) and
+        whether points are culled at all."""
+        _check(lib().frx_debug_set_clear_exact(self.h, int(chunk_points), int(bool(cull_on))))
+
+    def clear_exact_counts(self):
+        """Tests (frx_debug_clear_exact_counts): (survivors (P,), degree-21 tasks (P,)) int32 of the last exact clearance call on the handle."""
+        s = np.zeros(self.P, np.int32); e = np.zeros(self.P, np.int32)
+        _check(lib().frx_debug_clear_exact_counts(self.h, s.ctypes.data, e.ctypes.data))
+        return s, e
 
     def set_clear_chunk(self, points: int):
         """Tests (frx_debug_set_clear_chunk): cloud points per chunk of every later clearance call on the handle, 0 = the library's own split."""

@@ -969,6 +969,7 @@ int frx_trajectory_clearance(frx_problem *p, const double *T, const double *C, i
     HIP_TRY(hipSetDevice(p->device));
     const size_t n_rows = (size_t)FRX_CLEAR_FIELDS * p->P, n_cloud = 3 * (size_t)n_obs, n_work = nchunks > 1 ? n_rows * (size_t)nchunks : 0;
     FRX_TRY(grow(p->d_clear, n_rows + n_cloud + n_work, "frx_trajectory_clearance"));
+    p->clx_last_work = nullptr;                                              // (the buffer is laid out anew: the exact form's partials in it are gone)
     double *d_rows = p->d_clear.p, *d_obs = d_rows + n_rows, *d_work = n_work ? d_obs + n_cloud : nullptr;
     FRX_TRY(stage_TC(p, T, C));
     HIP_TRY(hipMemcpyAsync(d_obs, obs, sizeof(double) * n_cloud, hipMemcpyHostToDevice, p->stream));
@@ -983,6 +984,88 @@ int frx_trajectory_clearance(frx_problem *p, const double *T, const double *C, i
 int frx_debug_set_clear_chunk(frx_problem *p, int points) {
     if (!p || points < 0) return fail(FRX_ERR_INVALID_ARG, "null handle or a negative chunk");
     p->clear_chunk = points;
+    return FRX_OK;
+}
+
+int frx_clearance_exact_fold(int B, const int *piece_off, const double *T, const double *rows, double *cand_out, unsigned *flags) {
+    if (B < 1 || !piece_off || !T || !rows) return fail(FRX_ERR_INVALID_ARG, "frx_clearance_exact_fold: B must be >= 1 and piece_off, T, rows not NULL");
+    if (piece_off[0] < 0) return fail(FRX_ERR_INVALID_ARG, "frx_clearance_exact_fold: piece_off[0] must be >= 0");
+    for (int b = 0; b < B; b++)
+        if (piece_off[b + 1] < piece_off[b]) return fail(FRX_ERR_INVALID_ARG, "frx_clearance_exact_fold: piece_off must not fall (candidate " + std::to_string(b) + ")");
+    frx::fold_clearance_exact(B, piece_off, T, rows, cand_out, flags);
+    return FRX_OK;
+}
+
+// argument rules of every form of frx_trajectory_clearance_exact, checked before a device is looked for and before the handle is read; then the split of the cloud
+static int clear_exact_args(frx_problem *p, const void *T, const void *C, int n_obs, const void *obs, const void *work, const void *out, int *chunk, int *nchunks) {
+    static_assert(FRX_CLEAR_EXACT_FIELDS == (int)frx::CLEAR_EXACT_FIELDS && FRX_CLEAR_EXACT_FIELDS <= 20, "frx.h and frx_device.hpp agree, and the rows fit the P x 20 staging");
+    if (!p || !T || !C || !obs || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (!work) return fail(FRX_ERR_INVALID_ARG, "work_dev is NULL: frx_trajectory_clearance_exact_workspace says how much scratch the launches need");
+    if (n_obs < 1 || n_obs > FRX_CLEAR_MAX_POINTS) return fail(FRX_ERR_INVALID_ARG, "n_obs must lie in 1.." + std::to_string(FRX_CLEAR_MAX_POINTS));
+    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (!frx::clear_exact_geometry(p->P, n_obs, p->clx_chunk, chunk, nchunks))
+        return fail(FRX_ERR_CAPACITY, "frx_trajectory_clearance_exact: " + std::to_string(p->P) + " pieces x the cloud's chunks exceed a grid");
+    return FRX_OK;
+}
+
+int frx_trajectory_clearance_exact_workspace(frx_problem *p, int n_obs, size_t *bytes) {
+    int chunk = 0, nchunks = 0;
+    const int rc = clear_exact_args(p, bytes, bytes, n_obs, bytes, bytes, bytes, &chunk, &nchunks);
+    if (rc != FRX_OK) return rc;
+    *bytes = sizeof(double) * frx::CLEAR_EXACT_PARTIAL * (size_t)p->P * (size_t)nchunks;
+    return FRX_OK;
+}
+
+int frx_trajectory_clearance_exact_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_obs, const double *obs_dev, void *work_dev,
+                                          double *piece_out_dev, void *hip_stream) {
+    int chunk = 0, nchunks = 0;
+    const int rc = clear_exact_args(p, T_dev, C_dev, n_obs, obs_dev, work_dev, piece_out_dev, &chunk, &nchunks);
+    if (rc != FRX_OK) return rc;
+    HIP_TRY((hipError_t)frx::launch_clear_exact(p->dp, T_dev, C_dev, n_obs, obs_dev, chunk, nchunks, p->clx_cull, (double *)work_dev, piece_out_dev, hip_stream));
+    p->clx_last_work = (const double *)work_dev; p->clx_last_nchunks = nchunks;
+    return FRX_OK;
+}
+
+int frx_trajectory_clearance_exact(frx_problem *p, const double *T, const double *C, int n_obs, const double *obs, double *piece_out, double *cand_out,
+                                   unsigned *flags) {
+    int chunk = 0, nchunks = 0;
+    FRX_TRY(clear_exact_args(p, T, C, n_obs, obs, obs, cand_out, &chunk, &nchunks));
+    HIP_TRY(hipSetDevice(p->device));
+    // the handle's cloud buffer, as the dense form lays it out: the rows, the cloud, then the partials
+    const size_t n_rows = (size_t)FRX_CLEAR_EXACT_FIELDS * p->P, n_cloud = 3 * (size_t)n_obs, n_work = (size_t)frx::CLEAR_EXACT_PARTIAL * p->P * (size_t)nchunks;
+    FRX_TRY(grow(p->d_clear, n_rows + n_cloud + n_work, "frx_trajectory_clearance_exact"));
+    double *d_rows = p->d_clear.p, *d_obs = d_rows + n_rows, *d_work = d_obs + n_cloud;
+    FRX_TRY(stage_TC(p, T, C));
+    HIP_TRY(hipMemcpyAsync(d_obs, obs, sizeof(double) * n_cloud, hipMemcpyHostToDevice, p->stream));
+    FRX_TRY(frx_trajectory_clearance_exact_device(p, p->d_T.p, p->d_C.p, n_obs, d_obs, d_work, d_rows, p->stream));
+    FRX_TRY(fetch_rows(p, d_rows, n_rows, piece_out));
+    frx::fold_clearance_exact(p->B, p->poff.data(), T, p->h_out20.p, cand_out, flags);
+    return FRX_OK;
+}
+
+// Tests: points > 0 forces that many cloud points per chunk of every later exact clearance call and workspace query on the handle (0: the library's own split);
+// cull_on == 0 makes every point a survivor that runs both tasks.  Rows depend on neither.
+int frx_debug_set_clear_exact(frx_problem *p, int chunk_points, int cull_on) {
+    if (!p || chunk_points < 0) return fail(FRX_ERR_INVALID_ARG, "null handle or a negative chunk");
+    p->clx_chunk = chunk_points; p->clx_cull = cull_on ? 1 : 0;
+    return FRX_OK;
+}
+
+// Tests: per piece, the points that survived the cull and the degree-21 tasks that ran in the last exact clearance call on the handle, summed over the chunks of
+// the partials that call left in its workspace (which must still be alive).  Waits for the device.
+int frx_debug_clear_exact_counts(frx_problem *p, int *survivors, int *ell_tasks) {
+    if (!p || !survivors || !ell_tasks) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (!p->clx_last_work) return fail(FRX_ERR_INVALID_ARG, "frx_debug_clear_exact_counts: no exact clearance call on this handle since its cloud buffer was last laid out");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const int nc = p->clx_last_nchunks;
+    std::vector<double> part((size_t)frx::CLEAR_EXACT_PARTIAL * p->P * (size_t)nc);
+    HIP_TRY(hipMemcpy(part.data(), p->clx_last_work, sizeof(double) * part.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < p->P; k++) {
+        double s = 0.0, e = 0.0;
+        for (int c = 0; c < nc; c++) { const double *w = part.data() + ((size_t)k * nc + c) * frx::CLEAR_EXACT_PARTIAL; s += w[6]; e += w[7]; }
+        survivors[k] = (int)s; ell_tasks[k] = (int)e;
+    }
     return FRX_OK;
 }
 

@@ -1,4 +1,4 @@
-// Piece rows -> candidate rows and flag words of frx_trajectory_check / _extrema / _clearance / _contain (include/frx.h documents the rows).  Plain C++: no HIP
+// Piece rows -> candidate rows and flag words of frx_trajectory_check / _extrema / _clearance / _clearance_exact / _contain (include/frx.h documents the rows).  Plain C++: no HIP
 // and no handle, so the blocking entries (frx_api.cpp), frx_debug_fold_rows, frx_contain_fold and a host-only program share this one implementation.
 //
 // One shape: the candidates b = 0..B-1 own the pieces poff[b]..poff[b+1]-1 of T[] and of rows[] (piece rows, FIELDS doubles each), folded in piece order;
@@ -75,6 +75,24 @@ inline void fold_clearance(int B, const int *poff, const double *T, const double
             o[FRX_CLEAR_DIST] = k == 0 ? r[FRX_CLEAR_DIST] : nan_min(o[FRX_CLEAR_DIST], r[FRX_CLEAR_DIST]);
         },
         [](const double *o) { return o[FRX_CLEAR_ELL] < 1.0 ? FRX_CLEAR_FLAG_COLLISION : 0u; });
+}
+
+// exact clearance: ELL and DIST each under the kernel's order on (value, piece) - NaN beats any number, then the smaller value, then the earlier piece - each
+// with its own time and point
+inline void fold_clearance_exact(int B, const int *poff, const double *T, const double *rows, double *cand_out, unsigned *flags) {
+    fold_rows<FRX_CLEAR_EXACT_FIELDS>(B, poff, T, rows, cand_out, flags, FRX_CLEAR_FLAG_NONFINITE,
+        [](double *o, const double *r, int k, double t0) {
+            const int val[2] = {FRX_CLEAR_EXACT_ELL, FRX_CLEAR_EXACT_DIST}, tm[2] = {FRX_CLEAR_EXACT_T_ELL, FRX_CLEAR_EXACT_T_DIST},
+                      pt[2] = {FRX_CLEAR_EXACT_I_ELL, FRX_CLEAR_EXACT_I_DIST};
+            for (int f = 0; f < 2; f++) {
+                const double a = o[val[f]], c = r[val[f]];
+                if (k == 0 || (a == a && (c < a || c != c))) { o[val[f]] = c; o[tm[f]] = t0 + r[tm[f]]; o[pt[f]] = r[pt[f]]; }
+            }
+        },
+        [](const double *o) { return o[FRX_CLEAR_EXACT_ELL] < 1.0 ? FRX_CLEAR_FLAG_COLLISION : 0u; });
+    if (!flags) return;
+    for (int b = 0; b < B; b++)
+        if (poff[b + 1] == poff[b]) flags[b] = 0u;                       // (a row nobody wrote says nothing: ELL = 0 in it is no collision)
 }
 
 // contain: N_CONTACT summed; OUTSIDE and CENTRE maxima in piece order (strict > replaces, a value that is not a number takes the field and stays); the

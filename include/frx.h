@@ -334,7 +334,8 @@ int frx_trajectory_check_device(frx_problem *p, const double *T_dev, const doubl
  * A candidate's row reduces its pieces in piece order (max; min for THRUST_MIN; the first piece wins a tie, NaN propagates); its times count
  * from the candidate's start.  Flags per candidate: FRX_CHECK_FLAG_SPEED / THRUST_MIN / THRUST_MAX / BODY_RATE / NONFINITE against the handle's
  * own limits with no slack (ACC is not limited).  The corridor is NOT covered: the body's reach past a face is not polynomial in t; judge it
- * with frx_trajectory_check and frx_trajectory_clearance.  Rows are bit-identical run to run and independent of the rest of the batch.
+ * with frx_trajectory_check or, exactly, frx_trajectory_contain; the obstacle cloud itself with frx_trajectory_clearance_exact, which samples nothing
+ * either (frx_trajectory_clearance is its dense form).  Rows are bit-identical run to run and independent of the rest of the batch.
  *   frx_trajectory_extrema        blocking: T[total fine pieces], C[total fine pieces x 18] on the host as frx_optimize returns them;
  *                                 piece_out (P x 10) and flags (B) may be NULL, cand_out (B x 10) may not.
  *   frx_trajectory_extrema_device a pure launch on the caller's stream (no copy, no synchronisation, no allocation): piece rows only, device pointers.
@@ -554,6 +555,63 @@ int frx_trajectory_clearance(frx_problem *p, const double *T, const double *C, i
 int frx_trajectory_clearance_workspace(frx_problem *p, int intervals, int n_obs, size_t *bytes);
 int frx_trajectory_clearance_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, int n_obs, const double *obs_dev,
                                     void *work_dev, double *piece_out_dev, void *hip_stream);
+
+/* Exact clearance certificate of a batch of results against the obstacle cloud, on the device.  frx_trajectory_clearance evaluates the body ellipsoid at
+ * M + 1 instants a piece: a cloud point the body sweeps over between two samples is not seen, and a larger M costs P (M + 1) n_obs tests and still proves
+ * nothing.  These entries find, for every piece, the exact minimum over time and over the cloud of the two quantities the dense form reports - nothing is
+ * sampled.
+ * The body is E = diag(eh, eh, ev) (horiz_half_len twice, vert_half_len) and [xB yB zB] is orthonormal, so for a cloud point o with u = o - p, h = a + g e3,
+ * zB = h / |h| the squared ellipsoid distance is
+ *   q = ((u.u) - (zB.u)^2) / eh^2 + (zB.u)^2 / ev^2,   r = u.u
+ * which is the dense form's q with e0 = e1: the frame's x and y axes drop out, and with them the singularity where the dense frame's yB degenerates; q is
+ * not a number only where h = 0.  In normalised time tau = t / T with w_k = c_k T^k and wh = T^2 (a + g e3), as frx_trajectory_contain forms them:
+ * u = o - p(tau) is a quintic whose constant term is o - w_0 (the difference first), S = u.u has degree 10, Q = wh.wh degree 6, m = u.wh degree 8,
+ *   r = S,   q = (S - m^2 / Q) / eh^2 + (m^2 / Q) / ev^2.
+ * The minima of r over the piece lie among the roots of S' (degree 9) and the piece's ends; those of q among the roots of
+ *   F = ev^2 S' Q^2 - (ev^2 - eh^2) m (2 m' Q - m Q')                                            (degree 21)
+ * (Q^2 times the numerator of d/dtau [ev^2 S + (eh^2 - ev^2) m^2 / Q]) and the ends.  The roots are found as frx_trajectory_extrema finds roots (every
+ * sign change on [0, 1], bracketed by the derivative's roots and bisected down to adjacent doubles).  Candidates: the roots ascending, then tau = 0, then
+ * tau = 1.  The VALUES never come from the expanded polynomials: r and q are evaluated at each candidate directly from p and wh, so an error in a root
+ * enters a minimum only to second order and every reported number is a value the trajectory attains.  A point's minimum follows the rule of
+ * frx_trajectory_extrema (the first candidate wins a tie, a NaN takes the field and stays); a q that rounds below 0 is taken as 0.
+ * Fields of a piece's row (FRX_CLEAR_EXACT_FIELDS doubles, times local in [0, T]):
+ *   FRX_CLEAR_EXACT_ELL      sqrt(min q), dimensionless; >= 1 means free          FRX_CLEAR_EXACT_DIST     sqrt(min r), metres from the body centre
+ *   FRX_CLEAR_EXACT_T_ELL    the local time tau T at which min q is attained       FRX_CLEAR_EXACT_I_ELL    the index i of the cloud point that attains it
+ *   FRX_CLEAR_EXACT_T_DIST, FRX_CLEAR_EXACT_I_DIST   likewise for min r
+ * Over the cloud each minimum is taken under a total order: NaN first, then the smaller value, then the lower i.  T not finite or <= 0, or a coefficient
+ * not finite: all six NaN.  A cloud point that is not finite makes ELL NaN (DIST is NaN or +inf of that point) and is never hidden.
+ * Most of the cloud is far from a piece, and the library leaves such points out by rules that are rigorous (fast-racing_amd/csrc/frx_clear_exact_kernel.hpp:
+ * a lower bound from the box of the piece's Bezier control points against upper bounds that are values at candidates): they change the work, never a
+ * row.  Rows are bit-identical run to run, between the forms, whatever else is in the batch and however the cloud is split over workgroups.
+ * Candidate rows: each of the two minima with its time and point under the same order, an earlier piece before a later one; times from the candidate's
+ * start on the durations summed left to right.  Flags: FRX_CLEAR_FLAG_COLLISION (ELL < 1), FRX_CLEAR_FLAG_NONFINITE.
+ * What the certificate is NOT.  The instants are exact to the root finder's bisection (adjacent doubles of tau where the critical polynomial changes
+ * sign); a critical point at which the polynomial touches zero without changing sign is no candidate, which can only miss a point of inflection, never
+ * a minimum.  h = 0 (free fall) leaves the attitude undefined: q is not a number at such an instant and ELL reports it.
+ *   frx_trajectory_clearance_exact            blocking, host pointers: T[total fine pieces], C[total fine pieces x 18], obs[n_obs x 3]; piece_out (P x 6)
+ *                                             and flags (B) may be NULL, cand_out (B x 6) may not.  Uses the handle's cloud buffer as the dense form does
+ *                                             and grows it (FRX_ERR_ALLOC when it cannot).
+ *   frx_trajectory_clearance_exact_workspace  bytes of scratch the device form needs: a function of (total fine pieces, n_obs) alone, never of the device;
+ *                                             never 0.
+ *   frx_trajectory_clearance_exact_device     pure launches on the caller's stream, device pointers: no copy, no synchronisation, no allocation (capturable
+ *                                             in a hipGraph); piece rows only.
+ *   frx_clearance_exact_fold                  host only, no handle: candidate rows and flags from piece rows (for callers of the _device form); candidate b
+ *                                             owns the pieces piece_off[b] .. piece_off[b + 1] - 1; cand_out and flags may each be NULL.
+ * FRX_ERR_INVALID_ARG, reported before a device is looked for: NULL pointers (the optional outputs excepted), n_obs < 1 or > FRX_CLEAR_MAX_POINTS, B < 1
+ * or a falling piece_off (frx_clearance_exact_fold).  FRX_ERR_NO_DEVICE without a device.  Serves both kinds of handle. */
+#define FRX_CLEAR_EXACT_FIELDS 6
+#define FRX_CLEAR_EXACT_ELL 0
+#define FRX_CLEAR_EXACT_DIST 1
+#define FRX_CLEAR_EXACT_T_ELL 2
+#define FRX_CLEAR_EXACT_I_ELL 3
+#define FRX_CLEAR_EXACT_T_DIST 4
+#define FRX_CLEAR_EXACT_I_DIST 5
+int frx_trajectory_clearance_exact(frx_problem *p, const double *T, const double *C, int n_obs, const double *obs, double *piece_out, double *cand_out,
+                                   unsigned *flags);
+int frx_trajectory_clearance_exact_workspace(frx_problem *p, int n_obs, size_t *bytes);
+int frx_trajectory_clearance_exact_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_obs, const double *obs_dev, void *work_dev,
+                                          double *piece_out_dev, void *hip_stream);
+int frx_clearance_exact_fold(int B, const int *piece_off, const double *T, const double *rows, double *cand_out, unsigned *flags);
 
 /* Replaces ~cuda_computer / kill_kernel (cc.cu:44-49, 566-579; GPU.hpp:907-909). */
 void frx_problem_destroy(frx_problem *p);

@@ -136,6 +136,17 @@ int frx_debug_compact_from_history(int m, int n, int hs, int bound, int newest, 
  * handle, 0 returns to the library's rule.  Rows do not depend on it. */
 int frx_debug_set_clear_chunk(frx_problem *p, int points);
 
+/* Tests: frx_trajectory_clearance_exact splits the cloud into chunks, one one-wave workgroup per (piece, chunk) (fast-racing_amd/csrc/frx_device.hpp,
+ * clear_exact_geometry), and leaves out the points its cull proves irrelevant.  chunk_points > 0 forces that many cloud points per chunk (the last one shorter)
+ * for every later exact clearance call and workspace query on the handle, 0 returns to the library's rule; cull_on == 0 makes every point a survivor that
+ * runs both tasks.  Rows depend on neither.
+ * frx_debug_clear_exact_counts: per piece (survivors[P], ell_tasks[P]) how many points survived the cull and how many ran the degree-21 task in the last exact
+ * clearance call on the handle, summed over the chunks; read from the partials that call left in its workspace, which must still be alive (the blocking form's
+ * is the handle's own cloud buffer: a dense frx_trajectory_clearance call on the handle lays it out anew, and the counts are FRX_ERR_INVALID_ARG until the next exact
+ * call).  Waits for the device. */
+int frx_debug_set_clear_exact(frx_problem *p, int chunk_points, int cull_on);
+int frx_debug_clear_exact_counts(frx_problem *p, int *survivors, int *ell_tasks);
+
 /* Tests: the host fold of frx_trajectory_check (kind 0), _extrema (1) and _clearance (2), piece rows to candidate rows and flag words - the code the blocking
  * entries run (fast-racing_amd/csrc/frx_traj_fold.hpp) - on rows the caller supplies: candidate b owns the pieces piece_off[b] .. piece_off[b + 1] - 1 of T[] and
  * rows[] (FRX_CHECK_ / FRX_EXTREMA_ / FRX_CLEAR_FIELDS doubles a piece); limits[4] = {vel_max, thr_acc_min, thr_acc_max, body_rate_max}.  cand_out ([B][fields])
