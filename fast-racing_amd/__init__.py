@@ -74,6 +74,8 @@ ABI_SYMBOLS = [
     "frx_trajectory_clearance_exact", "frx_trajectory_clearance_exact_workspace", "frx_trajectory_clearance_exact_device", "frx_clearance_exact_fold",
     "frx_corridor_generate_batch", "frx_corridor_generate_batch_device",
     "frx_enumerate_vertices_batch", "frx_enumerate_vertices_batch_device", "frx_corridor_slots_to_tasks_device",
+    "frx_map_esdf", "frx_map_esdf_workspace", "frx_map_esdf_device", "frx_map_esdf_on_device", "frx_map_mark_cloud_device",
+    "frx_trajectory_map_distance", "frx_trajectory_map_distance_device", "frx_map_distance_fold",
 ]
 # diagnostics, include/frx_debug.h: not part of the drop-in boundary
 DEBUG_SYMBOLS = [
@@ -103,6 +105,11 @@ CLEAR_FLAG_COLLISION, CLEAR_FLAG_NONFINITE = 1, 2
 CLEAR_TILE, CLEAR_PASS = 64, 1024
 # frx_trajectory_clearance_exact (include/frx.h): fields of a row; its flags are the CLEAR_FLAG_* bits
 CLEAR_EXACT_FIELDS = ("ell", "dist", "t_ell", "i_ell", "t_dist", "i_dist")
+# frx_trajectory_map_distance (include/frx.h): fields of a row and flag bits
+MAPDIST_FIELDS = ("dist", "worst_t", "worst_cell", "outside")
+MAPDIST_FLAG_BELOW, MAPDIST_FLAG_OUTSIDE, MAPDIST_FLAG_NONFINITE = 1, 2, 4
+# frx_map_esdf (include/frx.h, fast-racing_amd/csrc/frx_esdf_plan.hpp): the most cells along x and along y or z, the lanes of a workgroup of every pass
+ESDF_MAX_LINE, ESDF_MAX_DIM, ESDF_THREADS = 8192, 16384, 256
 # frx_trajectory_sample (include/frx.h): doubles of a row and the named parts of it (FRX_SAMPLE_*)
 SAMPLE_FIELDS = 20
 SAMPLE_VIEWS = dict(pos=slice(0, 3), vel=slice(3, 6), acc=slice(6, 9), jerk=slice(9, 12), thrust=12, quat=slice(13, 17), omega=slice(17, 20))
@@ -225,6 +232,14 @@ def lib():
         L.frx_jps_tables.argtypes = [_vp] * 6
         L.frx_jps_plan.argtypes = [_vp, _vp, _vp, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         L.frx_route_plan.argtypes = [_vp, _vp, _vp, C.c_int, _vp, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]
+        L.frx_map_esdf.argtypes = [_vp] * 4
+        L.frx_map_esdf_workspace.argtypes = [_vp, C.POINTER(C.c_size_t)]
+        L.frx_map_esdf_device.argtypes = [_vp] * 6
+        L.frx_map_esdf_on_device.argtypes = [C.c_int] + [_vp] * 4
+        L.frx_map_mark_cloud_device.argtypes = [_vp, _vp, C.c_int, _vp, _vp, _vp]
+        L.frx_trajectory_map_distance.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp]
+        L.frx_trajectory_map_distance_device.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]
+        L.frx_map_distance_fold.argtypes = [C.c_int, _vp, _vp, _vp, C.c_double, _vp, _vp]
         for name in ABI_SYMBOLS + DEBUG_SYMBOLS:
             fn = getattr(L, name)
             if name not in ("frx_version", "frx_last_error", "frx_device_count", "frx_lbfgs_default_params",
@@ -469,6 +484,26 @@ class VoxelMap:
         _check(lib().frx_debug_map_blocked_device(device, C.byref(self._s), len(a), a.ctypes.data, b.ctypes.data, out.ctypes.data))
         return out.astype(bool)
 
+    def _esdf(self, fields, call):
+        n = self.cells.size
+        out = {k: np.empty(n) for k in fields}
+        if not out or set(out) - {"pos", "neg", "all"}:
+            raise ValueError(f"esdf: fields must name some of pos, neg, all, got {tuple(fields)}")
+        _check(call(*[out[k].ctypes.data if k in out else None for k in ("pos", "neg", "all")]))
+        return out
+
+    def esdf(self, fields=("pos", "neg", "all")):
+        """frx_map_esdf on the host: dict of the named fields, each a float64 array over the cells (x fastest); a field not named is not computed."""
+        return self._esdf(fields, lambda *o: lib().frx_map_esdf(C.byref(self._s), *o))
+
+    def esdf_on_device(self, fields=("pos", "neg", "all"), device: int = 0):
+        """frx_map_esdf_on_device: the same fields from the device (upload, five launches, download)."""
+        return self._esdf(fields, lambda *o: lib().frx_map_esdf_on_device(int(device), C.byref(self._s), *o))
+
+    def device_struct(self, cells_dev: int = 0) -> VoxelMapStruct:
+        """A frx_voxel_map with this map's origin, dim and res whose cells point to device memory at cells_dev (the device forms take such a struct)."""
+        return VoxelMapStruct((C.c_double * 3)(*self.origin), (C.c_int * 3)(*[int(d) for d in self.dim]), self.res, cells_dev or None)
+
     def plan(self, start, goal, eps: float = 1.0, use_jps: bool = False, cap: int = 1 << 16):
         """frx_jps_plan -> dict(status, raw_path, path, sample_path, expanded)."""
         start = np.ascontiguousarray(start, dtype=np.float64); goal = np.ascontiguousarray(goal, dtype=np.float64)
@@ -487,6 +522,51 @@ class VoxelMap:
         _check(lib().frx_route_plan(C.byref(self._s), start.ctypes.data, goal.ctypes.data, len(gates), gates.ctypes.data if len(gates) else None,
                                     float(eps), int(use_jps), int(threads), cap, C.byref(n), out.ctypes.data, st.ctypes.data, ex.ctypes.data))
         return out[:n.value].copy(), st, ex
+
+
+def map_esdf(vmap: VoxelMap, fields=("pos", "neg", "all")):
+    """frx_map_esdf: the distance field of a VoxelMap on the host (VoxelMap.esdf)."""
+    return vmap.esdf(fields)
+
+
+def map_esdf_on_device(vmap: VoxelMap, fields=("pos", "neg", "all"), device: int = 0):
+    """frx_map_esdf_on_device: the same field from the device (VoxelMap.esdf_on_device)."""
+    return vmap.esdf_on_device(fields, device)
+
+
+def map_esdf_workspace(dim) -> int:
+    """frx_map_esdf_workspace: bytes of device scratch map_esdf_device needs for a grid of dim cells; FrxError with code -1 / -5 for a grid it refuses."""
+    d = (C.c_int * 3)(*[int(v) for v in dim])
+    n = C.c_size_t(0)
+    _check(lib().frx_map_esdf_workspace(d, C.byref(n)))
+    return int(n.value)
+
+
+def map_esdf_device(map_struct: VoxelMapStruct, pos_dev: int, neg_dev: int, all_dev: int, work_dev: int, stream: int = 0):
+    """frx_map_esdf_device: five launches on `stream`; map_struct's cells and the other addresses (integers, 0 = that field is not computed) are device memory."""
+    _check(lib().frx_map_esdf_device(C.byref(map_struct), pos_dev or None, neg_dev or None, all_dev or None, work_dev or None, stream))
+
+
+def map_mark_cloud_device(map_struct: VoxelMapStruct, cells_dev: int, n_pts: int, pts_dev: int, n_inside_dev: int, stream: int = 0):
+    """frx_map_mark_cloud_device: the cells (int8 at cells_dev) holding the n_pts points at pts_dev become 100, the int32 at n_inside_dev the number of points
+    inside; launches on `stream`, device addresses as integers."""
+    _check(lib().frx_map_mark_cloud_device(C.byref(map_struct), cells_dev or None, int(n_pts), pts_dev or None, n_inside_dev or None, stream))
+
+
+def map_distance_fold(piece_rows, T, piece_off, margin: float):
+    """Candidate rows (B, 4) and MAPDIST_FLAG_* words (B,) uint32 from the piece rows (P, 4) of trajectory_map_distance_device (frx_map_distance_fold, host
+    only): candidate b owns the pieces piece_off[b] .. piece_off[b + 1] - 1.  A candidate without pieces keeps a row of zeros."""
+    piece_off = np.ascontiguousarray(piece_off, dtype=np.int32).reshape(-1)
+    rows = np.ascontiguousarray(piece_rows, dtype=np.float64).reshape(-1, len(MAPDIST_FIELDS))
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1)
+    B = piece_off.size - 1
+    if B >= 1 and (rows.shape[0] < int(piece_off.max()) or T.size < int(piece_off.max())):
+        raise ValueError(f"map_distance_fold: {rows.shape[0]} rows and {T.size} durations for piece_off up to {int(piece_off.max())}")
+    cand = np.zeros((max(B, 0), len(MAPDIST_FIELDS))); flags = np.zeros(max(B, 0), np.uint32)
+    pad = np.zeros(1)
+    _check(lib().frx_map_distance_fold(B, piece_off.ctypes.data, (T if T.size else pad).ctypes.data, (rows if rows.size else pad).ctypes.data, float(margin),
+                                       cand.ctypes.data, flags.ctypes.data))
+    return cand, flags
 
 
 def grid_search(cmap, dim, start, goal, eps: float = 1.0, use_jps: bool = False, max_expand: int = -1, cap: int = 1 << 20):
@@ -965,6 +1045,22 @@ class Problem:
         """frx_trajectory_clearance_exact_device: the piece rows (P x 6 doubles at out_ptr) as pure launches on `stream`, device pointers (work_ptr: the
         scratch trajectory_clearance_exact_workspace asks for), no copy, no synchronisation, no allocation; clearance_exact_fold gives the candidate rows."""
         _check(lib().frx_trajectory_clearance_exact_device(self.h, T_ptr, C_ptr, int(n_obs), obs_ptr, work_ptr or None, out_ptr, stream))
+
+    def trajectory_map_distance(self, T, Cf, vmap, field, margin: float = 0.0, intervals: int = 256):
+        """The batch (T, C) screened against `field`, a float64 array over the cells of the VoxelMap vmap - pos or all of its esdf(), or the caller's own
+        (frx_trajectory_map_distance): dict(piece (P, 4), cand (B, 4), flags (B,) uint32 of MAPDIST_FLAG_*) plus the candidate rows' fields by name
+        (MAPDIST_FIELDS: dist, worst_t, worst_cell, outside)."""
+        T, Cf = self._traj_TC("trajectory_map_distance", T, Cf)
+        field = np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
+        if field.size != vmap.cells.size:
+            raise ValueError(f"trajectory_map_distance: field must hold {vmap.cells.size} values, got {field.size}")
+        return self._traj_folded(MAPDIST_FIELDS, "cand", lib().frx_trajectory_map_distance, T.ctypes.data, Cf.ctypes.data, int(intervals), C.cast(C.pointer(vmap._s), C.c_void_p),
+                                 field.ctypes.data, float(margin))
+
+    def trajectory_map_distance_device(self, T_ptr: int, C_ptr: int, map_struct, field_ptr: int, out_ptr: int, intervals: int = 256, stream: int = 0):
+        """frx_trajectory_map_distance_device: the piece rows (P x 4 doubles at out_ptr) as one launch on `stream`, device pointers (map_struct: a VoxelMapStruct,
+        its cells are not read), no copy, no synchronisation, no allocation; map_distance_fold gives the candidate rows."""
+        _check(lib().frx_trajectory_map_distance_device(self.h, T_ptr, C_ptr, int(intervals), C.byref(map_struct), field_ptr or None, out_ptr or None, stream))
 
     def set_clear_exact(self, chunk_points: int = 0, cull_on: bool = True):
         """Tests (frx_debug_set_clear_exact): cloud points per chunk of every later exact clearance call on the handle (0 = the library's own split) and

@@ -1069,6 +1069,52 @@ int frx_debug_clear_exact_counts(frx_problem *p, int *survivors, int *ell_tasks)
     return FRX_OK;
 }
 
+int frx_map_distance_fold(int B, const int *piece_off, const double *T, const double *rows, double margin, double *cand_out, unsigned *flags) {
+    if (B < 1 || !piece_off || !T || !rows) return fail(FRX_ERR_INVALID_ARG, "frx_map_distance_fold: B must be >= 1 and piece_off, T, rows not NULL");
+    if (margin != margin) return fail(FRX_ERR_INVALID_ARG, "frx_map_distance_fold: margin is not a number");
+    if (piece_off[0] < 0) return fail(FRX_ERR_INVALID_ARG, "frx_map_distance_fold: piece_off[0] must be >= 0");
+    for (int b = 0; b < B; b++)
+        if (piece_off[b + 1] < piece_off[b]) return fail(FRX_ERR_INVALID_ARG, "frx_map_distance_fold: piece_off must not fall (candidate " + std::to_string(b) + ")");
+    frx::fold_map_distance(B, piece_off, T, rows, margin, cand_out, flags);
+    return FRX_OK;
+}
+
+// argument rules of both forms of frx_trajectory_map_distance, checked before a device is looked for and before the handle is read
+static int map_distance_args(frx_problem *p, const void *T, const void *C, int intervals, const frx_voxel_map *map, const void *field, const void *out) {
+    if (!p || !T || !C || !map || !field || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
+    if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
+    if (!(map->res > 0) || map->dim[0] <= 0 || map->dim[1] <= 0 || map->dim[2] <= 0)
+        return fail(FRX_ERR_INVALID_ARG, "frx_trajectory_map_distance: the map needs res > 0 and dim > 0 on all three axes");
+    if ((long long)map->dim[0] * map->dim[1] > 0x7fffffffLL || (long long)map->dim[0] * map->dim[1] * map->dim[2] > 0x7fffffffLL)
+        return fail(FRX_ERR_INVALID_ARG, "frx_trajectory_map_distance: more than 2^31 - 1 cells");
+    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    return FRX_OK;
+}
+
+int frx_trajectory_map_distance_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, const frx_voxel_map *map, const double *field_dev,
+                                       double *piece_out_dev, void *hip_stream) {
+    static_assert(FRX_MAPDIST_FIELDS == (int)frx::MAPDIST_FIELDS && FRX_MAPDIST_FIELDS <= 20, "frx.h and frx_device.hpp agree, and the rows fit the P x 20 staging");
+    FRX_TRY(map_distance_args(p, T_dev, C_dev, intervals, map, field_dev, piece_out_dev));
+    HIP_TRY((hipError_t)frx::launch_map_distance(p->P, T_dev, C_dev, intervals, map->origin, map->dim, map->res, field_dev, piece_out_dev, hip_stream));
+    return FRX_OK;
+}
+
+int frx_trajectory_map_distance(frx_problem *p, const double *T, const double *C, int intervals, const frx_voxel_map *map, const double *field, double margin,
+                                double *piece_out, double *cand_out, unsigned *flags) {
+    FRX_TRY(map_distance_args(p, T, C, intervals, map, field, cand_out));
+    if (margin != margin) return fail(FRX_ERR_INVALID_ARG, "frx_trajectory_map_distance: margin is not a number");
+    HIP_TRY(hipSetDevice(p->device));
+    const size_t n_rows = (size_t)FRX_MAPDIST_FIELDS * p->P, n_cells = (size_t)map->dim[0] * map->dim[1] * map->dim[2];
+    FRX_TRY(grow(p->d_mapdist, n_rows + n_cells, "frx_trajectory_map_distance"));
+    double *d_rows = p->d_mapdist.p, *d_field = d_rows + n_rows;
+    FRX_TRY(stage_TC(p, T, C));
+    HIP_TRY(hipMemcpyAsync(d_field, field, sizeof(double) * n_cells, hipMemcpyHostToDevice, p->stream));
+    FRX_TRY(frx_trajectory_map_distance_device(p, p->d_T.p, p->d_C.p, intervals, map, d_field, d_rows, p->stream));
+    FRX_TRY(fetch_rows(p, d_rows, n_rows, piece_out));
+    frx::fold_map_distance(p->B, p->poff.data(), T, p->h_out20.p, margin, cand_out, flags);
+    return FRX_OK;
+}
+
 // Tests: the fold of the blocking check (kind 0), extrema (1) and clearance (2) entries on piece rows the caller made up; no handle, no device.
 int frx_debug_fold_rows(int kind, int B, const int *piece_off, const double *T, const double *rows, const double *limits, double *cand_out, unsigned *flags) {
     if (kind < 0 || kind > 2 || B < 1 || !piece_off || !T || !rows || !limits) return fail(FRX_ERR_INVALID_ARG, "kind must be 0, 1 or 2, B >= 1 and no input NULL");

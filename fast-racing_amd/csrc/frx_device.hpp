@@ -193,6 +193,21 @@ inline int clear_exact_geometry(int P, int n_obs, int force, int *chunk, int *nc
 int launch_clear_exact(const DevProblem &dp, const double *T, const double *C, int n_obs, const double *obs, int chunk, int nchunks, int cull, double *work,
                        double *rows, void *stream);
 
+// ---- the voxel map on the device: distance field, marking of a cloud (frx_esdf_kernel.hpp), screen of a batch against a field (frx_mapdist_kernel.hpp) ----
+struct EsdfLaunch {
+    const signed char *cells; int dim[3]; double res;               // cells: device pointer, x fastest
+    void *work;                                                     // esdf_plan(dim).work_bytes of device scratch (frx_esdf_plan.hpp)
+    double *pos, *neg, *all;                                        // device outputs over the grid, each may be null (not all three)
+};
+enum { MAPDIST_FIELDS = 4 };
+// Pure launches: five kernels (flag words, z pass, column distances, y pass, x pass).  hipErrorInvalidValue for a grid esdf_plan refuses.
+int launch_esdf(const EsdfLaunch &e, void *stream);
+// cells [dim] and n_inside (one int) are device pointers; two kernels (the count's zero, the points), one when n_pts == 0
+int launch_mark_cloud(const double *origin, const int *dim, double res, signed char *cells, int n_pts, const double *pts, int *n_inside, void *stream);
+// rows: [P][4] (frx.h FRX_MAPDIST_*) of the pieces (T, C) against field over the grid (origin, dim, res); T / C / field / rows are device pointers.  One launch.
+int launch_map_distance(int P, const double *T, const double *C, int intervals, const double *origin, const int *dim, double res, const double *field,
+                        double *rows, void *stream);
+
 // ---- device-vector L-BFGS (frx_lbfgs_kernels.hpp) ----
 struct DvBuffers;
 struct DvLaunch {

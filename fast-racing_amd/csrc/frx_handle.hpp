@@ -115,6 +115,7 @@ struct frx_problem {
     DevBuf<double> d_sample;                                // frx_trajectory_sample: [B][S][20] rows, then [B][S] times; grown as needed
     DevBuf<double> d_gates;                                 // frx_trajectory_gates: [n_gates][10] rows, the records [n_gates][9], then gate_off [B + 1] as ints; grown as needed
     DevBuf<double> d_clear;                                 // frx_trajectory_clearance: [P][4] rows, the cloud [n_obs][3], then the partials [P][chunks][4]; grown as needed
+    DevBuf<double> d_mapdist;                               // frx_trajectory_map_distance: [P][4] rows, then the field over the map's grid; grown as needed
     int clear_chunk = 0;                                    // tests (frx_debug_set_clear_chunk): > 0 = cloud points per chunk, 0 = the library's own split
     int clx_chunk = 0, clx_cull = 1;                        // tests (frx_debug_set_clear_exact): cloud points per chunk of frx_trajectory_clearance_exact (0 = the library's own split), the cull on / off
     const double *clx_last_work = nullptr; int clx_last_nchunks = 0;   // the partials of the last exact clearance call on the handle (frx_debug_clear_exact_counts reads its counts)

@@ -27,6 +27,7 @@
 #include "../../include/frx.h"
 #include "../../include/frx_debug.h"
 #include "frx_device.hpp"
+#include "frx_esdf_plan.hpp"
 #include "frx_internal.hpp"
 
 namespace {
@@ -557,6 +558,68 @@ int frx_enumerate_vertices_batch(int device, int B, const int *coarse_n, const i
         for (int t = 0; t < NT && e == hipSuccess; t++) std::memcpy(v_rec + 3 * (size_t)v_off[t], stage.data() + (size_t)3 * widest * t, sizeof(double) * 3 * (size_t)nv[t]);
     }
     cleanup();
+    if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return FRX_OK;
+}
+
+// ---- the voxel map's distance field (frx_esdf_kernel.hpp): the device form is five launches, the blocking form is those between an upload and a download ----
+int frx_map_esdf_device(const frx_voxel_map *map, double *pos_dev, double *neg_dev, double *all_dev, void *work_dev, void *hip_stream) {
+    const char *who = "frx_map_esdf_device";
+    if (int rc = frx::esdf_map_args(map, who)) return rc;
+    if (!pos_dev && !neg_dev && !all_dev) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": pos, neg and all are all NULL");
+    if (!work_dev) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": work_dev is NULL: frx_map_esdf_workspace says how much scratch the launches need");
+    if (frx_device_count() < 1) return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    frx::EsdfLaunch L;
+    L.cells = map->cells; L.res = map->res; L.work = work_dev; L.pos = pos_dev; L.neg = neg_dev; L.all = all_dev;
+    for (int i = 0; i < 3; i++) L.dim[i] = map->dim[i];
+    const hipError_t e = (hipError_t)frx::launch_esdf(L, hip_stream);
+    if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return FRX_OK;
+}
+
+int frx_map_esdf_on_device(int device, const frx_voxel_map *map, double *pos, double *neg, double *all) {
+    const char *who = "frx_map_esdf_on_device";
+    if (int rc = frx::esdf_map_args(map, who)) return rc;
+    if (!pos && !neg && !all) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": pos, neg and all are all NULL");
+    if (frx_device_count() < 1) return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    DeviceGuard restore_device;
+    if (hipSetDevice(device) != hipSuccess) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": device ordinal out of range");
+    const frx::EsdfPlan plan = frx::esdf_plan(map->dim);
+    const size_t n = (size_t)plan.cells;
+    signed char *d_cells = nullptr; void *d_work = nullptr; double *d_out[3] = {nullptr, nullptr, nullptr};
+    double *host[3] = {pos, neg, all};
+    auto cleanup = [&]() { for (void *q : {(void *)d_cells, d_work, (void *)d_out[0], (void *)d_out[1], (void *)d_out[2]}) if (q) (void)hipFree(q); };
+    bool ok = hipMalloc((void **)&d_cells, n) == hipSuccess && hipMalloc(&d_work, plan.work_bytes) == hipSuccess;
+    for (int k = 0; k < 3 && ok; k++)
+        if (host[k]) ok = hipMalloc((void **)&d_out[k], sizeof(double) * n) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        cleanup();
+        return frx::set_error(FRX_ERR_ALLOC, std::string(who) + ": device buffers (" + std::to_string(plan.work_bytes) + " bytes of scratch)");
+    }
+    hipError_t e = hipMemcpy(d_cells, map->cells, n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cleanup(); return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+    frx_voxel_map dmap = *map;
+    dmap.cells = d_cells;
+    const int rc = frx_map_esdf_device(&dmap, d_out[0], d_out[1], d_out[2], d_work, nullptr);
+    if (rc != FRX_OK) { cleanup(); return rc; }
+    e = hipStreamSynchronize(nullptr);
+    for (int k = 0; k < 3 && e == hipSuccess; k++)
+        if (host[k]) e = hipMemcpy(host[k], d_out[k], sizeof(double) * n, hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return FRX_OK;
+}
+
+int frx_map_mark_cloud_device(const frx_voxel_map *map, signed char *cells_dev, int n_pts, const double *pts_dev, int *n_inside_dev, void *hip_stream) {
+    const char *who = "frx_map_mark_cloud_device";
+    if (!map || !cells_dev || !n_inside_dev || n_pts < 0 || (n_pts > 0 && !pts_dev)) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null argument or n_pts < 0");
+    if (!(map->res > 0) || map->dim[0] <= 0 || map->dim[1] <= 0 || map->dim[2] <= 0)
+        return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": the map needs res > 0 and dim > 0 on all three axes");
+    if ((long long)map->dim[0] * map->dim[1] > 0x7fffffffLL || (long long)map->dim[0] * map->dim[1] * map->dim[2] > 0x7fffffffLL)
+        return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": more than 2^31 - 1 cells");
+    if (frx_device_count() < 1) return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    const hipError_t e = (hipError_t)frx::launch_mark_cloud(map->origin, map->dim, map->res, cells_dev, n_pts, pts_dev, n_inside_dev, hip_stream);
     if (e != hipSuccess) return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
     return FRX_OK;
 }

@@ -22,6 +22,7 @@
 // across faces.  The test suite's restatement evaluates the same expressions in IEEE double without fusing.
 #include "../../include/frx.h"
 #include "../../include/frx_debug.h"
+#include "frx_esdf_host.hpp"
 #include "frx_internal.hpp"
 
 #include <algorithm>
@@ -784,6 +785,24 @@ int frx_map_mark_cloud(const double *origin, const int *dim, double res, int n_p
     return marked;
 }
 
+int frx_map_esdf_workspace(const int *dim, size_t *bytes) {
+    if (!dim || !bytes) return frx::set_error(FRX_ERR_INVALID_ARG, "frx_map_esdf_workspace: null argument");
+    const frx::EsdfPlan plan = frx::esdf_plan(dim);
+    if (plan.verdict == frx::ESDF_INVALID) return frx::set_error(FRX_ERR_INVALID_ARG, "frx_map_esdf_workspace: dim must be > 0 on all three axes");
+    if (plan.verdict == frx::ESDF_CAPACITY)
+        return frx::set_error(FRX_ERR_CAPACITY, "frx_map_esdf_workspace: at most " + std::to_string((int)frx::ESDF_MAX_LINE) + " cells along x, " +
+                                                    std::to_string((int)frx::ESDF_MAX_DIM) + " along y and z, 2^31 - 1 in all");
+    *bytes = plan.work_bytes;
+    return FRX_OK;
+}
+
+int frx_map_esdf(const frx_voxel_map *map, double *pos, double *neg, double *all) {
+    if (int rc = frx::esdf_map_args(map, "frx_map_esdf")) return rc;
+    if (!pos && !neg && !all) return frx::set_error(FRX_ERR_INVALID_ARG, "frx_map_esdf: pos, neg and all are all NULL");
+    frx::esdf_host(map->cells, map->dim, map->res, pos, neg, all);
+    return FRX_OK;
+}
+
 int frx_map_is_blocked(const double *a, const double *b, void *map) {
     const frx_voxel_map *m = static_cast<const frx_voxel_map *>(map);
     VoxelMap vm{m};
@@ -856,3 +875,16 @@ int frx_route_plan(const frx_voxel_map *map, const double *start, const double *
     return FRX_OK;
 }
 }
+
+namespace frx {
+int esdf_map_args(const frx_voxel_map *map, const char *who) {
+    if (!map || !map->cells) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null map or cells");
+    if (!(map->res > 0)) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": res must be above 0");
+    const EsdfPlan plan = esdf_plan(map->dim);
+    if (plan.verdict == ESDF_INVALID) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": dim must be > 0 on all three axes");
+    if (plan.verdict == ESDF_CAPACITY)
+        return set_error(FRX_ERR_CAPACITY, std::string(who) + ": at most " + std::to_string((int)ESDF_MAX_LINE) + " cells along x, " + std::to_string((int)ESDF_MAX_DIM) +
+                                               " along y and z, 2^31 - 1 in all");
+    return FRX_OK;
+}
+} // namespace frx

@@ -1,4 +1,4 @@
-// Piece rows -> candidate rows and flag words of frx_trajectory_check / _extrema / _clearance / _clearance_exact / _contain (include/frx.h documents the rows).  Plain C++: no HIP
+// Piece rows -> candidate rows and flag words of frx_trajectory_check / _extrema / _clearance / _clearance_exact / _contain / _map_distance (include/frx.h documents the rows).  Plain C++: no HIP
 // and no handle, so the blocking entries (frx_api.cpp), frx_debug_fold_rows, frx_contain_fold and a host-only program share this one implementation.
 //
 // One shape: the candidates b = 0..B-1 own the pieces poff[b]..poff[b+1]-1 of T[] and of rows[] (piece rows, FIELDS doubles each), folded in piece order;
@@ -93,6 +93,26 @@ inline void fold_clearance_exact(int B, const int *poff, const double *T, const 
     if (!flags) return;
     for (int b = 0; b < B; b++)
         if (poff[b + 1] == poff[b]) flags[b] = 0u;                       // (a row nobody wrote says nothing: ELL = 0 in it is no collision)
+}
+
+// map distance: the kernel's order on (DIST, piece) - a value that is not a number first, then the smaller value, then the earlier piece - with its time (-1,
+// no sample inside the map, stays -1) and cell; OUTSIDE summed.  A candidate without pieces gets no flag.
+inline void fold_map_distance(int B, const int *poff, const double *T, const double *rows, double margin, double *cand_out, unsigned *flags) {
+    fold_rows<FRX_MAPDIST_FIELDS>(B, poff, T, rows, cand_out, flags, FRX_MAPDIST_FLAG_NONFINITE,
+        [](double *o, const double *r, int k, double t0) {
+            const double a = o[FRX_MAPDIST_DIST], c = r[FRX_MAPDIST_DIST];
+            if (k == 0 || (a == a && (c < a || c != c))) {
+                o[FRX_MAPDIST_DIST] = c; o[FRX_MAPDIST_WORST_CELL] = r[FRX_MAPDIST_WORST_CELL];
+                o[FRX_MAPDIST_WORST_T] = r[FRX_MAPDIST_WORST_CELL] >= 0.0 ? t0 + r[FRX_MAPDIST_WORST_T] : -1.0;
+            }
+            o[FRX_MAPDIST_OUTSIDE] = k == 0 ? r[FRX_MAPDIST_OUTSIDE] : o[FRX_MAPDIST_OUTSIDE] + r[FRX_MAPDIST_OUTSIDE];
+        },
+        [margin](const double *o) {
+            return (o[FRX_MAPDIST_DIST] < margin ? FRX_MAPDIST_FLAG_BELOW : 0u) | (o[FRX_MAPDIST_OUTSIDE] > 0.0 ? FRX_MAPDIST_FLAG_OUTSIDE : 0u);
+        });
+    if (!flags) return;
+    for (int b = 0; b < B; b++)
+        if (poff[b + 1] == poff[b]) flags[b] = 0u;                       // (a row nobody wrote says nothing: DIST = 0 in it is below no margin)
 }
 
 // contain: N_CONTACT summed; OUTSIDE and CENTRE maxima in piece order (strict > replaces, a value that is not a number takes the field and stays); the

@@ -241,6 +241,34 @@ int frx_map_mark_cloud(const double *origin, const int *dim, double res, int n_p
 /* MapUtil::isBlocked (map_util.h:395-425) with the signature of frx_blocked_fn: pass it to frx_corridor_generate with
  * user = the frx_voxel_map.  1 when a cell at or above 100 lies on the 0.8-cell ray walk strictly between a and b. */
 int frx_map_is_blocked(const double *a, const double *b, void *map);
+/* The Euclidean distance field of the map: MapUtil::updateESDF3d / fillESDF (map_util.h:149-278), the buffers getDistance reads (:309-318).  A cell with
+ * cells > 0 is occupied (isOccupied, :326), one with cells == 0 is free (:322), one with cells == -1 is neither.  Over the grid, x fastest:
+ *   pos[c] = res sqrt(d2_occ[c])    d2_occ = the exact squared distance in cells, an integer, from cell c to the nearest occupied cell (0 on one)
+ *   neg[c] = res sqrt(d2_free[c])   likewise to the nearest free cell
+ *   all[c] = pos[c], and where neg[c] > 0.0, all[c] = pos[c] + (-neg[c] + res) with the parenthesis first (:241-243)
+ * Every double is fully determined - one correctly rounded square root, one product, for all two sums in that order, none of it fused - so the forms agree bit
+ * for bit, run to run and inside a graph.  One deliberate difference from the reference: its arithmetic on DBL_MAX gives res sqrt(DBL_MAX) where a map holds no
+ * site of a kind at all; here such a field is +inf, and the combine rule's IEEE outcome stands: all = -inf where only neg is infinite, NaN (the quiet NaN with a clear sign and no payload) where both are.
+ * Any of pos, neg, all may be NULL and is then not computed (all three NULL: FRX_ERR_INVALID_ARG).
+ *   frx_map_esdf             host code on one thread (csrc/frx_esdf_host.hpp): the reference's three lower-envelope passes on integer values; the referee
+ *                            of the device form.
+ *   frx_map_esdf_workspace   bytes of scratch the device form needs for a grid of dim[3]: a function of dim alone, answered without a device.
+ *   frx_map_esdf_device      pure launches on hip_stream of the current device (csrc/frx_esdf_kernel.hpp): no copy, no synchronisation, no allocation
+ *                            (capturable).  map is a host struct whose cells point to device memory; pos_dev, neg_dev, all_dev, work_dev are device pointers.
+ *   frx_map_esdf_on_device   blocking, host pointers: upload, the device form, download.
+ * FRX_ERR_INVALID_ARG, reported before a device is looked for: a NULL map, cells, dim or work_dev, res not above 0, a dim <= 0.  FRX_ERR_CAPACITY, likewise: a
+ * dim[1] or dim[2] above 16384 (3 dim^2 stays inside 31 bits), a dim[0] above 8192 (the x pass keeps a line in LDS), more than 2^31 - 1 cells.
+ * FRX_ERR_NO_DEVICE without a device (the device forms).  Not built: the distance-map planner that reads the field in the reference. */
+int frx_map_esdf(const frx_voxel_map *map, double *pos, double *neg, double *all);
+int frx_map_esdf_workspace(const int *dim, size_t *bytes);
+int frx_map_esdf_device(const frx_voxel_map *map, double *pos_dev, double *neg_dev, double *all_dev, void *work_dev, void *hip_stream);
+int frx_map_esdf_on_device(int device, const frx_voxel_map *map, double *pos, double *neg, double *all);
+/* frx_map_mark_cloud on the DEVICE (setObs, map_util.h:108-136): pure launches on hip_stream, capturable.  map gives origin, dim and res (its cells are not
+ * read); cells_dev (the grid), pts_dev (n_pts x 3) and n_inside_dev (one int: the points inside) are device pointers.  The cell rule is map_blocked's,
+ * round((p - origin) / res - 0.5), none of it fused; the stores are bytes of 100, so racing ones are harmless, and the count is a sum of integers.
+ * FRX_ERR_INVALID_ARG (before a device is looked for): NULL arguments (pts_dev with n_pts == 0 excepted), n_pts < 0, res not above 0, a dim <= 0, more than
+ * 2^31 - 1 cells. */
+int frx_map_mark_cloud_device(const frx_voxel_map *map, signed char *cells_dev, int n_pts, const double *pts_dev, int *n_inside_dev, void *hip_stream);
 /* JPS::GraphSearch::plan (graph_search.h:129-161, graph_search.cpp:79-236) on a dense occupancy array cmap (0 = free, > 0 =
  * occupied, x fastest): A* (use_jps = 0; six face neighbours in 3-D, eight in 2-D -- the only mode plan_manage calls,
  * MinCoPlan_CPU.cpp:15) or jump-point search (26 / 8 neighbours) with heuristic eps * Euclidean distance.  dim[2] = 0 selects
@@ -612,6 +640,42 @@ int frx_trajectory_clearance_exact_workspace(frx_problem *p, int n_obs, size_t *
 int frx_trajectory_clearance_exact_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_obs, const double *obs_dev, void *work_dev,
                                           double *piece_out_dev, void *hip_stream);
 int frx_clearance_exact_fold(int B, const int *piece_off, const double *T, const double *rows, double *cand_out, unsigned *flags);
+
+/* A batch of results screened against a field over the voxel map's grid, on the device: P (M + 1) look-ups that tell a caller which pieces of which
+ * candidates are worth frx_trajectory_clearance or frx_trajectory_clearance_exact - both take any (T, C) batch, so only the doubtful pieces need go there.
+ * field is any double array over map's grid, x fastest: pos or all of frx_map_esdf (what MapUtil::getDistance reads, map_util.h:309-318), or a caller's own.
+ * Every fine piece is sampled at s_j = j (T / M), j = 0..M, M = intervals (1..FRX_CHECK_MAX_INTERVALS; the step is formed first, then multiplied, as in the
+ * check and the clearance).  The sample's cell is map_blocked's: round((p - origin) / res - 0.5) per axis, none of it fused.  A sample outside the map - a
+ * position that is not a number included - is counted and left out of the minimum (the reference reads out of bounds there).
+ * Fields of a piece's row (FRX_MAPDIST_FIELDS doubles):
+ *   FRX_MAPDIST_DIST        the smallest field[cell] over the samples inside the map under the order: not a number first, then the smaller value, then the lower j
+ *   FRX_MAPDIST_WORST_T     s_j of that sample
+ *   FRX_MAPDIST_WORST_CELL  its linear cell index, as a double
+ *   FRX_MAPDIST_OUTSIDE     the number of samples outside the map
+ * A piece with no sample inside: DIST = +inf, WORST_T = WORST_CELL = -1.  A candidate's row keeps that order on (DIST, piece) - an earlier piece before a later
+ * one - with WORST_T counted from the candidate's start on the durations summed left to right (-1 stays -1) and OUTSIDE summed.  Flags per candidate:
+ * FRX_MAPDIST_FLAG_BELOW (DIST < margin), _OUTSIDE (OUTSIDE > 0), _NONFINITE (a field of the row is not finite: DIST = +inf among them); a candidate
+ * without pieces keeps its row and gets no flag.  Rows are bit-identical run to run, between the forms and whatever else is in the batch.
+ *   frx_trajectory_map_distance         blocking, host pointers: T[total fine pieces], C[total fine pieces x 18], field[cells]; piece_out (P x 4) and flags (B)
+ *                                       may be NULL, cand_out (B x 4) may not.  Keeps one device buffer per handle for the field and grows it.
+ *   frx_trajectory_map_distance_device  one launch on the caller's stream, device pointers: no copy, no synchronisation, no allocation (capturable); piece rows only.
+ *   frx_map_distance_fold               host only, no handle: candidate rows and flags from piece rows; candidate b owns the pieces piece_off[b] ..
+ *                                       piece_off[b + 1] - 1; cand_out and flags may each be NULL.
+ * FRX_ERR_INVALID_ARG, reported before a device is looked for: NULL pointers (the optional outputs excepted; map->cells is not read), intervals out of range,
+ * res not above 0, a dim <= 0, more than 2^31 - 1 cells, a margin that is not a number, B < 1 or a falling piece_off (the fold).  Serves both kinds of handle. */
+#define FRX_MAPDIST_FIELDS 4
+#define FRX_MAPDIST_DIST 0
+#define FRX_MAPDIST_WORST_T 1
+#define FRX_MAPDIST_WORST_CELL 2
+#define FRX_MAPDIST_OUTSIDE 3
+#define FRX_MAPDIST_FLAG_BELOW 1u
+#define FRX_MAPDIST_FLAG_OUTSIDE 2u
+#define FRX_MAPDIST_FLAG_NONFINITE 4u
+int frx_trajectory_map_distance(frx_problem *p, const double *T, const double *C, int intervals, const frx_voxel_map *map, const double *field, double margin,
+                                double *piece_out, double *cand_out, unsigned *flags);
+int frx_trajectory_map_distance_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, const frx_voxel_map *map, const double *field_dev,
+                                       double *piece_out_dev, void *hip_stream);
+int frx_map_distance_fold(int B, const int *piece_off, const double *T, const double *rows, double margin, double *cand_out, unsigned *flags);
 
 /* Replaces ~cuda_computer / kill_kernel (cc.cu:44-49, 566-579; GPU.hpp:907-909). */
 void frx_problem_destroy(frx_problem *p);
