@@ -18,6 +18,7 @@
 #include "../../include/frx.h"
 #include "../../include/frx_debug.h"
 #include "frx_handle.hpp"
+#include "frx_batch_host.hpp"
 #include "frx_launch_forms.hpp"
 #include "frx_problem_tables.hpp"
 #include "frx_host_pool.hpp"
@@ -776,13 +777,7 @@ static int fetch_rows(frx_problem *p, const double *d_rows, size_t n, double *pi
     return FRX_OK;
 }
 // a scratch buffer that grows to `need` doubles
-static int grow(DevBuf<double> &buf, size_t need, const char *entry) {
-    if (buf.n < need && buf.alloc(need) != hipSuccess) {
-        (void)hipGetLastError();                                            // (a failed allocation is no error of a later launch)
-        return fail(FRX_ERR_ALLOC, std::string(entry) + ": cannot allocate " + std::to_string(need * sizeof(double)) + " bytes on the device");
-    }
-    return FRX_OK;
-}
+static int grow(DevBuf<double> &buf, size_t need, const char *entry) { return buf.n < need ? dev_alloc(buf, need, entry) : FRX_OK; }
 #define FRX_TRY(expr) do { const int rc_ = (expr); if (rc_ != FRX_OK) return rc_; } while (0)
 
 int frx_penalty_eval(frx_problem *p, const double *T, const double *C, double *cost, double *gdT, double *gdC) {
@@ -1083,10 +1078,7 @@ int frx_map_distance_fold(int B, const int *piece_off, const double *T, const do
 static int map_distance_args(frx_problem *p, const void *T, const void *C, int intervals, const frx_voxel_map *map, const void *field, const void *out) {
     if (!p || !T || !C || !map || !field || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
     if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
-    if (!(map->res > 0) || map->dim[0] <= 0 || map->dim[1] <= 0 || map->dim[2] <= 0)
-        return fail(FRX_ERR_INVALID_ARG, "frx_trajectory_map_distance: the map needs res > 0 and dim > 0 on all three axes");
-    if ((long long)map->dim[0] * map->dim[1] > 0x7fffffffLL || (long long)map->dim[0] * map->dim[1] * map->dim[2] > 0x7fffffffLL)
-        return fail(FRX_ERR_INVALID_ARG, "frx_trajectory_map_distance: more than 2^31 - 1 cells");
+    FRX_TRY(frx::voxel_map_args(map, "frx_trajectory_map_distance", false));
     if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
     return FRX_OK;
 }

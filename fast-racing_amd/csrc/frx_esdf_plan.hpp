@@ -1,6 +1,6 @@
 // What the distance field of a voxel map (frx_map_esdf*, include/frx.h) decides before anything runs: whether a grid is accepted, how much scratch the device
 // form needs, and the launch geometry of each pass.  Pure functions of the three dimensions: plain C++, no HIP, no environment - shared by the entries
-// (frx_multi.cpp), the launcher (frx_device_esdf.hip), the host referee's argument check (frx_search.cpp), a stand-alone host program
+// (frx_batch.cpp), the launcher (frx_device_esdf.hip), the host referee's argument check (frx_search.cpp), a stand-alone host program
 // (tests/hostcheck/esdf_main.cpp); the CPU tests read its verdict and bytes through frx_map_esdf_workspace.
 #pragma once
 #include <cstddef>

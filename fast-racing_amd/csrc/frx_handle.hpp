@@ -1,4 +1,4 @@
-// The handle behind the C ABI (struct frx_problem) and the small HIP helpers its translation units share: frx_api.cpp (creation, evaluation and trajectory
+// The handle behind the C ABI (struct frx_problem) and the small HIP helpers its translation units share (device buffers: frx_hip_scope.hpp): frx_api.cpp (creation, evaluation and trajectory
 // entries, self-tests), frx_optimize.cpp (the plan drivers) and frx_host_cpus.cpp (CPU budget, NUMA placement).  Private to libfrx.so; host code only.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -14,6 +14,7 @@
 #include "../../include/frx.h"
 #include "frx_device.hpp"
 #include "frx_eval_front.hpp"
+#include "frx_hip_scope.hpp"
 #include "frx_host_setup.hpp"
 #include "frx_internal.hpp"
 #include "frx_lbfgs.hpp"
@@ -39,24 +40,6 @@ struct HipEventPair {
 using clk = std::chrono::steady_clock;
 inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
 
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-    hipError_t alloc(size_t count) {
-        release();
-        const hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) n = count; else p = nullptr;
-        return e;
-    }
-    hipError_t reserve(size_t count) { return n >= count && p ? hipSuccess : alloc(count); }   // keep what is large enough
-    hipError_t upload(const std::vector<T> &h) {
-        hipError_t e = alloc(h.size());
-        if (e != hipSuccess || h.empty()) return e;
-        return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-};
 template <class T> struct PinBuf {
     T *p = nullptr;
     size_t n = 0;

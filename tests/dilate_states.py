@@ -41,7 +41,7 @@ import dilate_reference as dr  # noqa: E402
 
 BBOX = np.array([4.0, 4.0, 2.5])
 SAFE = 1e-6
-PCAP = 4096                                                       # candidate points of a cell (frx_multi.cpp, frx_device.hpp: CHAIN_PCAP)
+PCAP = 4096                                                       # candidate points of a cell (frx_batch.cpp, frx_device.hpp: CHAIN_PCAP)
 SIZES = [1, 2, 255, 256, 257, 511, 512, 513, 1025]
 COUNTS = [0, 1, 255, 256, 257, 4095, 4096, 4097]
 BIG_PLANES = 90                                                   # tangent planes of an M ~ 4096 state: cap_planes = 96 holds

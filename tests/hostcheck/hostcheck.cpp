@@ -386,3 +386,6 @@ extern "C" void hostcheck_eval_solo_choice(int lds_solo, int solo_char, int min_
 
 // ---- the route of a plan against drivers played from a script (plan_route_main.cpp), and its decisions, for tests/test_plan_route_cpu.py ----
 #include "plan_route_main.cpp"
+
+// ---- what the handle-less batch entries decide on the host (batch_host_main.cpp), for tests/test_batch_host_cpu.py ----
+#include "batch_host_main.cpp"
