@@ -81,7 +81,7 @@ ABI_SYMBOLS = [
 DEBUG_SYMBOLS = [
     "frx_debug_trace", "frx_resident_profile", "frx_debug_direction_log", "frx_debug_direction_log_read", "frx_debug_set_resident_retry",
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
-    "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_eval_geometry", "frx_debug_eval_front", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
+    "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_eval_geometry", "frx_debug_eval_front", "frx_debug_eval_prelude", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_profile_eval_forward", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
     "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device", "frx_debug_dv_layout", "frx_debug_dv_round", "frx_debug_fold_rows", "frx_debug_lane_exchange",
     "frx_debug_set_clear_exact", "frx_debug_clear_exact_counts",
 ]
@@ -162,12 +162,14 @@ def lib():
         L.frx_debug_eval_fused.argtypes = [C.c_void_p]
         L.frx_debug_eval_geometry.argtypes = [C.c_void_p]
         L.frx_debug_eval_front.argtypes = [C.c_void_p]
+        L.frx_debug_eval_prelude.argtypes = [C.c_void_p]
         L.frx_debug_set_eval_solo.argtypes = [C.c_void_p, C.c_int]
         L.frx_debug_eval_solo.argtypes = [C.c_void_p]
         L.frx_debug_penalty_kernel.argtypes = [C.c_void_p]
         L.frx_debug_mailbox_numa.argtypes = [C.c_void_p, C.c_void_p]
         L.frx_debug_profile_eval_cluster.argtypes = [C.c_void_p, _dp, C.c_void_p]
         L.frx_debug_profile_eval_tail.argtypes = [C.c_void_p, _dp, C.c_void_p]
+        L.frx_debug_profile_eval_forward.argtypes = [C.c_void_p, _dp, C.c_void_p]
         L.frx_multi_create.argtypes = [C.POINTER(FrxConfig), C.c_int, C.c_void_p, C.c_int, _ip, _dp, _dp, _ip, _dp, _ip, _dp, C.POINTER(C.c_void_p)]
         L.frx_multi_destroy.argtypes = [C.c_void_p]
         L.frx_multi_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
@@ -1122,6 +1124,13 @@ class Problem:
         _check(lib().frx_debug_profile_eval_tail(self.h, np.ascontiguousarray(x, dtype=np.float64), out.ctypes.data))
         return out
 
+    def profile_eval_forward(self, x):
+        """The same with the stamps of the forward map's prelude in [80..110] (frx_debug.h: frx_debug_profile_eval_forward): wave 0 of the leader [80..84] and of the last
+        member with a task [88..92], axis wave 1 of the leader [96..110]; 100 MHz ticks."""
+        out = np.zeros(112, np.int64)
+        _check(lib().frx_debug_profile_eval_forward(self.h, np.ascontiguousarray(x, dtype=np.float64), out.ctypes.data))
+        return out
+
     def set_eval_fused(self, on: bool):
         """Diagnostic: False = evaluations as three stage launches, True = the default (one launch where it applies, frx_eval_kernel.hpp)."""
         _check(lib().frx_debug_set_eval_fused(self.h, int(on)))          # (2: test mode - every wait inside the launch expires at once)
@@ -1138,6 +1147,11 @@ class Problem:
         """1 = the one-launch evaluation of this handle takes the two-trip front (frx_eval_kernel.hpp, FR: front records and the argument block's leading lines), 0 = the
         front that walks the offset tables (FRX_EVAL_FRONT=0, or a form without it)."""
         return int(lib().frx_debug_eval_front(self.h))
+
+    def eval_prelude(self) -> int:
+        """1 = the forward map of this handle's one-launch evaluation takes the shortened prelude (frx_eval_kernel.hpp, PRE), 0 = the form before (FRX_EVAL_PRELUDE=0, or
+        a form without the two-trip front and the value-major hand-off)."""
+        return int(lib().frx_debug_eval_prelude(self.h))
 
     def set_eval_solo(self, mode: int):
         """Diagnostic: 0 = never the solo form (one workgroup per candidate, one launch per evaluation, frx_solo_kernel.hpp), 1 = from the handle's batch-size

@@ -419,7 +419,10 @@ int frx_debug_profile_eval_cluster(frx_problem *p, const double *x, long long *o
 // The same evaluation with the stamps of its tail behind the first 64: out80[64..68] = wave 0 behind the barrier that follows the knot adjoint, wave 0's last gradient
 // store issued, axis wave 1's last store issued, thread 0 has the verdict, thread 0 has issued `done` (100 MHz counter, as 40..48).
 // out80[69..76]: the hand-off of the penalty partials (frx_debug.h; EvalHandoff, frx_kernels.hpp).
-int frx_debug_profile_eval_tail(frx_problem *p, const double *x, long long *out80) { return profile_eval_cluster(p, x, out80, 0, FRX_STAMP_SLOTS); }
+int frx_debug_profile_eval_tail(frx_problem *p, const double *x, long long *out80) { return profile_eval_cluster(p, x, out80, 0, 80); }
+// And with the stamps of the forward map's prelude behind those: out112[80..84] wave 0 of the leader, [88..92] wave 0 of the last member with a task, [96..110] axis wave 1 of
+// the leader (frx_debug.h; forward_knot_body<.., ET>, frx_kernels.hpp).
+int frx_debug_profile_eval_forward(frx_problem *p, const double *x, long long *out112) { static_assert(FRX_STAMP_SLOTS == 112, "out112"); return profile_eval_cluster(p, x, out112, 0, FRX_STAMP_SLOTS); }
 
 // Diagnostic (tests, tuning): drives k_lbfgs_pre alone.  `iters` successive accepted steps on random (x, g) sequences of
 // length n for B candidates; after each the device search direction is compared with a plain host two-loop recursion over
@@ -635,6 +638,7 @@ int frx_debug_set_eval_fused(frx_problem *p, int enable) {
 int frx_debug_eval_fused(const frx_problem *p) { return (p && p->eval_fused) ? p->eval_fused_G : 0; }
 int frx_debug_eval_geometry(const frx_problem *p) { return (p && p->eval_fused) ? frx::eval_cluster_class(p->geo) : 0; }
 int frx_debug_eval_front(const frx_problem *p) { return (p && p->eval_fused) ? frx::eval_cluster_front(p->geo) : 0; }
+int frx_debug_eval_prelude(const frx_problem *p) { return (p && p->eval_fused) ? frx::eval_cluster_prelude(p->geo) : 0; }
 // Diagnostic (bench, tests): the solo form of an evaluation (one workgroup per candidate, one launch).  mode: 0 = never, 1 = from the handle's threshold on (the
 // default), 2 = at every batch size.  frx_debug_eval_solo: workgroups of the kernel a CU holds when the NEXT evaluation of this handle takes the form, 0 = it does not.
 int frx_debug_set_eval_solo(frx_problem *p, int mode) {

@@ -23,9 +23,11 @@ namespace frx {
 //   FRX_EVAL_CHAIN=0    the form with the cycle stamps compiled in and every argument field loaded at its use - the one the diagnostics launch in any case
 //   FRX_EVAL_GEOM=0     the run-time instantiation also where the handle's geometry is the class EvalGeomK16
 //   FRX_EVAL_FRONT=0    the front that walks the offset tables, in every form that has the argument pointer and early durations
+//   FRX_EVAL_PRELUDE=0  the forward map's prelude as it was (the axis waves' staging loads and stores each behind a test of its own), in every form that has the two-trip
+//                       front and the value-major hand-off
 static const EvalSwitches &eval_switches() {
     static const EvalSwitches s{!env_off("FRX_EVAL_ARGPTR"), !env_off("FRX_EVAL_EARLY_T"), !env_off("FRX_EVAL_TAIL"), !env_off("FRX_EVAL_HANDOFF"), !env_off("FRX_EVAL_CHAIN"), !env_off("FRX_EVAL_GEOM"),
-                                env_off("FRX_EVAL_FRONT")};
+                                env_off("FRX_EVAL_FRONT"), env_off("FRX_EVAL_PRELUDE")};
     return s;
 }
 typedef eval_geom<EvalGeomK16> GeomK16;
@@ -38,11 +40,16 @@ int eval_cluster_front(const LaunchGeom &g) {
     if (!g.ev_G || !eval_cluster_form(eval_switches(), eval_geom_class(g), false, true, m)) return 0;
     return (m.argp && m.et && !m.old_front) ? 1 : 0;
 }
+int eval_cluster_prelude(const LaunchGeom &g) {
+    EvalClusterForm m;
+    if (!g.ev_G || !eval_cluster_form(eval_switches(), eval_geom_class(g), false, true, m)) return 0;
+    return (eval_form_has_prelude(m) && !m.old_prelude) ? 1 : 0;
+}
 
 // The instantiation of a form (frx_launch_forms.hpp): f(kernel).  THE list of the instantiations that exist: a new form of the kernel is one more line here and
 // its rung in eval_cluster_form.
-template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void, bool FR = false> struct eval_inst {
-    static constexpr EvalClusterForm form() { return {ARGP, ET, TAIL, HO, CH, !std::is_void<GEO>::value, ARGP && ET && !FR}; }
+template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void, bool FR = false, bool PRE = false> struct eval_inst {
+    static constexpr EvalClusterForm form() { return {ARGP, ET, TAIL, HO, CH, !std::is_void<GEO>::value, ARGP && ET && !FR, ARGP && ET && FR && HO && !PRE}; }
 };
 template <class F> static int with_eval_kernel(const EvalClusterForm &m, F &&f) {
 #define FRX_EVAL_FORM(...) if (m == eval_inst<__VA_ARGS__>::form()) return f(k_eval_cluster<__VA_ARGS__>);
@@ -63,6 +70,10 @@ template <class F> static int with_eval_kernel(const EvalClusterForm &m, F &&f) 
     FRX_EVAL_FORM(true, true, true, true, false, void, true)
     FRX_EVAL_FORM(true, true, false, false, false, void, true)
     FRX_EVAL_FORM(true, true, true, false, false, void, true)
+    FRX_EVAL_FORM(true, true, true, true, true, EvalGeomK16, true, true)   // the shortened prelude (PRE): every form with the two-trip front and the value-major hand-off has one
+    FRX_EVAL_FORM(true, true, true, true, false, EvalGeomK16, true, true)
+    FRX_EVAL_FORM(true, true, true, true, true, void, true, true)
+    FRX_EVAL_FORM(true, true, true, true, false, void, true, true)
 #undef FRX_EVAL_FORM
     return (int)hipErrorInvalidValue;                                 // (a form nobody instantiated)
 }

@@ -8,7 +8,8 @@
 // frx_round_kernel.hpp, take 5.2 / 3.1 / 5.2 us).  Here an evaluation is one grid of CLUSTERS, one per candidate:
 //   every workgroup   runs the forward map on the same x (forward_knot_body, MODE 5: x and the polytopes staged into its own LDS, (C, T) kept there, nothing to global memory),
 //                     so (C, T) never travel between workgroups.  Early-duration form (ET, the default; FRX_EVAL_EARLY_T=0 takes the staged form): wave 0 - the matrix
-//                     wave - loads tau into registers as its first loads and forms the durations on its own, waves 1-3 stage xi and the polytopes; one early barrier
+//                     wave - loads tau into registers as its first loads and forms the durations on its own, waves 1-3 stage xi and the polytopes (PRE below: without a
+//                     test per element; FRX_EVAL_PRELUDE=0 takes the form before); one early barrier
 //                     (counters zeroed, the status word broadcast) and the barrier in front of the coefficient collection are the only workgroup barriers of the forward map
 //   workgroup 0       LEADER: then everything of the adjoint that does not need the penalty partials, polls the partials, finishes the adjoint, writes f and the gradient
 //   workgroups 1..G-1 MEMBERS, every WAVE on its own behind the forward map: the corridor blocks of its wave-task (ppw pieces; loaded behind the forward map's own loads,
@@ -102,13 +103,16 @@ static_assert(sizeof(EvalCallArgs) + 2 * sizeof(void *) <= 64, "argument pointer
 // The early barrier of the early-duration form (forward_knot_body<.., ET>): the caller's loads behind the body's, then one barrier that zeroes the counters and makes the
 // status early-out workgroup-uniform.
 // FRN (FR below): the caller has issued wave 0's tau load itself and holds what the early-duration block otherwise reads from the index tables and the argument block.
-template <class F, bool NS = false, bool FRN = false> struct EvalEarlySync {
+// PRN (PRE below): the shortened prelude of the forward map.
+template <class F, bool NS = false, bool FRN = false, bool PRN = false> struct EvalEarlySync {
     static constexpr bool nostamps = NS;          // (CH below: no cycle stamps compiled into the forward map)
     static constexpr bool front_held = FRN;
+    static constexpr bool prelude = PRN;
     const F &f; long long *st; bool steps;
     long long *front;                             // (cluster 0's leader, stamped form) [0] wave 0's tau load issued, [1] tau in its register: slots 32, 33 of the stamp block
     // (FRN) the candidate's tau / variable / vertex-double counts, the time layer's two switches, the candidate's first vertex record, wave 0's tau
     int nT, nx, nvd, soft, c2; gptr<const double> vsrc; double tau;
+    long long *pst = nullptr;                     // (cluster 0's leader and its last member with a task, stamped form) the prelude's stamps, stretch by stretch: forward_knot_body
     __device__ __forceinline__ bool sync() const { return f(); }
 };
 // TAIL (the default; FRX_EVAL_TAIL=0 takes the other form, A/B): thread 0 of the leader stores f and `done` inside the adjoint, right behind the objective's sum
@@ -160,7 +164,13 @@ template <> struct eval_geom<void> { static constexpr bool fixed = false; static
 // for at the early barrier.  Integers only: no floating-point expression, operand or order changes, f and the gradient are the other front's bits
 // (tests/test_gpu_eval_front.py).  The read of the broadcast status word behind the early barrier is an LDS read by type here (as a generic volatile read it is a flat load
 // with a wait for every load the wave has in flight).
-template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void, bool FR = false>
+// PRE (the default wherever the form has the two-trip front and the value-major hand-off; FRX_EVAL_PRELUDE=0 takes the prelude before, A/B): the forward map's axis waves
+// stage xi and the polytopes without a test per element (forward_knot_body<.., ET>, ES::prelude: frx_kernels.hpp) - all 256 workgroups run that stretch, between the
+// early barrier and the waypoint map, so it is on every workgroup's chain.  Measured 12.26 -> 11.89 us per evaluation (profiles/NOTES.md); three further steps on the
+// same two chains - a member's wave 0 requesting its corridor block behind the durations, the Hermite operands under the wait for the last reduction step, the axis
+// waves' step gate without its sleep - measured level or slower on top of it and are not in the tree.  The stamped instantiation (CH = false) of either prelude carries
+// the stamps of both chains stretch by stretch: slots 80..110, frx_debug_profile_eval_forward.
+template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void, bool FR = false, bool PRE = false>
 __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::conditional<ARGP, const EvalClusterArgs *__restrict__, EvalClusterArgs>::type arg, EvalCallArgs call,
                                                          const EvalFront *__restrict__ front) {   // (front: a kernel argument of its own - through a restrict pointer to const the record is a scalar load)
     static_assert(!CH || (ARGP && TAIL && HO), "the production form: argument pointer, inline tail, value-major hand-off");
@@ -168,6 +178,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     constexpr bool GF = GC::fixed;
     static_assert(!GF || (ARGP && ET && TAIL && HO), "the geometry class: the default form of every other switch");
     static_assert(!FR || (ARGP && ET), "the two-trip front: the argument pointer and early durations");
+    static_assert(!PRE || (FR && HO), "the shortened prelude: the two-trip front and the value-major hand-off");
     const EvalClusterArgs &a = [&]() -> const EvalClusterArgs & { if constexpr (ARGP) return *arg; else return arg; }();
     const auto stp = [&]() -> long long * { if constexpr (CH) return nullptr; else return a.dp.stamps; };   // (CH: a constant - every stamp below folds away)
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -275,6 +286,9 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     }
     if constexpr (ET) {
         if (k == 0 && wg == 1 && wave == 0 && lane == 0 && stp()) stp()[44] = (long long)wall_clock64();
+        const int wg_last = min(nG - 1, (ntasks - 1) / 4 + 1);            // the last-dispatched member with a task
+        long long *pst = nullptr;                                   // (the prelude's stamps: slots 80.. of cluster 0's leader and of its last member with a task)
+        if constexpr (!CH) { if (stp() && k == 0 && (wg == 0 || wg == wg_last)) pst = stp() + 80; }
         const auto early = [&]() -> bool {
             if (has_task) {
                 if constexpr (GF) hv[0] = h2[lane < nh2 ? lane : nh2 - 1];          // (nh2 <= 54: the one trip there is)
@@ -285,7 +299,9 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
             }
             unsigned *w = (unsigned *)(ev + 24 * 64);               // forward_knot_body's progress words (its rowbuf is ev)
             if (t == 0) { w[0] = 0u; w[2] = 0u; w[3] = 0u; w[4] = 0u; w[5] = st0; *verdict = 0u; }
+            if (pst && t == 0) pst[wg == 0 ? 0 : 8] = (long long)wall_clock64();   // (wave 0 at the early barrier)
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (pst && t == 0) pst[wg == 0 ? 1 : 9] = (long long)wall_clock64();   // (and out of it)
             if constexpr (FR) {
                 bad = ((lds_vuptr)w)[5] != 0u;                       // (an LDS read by type)
                 if (!bad && wg == 0 && t == 0) {                     // (the tag is formed where it is used: here by the leader's thread 0 alone, by everybody else behind the forward map)
@@ -299,7 +315,6 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
             if (!bad && wg == 0 && t == 0) __hip_atomic_store(flag, (tag << 4) | (my_xcc ? my_xcc : 15u), FRX_RLX_AGENT);
             return bad;
         };
-        const int wg_last = min(nG - 1, (ntasks - 1) / 4 + 1);            // the last-dispatched member with a task
         long long *est = nullptr;
         if (stp() && k == 0 && (wg == 0 || wg == wg_last)) est = stp() + (wg == 0 ? 50 : 60);
         long long *const fst = (stp() && k == 0 && wg == 0) ? stp() + 32 : nullptr;
@@ -324,13 +339,13 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
             }
             if (wave == 0 && fst) { asm volatile("" :: "v"(tau)); const long long f_in = (long long)wall_clock64(); if (lane == 0) { fst[0] = f_iss; fst[1] = f_in; } }
             const KnotPre kpre{fr.p0, fr.N, fr.c0, fr.cN, fr.x0, fr.cv0, r_pc, r_piv, r_wnv, r_wvb, r_wxb, {r_bs[0], r_bs[1], r_bs[2], r_bs[3], r_bs[4], r_bs[5]}};
-            const EvalEarlySync<decltype(early), CH, true> es{early, est, wg == 0, nullptr, fr.nT, fr.nx, fr.nvd, ld.soft, ld.c2, l_vrec + 3 * (size_t)fr.cv0, tau};
+            const EvalEarlySync<decltype(early), CH, true, PRE> es{early, est, wg == 0, nullptr, fr.nT, fr.nx, fr.nvd, ld.soft, ld.c2, l_vrec + 3 * (size_t)fr.cv0, tau, pst};
             forward_knot_body<false, 64, 5, 0, true>(a.dp, call.x, a.T, a.C, ld.maxCN, ld.maxXb, ld.maxVb, 64, nullptr, nsteps, c, ev, ctl, true, &ro, &kpre, nullptr, &es);
             asm volatile("" : "+v"(tag_v));
             tag = tag_v + 1u;
             if (tag >= (1u << 28)) tag = 1u;
         } else {
-        const EvalEarlySync<decltype(early), CH> es{early, est, wg == 0, fst, 0, 0, 0, 0, 0, nullptr, 0.0};
+        const EvalEarlySync<decltype(early), CH> es{early, est, wg == 0, fst, 0, 0, 0, 0, 0, nullptr, 0.0, pst};
         forward_knot_body<false, 64, 5, 0, true>(a.dp, call.x, a.T, a.C, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, nsteps, c, ev, ctl, true, &ro, nullptr, nullptr, &es);
         }
         if (bad) {                                                   // an earlier launch's wait expired (see above): uniform over the workgroup

@@ -71,7 +71,7 @@ struct NumaScope {
 };
 } // namespace frx
 
-constexpr int FRX_STAMP_SLOTS = 80;                         // words of frx_problem::d_stamps
+constexpr int FRX_STAMP_SLOTS = 112;                        // words of frx_problem::d_stamps
 
 struct frx_problem {
     frx_config cfg;
@@ -87,7 +87,7 @@ struct frx_problem {
     DevBuf<double> d_head, d_tail, d_hblk, d_vrec;
     // device work space
     DevBuf<double> d_x, d_f, d_g, d_T, d_C, d_band, d_out20;
-    DevBuf<long long> d_stamps;                             // FRX_STAMP_SLOTS words (0..63 as ever; 64.. the tail of the one-launch evaluation, frx_debug_profile_eval_tail)
+    DevBuf<long long> d_stamps;                             // FRX_STAMP_SLOTS words (0..63 as ever; 64..79 the tail of the one-launch evaluation, frx_debug_profile_eval_tail; 80..111 its prelude, frx_debug_profile_eval_forward)
     DevBuf<double> d_pcrw;
     DevBuf<double> d_wq;                                    // [P][4]: per waypoint {|xi|^2, sum_a V_a xi_a^2}, forward map -> adjoint of the same evaluation
     // pinned staging

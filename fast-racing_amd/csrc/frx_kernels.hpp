@@ -139,6 +139,9 @@ template <> struct es_nostamps<void> { static constexpr bool value = false; };
 // (ES::front_held - the caller holds the candidate's counts, the time layer's switches, the vertex base and wave 0's tau, already requested: the early-duration block reads no table)
 template <class ES> struct es_front { static constexpr bool value = ES::front_held; };
 template <> struct es_front<void> { static constexpr bool value = false; };
+// (ES::prelude - the shortened prelude of the early-duration form, forward_knot_body<.., ET>: see PRE there)
+template <class ES> struct es_prelude { static constexpr bool value = ES::prelude; };
+template <> struct es_prelude<void> { static constexpr bool value = false; };
 // Pinning a wave-uniform value in scalar registers: `asm volatile("" : "+s"(v), ...)` defines it anew, so the compiler may not re-load it at its uses, and ONE statement for a
 // group of values lets their loads go out together in front of it.  as_uniform: a uniform value that came through a vector load moves to a scalar register first (a no-op otherwise).
 // gptr: a pointer goes through such a statement as a pointer to GLOBAL memory by type - as a plain one it would come out with its address space unknown, and its stores as flat stores.
@@ -1262,7 +1265,7 @@ __device__ __forceinline__ void lds_wait_ge(lds_vuptr w, unsigned want) {
 // NOBAR (the early-duration form of forward_knot_body): no s_barrier at all - the axis waves take the multipliers by the step counter alone.
 template <bool NOBAR = false>
 __device__ __forceinline__ void pcr_matrix_wave64(double *rowbuf, int kk, int N, double hL, double hR, double *pw, int pws, double *save, size_t sstride,
-                                                  size_t gk0, int nsteps, lds_vuptr progress, long long *est = nullptr) {
+                                                  size_t gk0, int nsteps, lds_vuptr progress, long long *est = nullptr, long long *pst0 = nullptr) {
     const int nrow = 64;
     const bool act = kk >= 1 && kk <= N - 1;
     int nst = 0;
@@ -1286,6 +1289,9 @@ __device__ __forceinline__ void pcr_matrix_wave64(double *rowbuf, int kk, int N,
     } else if (act) {
         MR2(0, 0, kk) = make_double2(I[0], I[1]); MR2(0, 1, kk) = make_double2(I[2], I[3]);
         MR2(0, 2, kk) = make_double2(L[0], L[1]); MR2(0, 3, kk) = make_double2(L[2], L[3]);
+    }
+    if constexpr (NOBAR) {                                          // (pst0, optional, the stamped early-duration form: the rows are built and the first inverse is in its registers)
+        if (pst0) { asm volatile("" :: "v"(I[0]), "v"(I[1]), "v"(I[2]), "v"(I[3])); const long long c = (long long)wall_clock64(); if (kk == 0) *pst0 = c; }
     }
     double2 *sp = save ? (double2 *)(save + (gk0 + kk) * sstride) : nullptr;     // null: the multipliers stay in LDS (resident caller)
     // (Round 5 tried the neighbours' (D^-1, L) straight out of their lanes' registers through the LDS crossbar - 32 ds_bpermute per step instead of four
@@ -1359,6 +1365,12 @@ __device__ __forceinline__ void pcr_matrix_wave64(double *rowbuf, int kk, int N,
 // each other at LDS arrival counters and read Tf once wave 0 has flagged it.  The caller zeroes nothing itself: `es->sync()` is called once every wave has issued its loads,
 // zeroes the counters behind the caller's own loads and ends in the workgroup's one early barrier; it returns true when the workgroup is to do nothing (uniformly).
 // es->st (optional): 100 MHz stamps - [0] durations formed, [1] staged, [2] waypoint map done, es->steps: [3 + s] matrix step s done, [9] matrix wave done; otherwise [3] matrix wave done.
+// PRE (ES::prelude; behind the two-trip front only; FRX_EVAL_PRELUDE=0 takes the form before, A/B): the axis waves' first staging trip without a test per element.  The
+// twenty loads are clamped to the last element already; here they stand in one basic block (an empty array reads a word of the argument block instead of being skipped),
+// and behind the early barrier every value is stored at the clamped index it was loaded from - the lanes beyond the end write the last element's value over itself.
+// Before, each load sat behind a test of its count and each store inside compare / save-exec / branch / restore with a wait for ALL loads in front of it: 160
+// instructions for the twenty stores where 98 do (profiles/eval_prelude_isa_report.txt).  stage_to_lds's remainder loops take what the first trip does not hold, as before.
+// Integers and the order of memory operations only: (C, T) are the other form's bits (tests/test_gpu_eval_prelude.py).
 template <bool SH, int NR = 0, int MODE = 0, int RB = 0, bool ET = false, class ES = void>
 __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const double *__restrict__ x, double *__restrict__ Tout, double *__restrict__ Cout,
                                int maxCN, int maxXb, int maxVb, int nrow_rt, double *__restrict__ pcrw, int nsteps, int b, double *sm, double *ct_lds = nullptr, bool wt = true, const ResidentOps *ro = nullptr,
@@ -1414,6 +1426,18 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
     long long *est = nullptr;
     bool est_steps = false;
     if constexpr (ET) { est = es->st; est_steps = es->steps; }
+    // es->pst (optional, the stamped instantiation): 100 MHz stamps of the prelude, stretch by stretch.  Wave 0 of the leader [0..4] and of the last member with a task [8..12]:
+    // at the early barrier, out of it (both the caller's, in es->sync()), tau in its register, Tc written, rows built and first inverse done.  Axis wave 1 of the leader
+    // [16..30]: last staging load issued, out of the barrier, loads landed, staging stores done, vertex trips done, division done, right-hand side built, steps 0..5 done,
+    // final multipliers seen, coefficients written.
+    long long *pw0 = nullptr, *pax = nullptr;
+    if constexpr (ET) {
+        if constexpr (!es_nostamps<ES>::value) {
+            if (es->pst) { if (k < 64) pw0 = es->pst + (es->steps ? 0 : 8); else if (k == 64 && es->steps) pax = es->pst + 16; }
+        }
+    }
+    constexpr bool PRE = es_prelude<ES>::value;
+    static_assert(!PRE || (ET && es_front<ES>::value), "the shortened prelude: the early-duration form behind the two-trip front");
     if constexpr (ET) {
         static_assert(NR == 64 && (MODE & 1), "early durations: the wave-specialised <= 64-piece path of a caller that stages");
         const int wave = __builtin_amdgcn_readfirstlane(k >> 6), kk = k & 63;
@@ -1433,17 +1457,32 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
             if (fst) { asm volatile("" :: "v"(x + x0 + kk), "v"(nT)); f_iss = (long long)wall_clock64(); }
             if constexpr (!FH) { if (kk < nT) tau = x[x0 + kk]; }   // (FH: requested by the caller, in front of its other loads, and read from es below - a copy here would be written on the axis waves' path too, behind a wait for all of their loads)
             if (fst) { asm volatile("" :: "v"(tau)); const long long f_in = (long long)wall_clock64(); if (kk == 0) { fst[0] = f_iss; fst[1] = f_in; } }
+        } else if constexpr (PRE) {
+            // (PRE) the same twenty loads in ONE basic block: a branch around a group that an empty array skips leaves the compiler's count of the loads in flight
+            // ambiguous behind it, and every store below would wait for all of them.  An empty array (nx and nvd are uniform) reads a word of the argument block
+            // instead - a value nobody stores
+            const double *const none = &dp.sumT;
+            const double *const xb = nx > 0 ? x + x0 : none, *const vb = nvd > 0 ? vsrc : none;
+            const int xl = nx > 0 ? nx - 1 : 0, vl = nvd > 0 ? nvd - 1 : 0;
+#pragma unroll
+            for (int u = 0; u < UX; u++) sx[u] = xb[min(nT + t2 + u * NA, xl)];
+#pragma unroll
+            for (int u = 0; u < UV; u++) sv[u] = vb[min(t2 + u * NA, vl)];
+            if (pax) pax[0] = (long long)wall_clock64();
         } else {
 #pragma unroll
             for (int u = 0; u < UX; u++) { const int i = nT + t2 + u * NA; sx[u] = nx > 0 ? x[x0 + (i < nx ? i : nx - 1)] : 0.0; }
 #pragma unroll
             for (int u = 0; u < UV; u++) { const int i = t2 + u * NA; sv[u] = nvd > 0 ? vsrc[i < nvd ? i : nvd - 1] : 0.0; }
+            if (pax) pax[0] = (long long)wall_clock64();            // (every staging load of axis wave 1 is issued)
         }
         if (es->sync()) return;
+        if (pax) pax[1] = (long long)wall_clock64();                // (out of the early barrier; wave 0's two stamps around it: the caller's, in es->sync())
         if (wave == 0) {
             // forwardT (CPU.hpp:626-676) and splitToFineT (CPU.hpp:930-944) inside the wave, the same expressions in the same order as below; LDS operations of one wave
             // complete in order, so lane 0 sees the other lanes' writes without a barrier
             if constexpr (FH) tau = es->tau;
+            if (pw0) { asm volatile("" :: "v"(tau)); const long long c = (long long)wall_clock64(); if (kk == 0) pw0[2] = c; }   // (tau is in its register)
             if (kk < nT) xs[kk] = tau;                                // (the adjoint reads tau from ro->xs)
             if (t_soft()) {
                 if (kk < cN) Tc[kk] = tau_to_T(tau, t_c2() != 0);
@@ -1460,6 +1499,7 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
                 Tc[Ms1] = 1.0 - sum;
                 for (int i = 0; i <= Ms1; i++) Tc[i] *= dp.sumT;
             }
+            if (pw0 && kk == 0) pw0[3] = (long long)wall_clock64();  // (Tc written)
             if (kk < N) {
                 hMine = Tc[r_pc - c0] / r_piv;
                 Tf[kk] = hMine;
@@ -1468,13 +1508,28 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (kk == 0) { progress[4] = 1u; if (est) est[0] = (long long)wall_clock64(); }
         } else {
+            if (pax) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); pax[2] = (long long)wall_clock64(); }   // (the staging loads have landed)
+            if constexpr (PRE) {
+                // (PRE) every value goes to the clamped index it was loaded from - the lanes beyond the end write the last element's value over itself - so a store is an
+                // address and a write, nothing around it, and the waits in front of the stores are counted ones (the corridor block of a member stays in flight)
+                if (nx > 0) {
+#pragma unroll
+                    for (int u = 0; u < UX; u++) xs[min(nT + t2 + u * NA, nx - 1)] = sx[u];
+                }
+                if (nvd > 0) {
+#pragma unroll
+                    for (int u = 0; u < UV; u++) vs[min(t2 + u * NA, nvd - 1)] = sv[u];
+                }
+            } else {
 #pragma unroll
             for (int u = 0; u < UX; u++) { const int i = nT + t2 + u * NA; if (i < nx) xs[i] = sx[u]; }
 #pragma unroll
             for (int u = 0; u < UV; u++) { const int i = t2 + u * NA; if (i < nvd) vs[i] = sv[u]; }
+            }
             stage_to_lds<4>(xs, x + x0, nx, nT + t2 + UX * NA, NA);   // (longer candidates: the rest)
             stage_to_lds<8>(vs, vsrc, nvd, t2 + UV * NA, NA);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (pax) pax[3] = (long long)wall_clock64();            // (the staging stores are done)
             if (kk == 0) __hip_atomic_fetch_add(arrive + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             lds_wait_ge(progress + 2, 3u);
             if (est && k == 64) est[1] = (long long)wall_clock64();
@@ -1533,6 +1588,10 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
             // durations left and right of knot kk: the left one comes from the neighbouring lane (lane = piece = knot)
             const double hLs = lane_up1(hMine);
             const bool act0 = kk >= 1 && kk <= N - 1;
+            if constexpr (ET)
+            pcr_matrix_wave64<ET>(rowbuf, kk, N, act0 ? hLs : 1.0, act0 ? hMine : 1.0, pwf, pws, ro ? nullptr : pcrw, (size_t)(nsteps * 8 + 4), (size_t)p0, nsteps, progress,
+                                  (est && est_steps) ? est + 3 : nullptr, pw0 ? pw0 + 4 : nullptr);
+            else
             pcr_matrix_wave64<ET>(rowbuf, kk, N, act0 ? hLs : 1.0, act0 ? hMine : 1.0, pwf, pws, ro ? nullptr : pcrw, (size_t)(nsteps * 8 + 4), (size_t)p0, nsteps, progress,
                                   (est && est_steps) ? est + 3 : nullptr);
             if (est && !est_steps && kk == 0) est[3] = (long long)wall_clock64();
@@ -1560,11 +1619,13 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
                             if (a0 + 2 * j < nv1) { const double x2 = xv[j] * xv[j]; nrm += x2; q0 += v0[j] * x2; q1 += v1[j] * x2; q2 += v2[j] * x2; }
                     }
                 }
+                if constexpr (ET) { if (pax) { asm volatile("" :: "v"(nrm), "v"(q0), "v"(q1), "v"(q2)); pax[4] = (long long)wall_clock64(); } }   // (the vertex trips are done)
                 nrm += dpp_mov<0xB1>(nrm); q0 += dpp_mov<0xB1>(q0); q1 += dpp_mov<0xB1>(q1); q2 += dpp_mov<0xB1>(q2);   // pair sums
                 if (wact && sub == 0) {
                     if (ro && ro->wq) { double *wq = ro->wq + 4 * w; wq[0] = nrm; wq[1] = q0; wq[2] = q1; wq[3] = q2; }
                     else if (dp.wq_glob) { double2 *wq = (double2 *)(dp.wq_glob + 4 * (size_t)(p0 - b + w)); wq[0] = make_double2(nrm, q0); wq[1] = make_double2(q1, q2); }
                     const double sc = 2.0 / (1.0 + nrm), sc2 = sc * sc;
+                    if constexpr (ET) { if (pax) { asm volatile("" :: "v"(sc2)); pax[5] = (long long)wall_clock64(); } }   // (the division is done)
                     KN(KP, 0, w + 1) = sc2 * q0 + V[0]; KN(KP, 1, w + 1) = sc2 * q1 + V[1]; KN(KP, 2, w + 1) = sc2 * q2 + V[2];
                 }
             }
@@ -1611,6 +1672,7 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
                 const bool all_here = __builtin_amdgcn_ballot_w64(vq != go->gate_val) == 0ull;
                 if (kk == 0) progress[1] = all_here ? 1u : 0u;
             }
+            if constexpr (ET) { if (pax) { asm volatile("" :: "v"(r0), "v"(r1)); pax[6] = (long long)wall_clock64(); } }   // (the right-hand side is built)
             int nst = 0;
             for (int s = 1; s < N - 1; s <<= 1) nst++;
             for (int st = 0; st < nst; st++) {                             // pcr_rhs_step behind the matrix wave, neighbours by lane shifts
@@ -1625,6 +1687,7 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
                 const double n0 = r0 - (ab[0] * l0 + ab[1] * l1) - (ab[4] * h0 + ab[5] * h1);
                 const double n1 = r1 - (ab[2] * l0 + ab[3] * l1) - (ab[6] * h0 + ab[7] * h1);
                 r0 = n0; r1 = n1;
+                if constexpr (ET) { if (pax && st < 6) { asm volatile("" :: "v"(r0), "v"(r1)); pax[7 + st] = (long long)wall_clock64(); } }   // (step st is done)
             }
             FWD_STAMP_AX(11);
             // everything of the Hermite stage that does not need the solution is computed while the matrix wave finishes: durations and their
@@ -1635,6 +1698,7 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
             const double c3p = 10.0 * dl * ih3, c4p = -15.0 * dl * ih4, c5p = 6.0 * dl * ih5;
             const double vHead = KN(KV, ax, 0), aHead = KN(KA, ax, 0), vTail = KN(KV, ax, N), aTail = KN(KA, ax, N);
             lds_wait_ge(progress, (unsigned)(nst + 1));
+            if constexpr (ET) { if (pax) pax[13] = (long long)wall_clock64(); }   // (the final multipliers are seen)
             double vK, aK;                                                 // (v, a) of knot kk on this axis
             {
                 const double *Di = pwf + kc * pws + nsteps * 8;
@@ -1654,6 +1718,7 @@ __device__ __forceinline__ void forward_knot_body(const DevProblem &dp, const do
 #pragma unroll
                 for (int q = 0; q < 6; q++) cstage[kk * 19 + q * 3 + ax] = cq[q];
             }
+            if constexpr (ET) { if (pax) pax[14] = (long long)wall_clock64(); }   // (the coefficients are written)
             FWD_STAMP_AX(12);
         }
         // C leaves the workgroup as ONE coalesced sweep of 16-byte stores by all four waves.  Stored straight from the axis lanes it was 1152

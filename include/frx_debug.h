@@ -65,6 +65,9 @@ int frx_debug_eval_geometry(const frx_problem *p);
  * operand load of the front in one group), 0 = the front that walks the offset tables (FRX_EVAL_FRONT=0, a form without the argument pointer or early durations, or no
  * one-launch form at all).  The two give the same bits. */
 int frx_debug_eval_front(const frx_problem *p);
+/* Which prelude the forward map of the handle's one-launch form takes: 1 = the shortened one (the axis waves store what they staged without predication, each
+ * value at the clamped index it was loaded from, and load it in one basic block), 0 = the form before (FRX_EVAL_PRELUDE=0, a form without the two-trip front or the value-major hand-off, or no one-launch form at all).  The two give the same bits. */
+int frx_debug_eval_prelude(const frx_problem *p);
 /* The solo form of an evaluation (one workgroup per candidate runs forward map, penalty integral and adjoint in ONE launch; batches larger than the clusters of the
  * one-launch form reach; the per-stage rounds of frx_optimize take it too).  mode 0 = never, 1 = from the handle's batch-size threshold on (default; FRX_EVAL_SOLO_MIN_B),
  * 2 = at every batch size, also where the cluster form would apply.  Results are bit-identical to the three stage launches (replaces the same objectiveFunc,
@@ -84,6 +87,12 @@ int frx_debug_profile_eval_cluster(frx_problem *p, const double *x, long long *o
  * the hand-off of the penalty partials: [69] wave 0 of the first member has the gate word's value, [70] / [71] wave 0 of the leader enters / has left its poll for the
  * partials, [72] / [73] the same for axis wave 1, [74] axis wave 1's Hermite adjoint is done, [75] / [76] NOT times: the spins of lane 0 of wave 0 / of axis wave 1. */
 int frx_debug_profile_eval_tail(frx_problem *p, const double *x, long long *out80);
+/* The same with the stamps of the forward map's prelude behind those (100 MHz counter).  Wave 0 of the leader, out112[80..84]: at the early barrier, out of it, tau in
+ * its register, the coarse durations written, the knot rows built and the first inverse done (the durations formed and the matrix steps: [50], [53..58]); wave 0 of the
+ * last member with a task, [88..92]: the same five ([60] its durations formed).  Axis wave 1 of the leader, [96..110]: last staging load issued, out of the early barrier,
+ * staging loads landed, staging stores done ([51]: every axis wave has staged), vertex trips done, division done ([52]: waypoint map done and durations seen),
+ * right-hand side built, reduction steps 0..5 done, final multipliers seen, coefficients written. */
+int frx_debug_profile_eval_forward(frx_problem *p, const double *x, long long *out112);
 
 /* Diagnostic: runs one evaluation at x and returns shader-clock stamps taken at the phase boundaries of candidate 0's
  * k_forward_knot (out32[0..6]) and k_backward_knot (out32[16..24]). */

@@ -7,7 +7,8 @@ AB_ROOT=<dir> in a variant loads the package (frx_import.py, fast-racing_amd/ wi
 Known switches of the one-launch evaluation, each read once per process ("0" = the form before): FRX_EVAL_ARGPTR, FRX_EVAL_EARLY_T, FRX_EVAL_TAIL, FRX_EVAL_HANDOFF
 (value-major granules of the penalty partials, 16-byte polls, multipliers ahead of the poll), FRX_EVAL_CHAIN (the production instantiation: no cycle stamps compiled in,
 the argument block's scalars loaded once and pinned in scalar registers), FRX_EVAL_GEOM (the compile-time geometry class of the headline handle: 17 samples per piece, 3 pieces
-per wave-task, Kmax = 8, six reduction steps), FRX_EVAL_FRONT (two trips behind the kernel's entry: front records and the argument block's leading lines); FRX_EVAL_FUSED_WT=1 forces write-through payload."""
+per wave-task, Kmax = 8, six reduction steps), FRX_EVAL_FRONT (two trips behind the kernel's entry: front records and the argument block's leading lines), FRX_EVAL_PRELUDE (the forward map's axis waves stage xi and the
+polytopes without a test per element: loads in one basic block, stores at the clamped index); FRX_EVAL_FUSED_WT=1 forces write-through payload."""
 import hashlib, json, os, subprocess, sys
 child = r'''
 import os, sys, json, hashlib

@@ -1,0 +1,59 @@
+// TEST INFRASTRUCTURE: a stand-alone host program around fast-racing_amd/csrc/frx_launch_forms.hpp, meant for a sanitizer build (tests/test_eval_prelude_cpu.py compiles it with
+// the address and undefined-behaviour sanitizers and runs it).  It enumerates the decision of the one-launch evaluation's prelude switch (FRX_EVAL_PRELUDE, EvalSwitches::old_prelude)
+// over all eight switches and both inputs of eval_cluster_form: the rule written out once more, what the switch may NOT move, and the list of forms whose LDS limit is raised.
+// Exit status 0 and no sanitizer report is the result.
+#include <cstdio>
+#include <memory>
+
+#include "../../fast-racing_amd/csrc/frx_launch_forms.hpp"
+
+using namespace frx;
+
+int main() {
+    int bad = 0, n = 0, with_prelude = 0, taken = 0;
+    for (int sw = 0; sw < 256; sw++) {
+        const bool A = sw & 1, E = sw & 2, T = sw & 4, H = sw & 8, C = sw & 16, G = sw & 32, OF = sw & 64, OP = sw & 128;
+        EvalSwitches s{A, E, T, H, C, G};
+        s.old_front = OF; s.old_prelude = OP;
+        EvalSwitches s_def = s;
+        s_def.old_prelude = false;
+        std::unique_ptr<EvalClusterForm[]> raised(new EvalClusterForm[4]);        // on the heap at its exact size: a form written past its end is reported
+        const int nr = eval_cluster_raised_forms(s, raised.get());
+        bad += nr < 1 || nr > 4;
+        for (int k = 0; k < 4; k++) {
+            const bool geom_class = k & 1, stamped = k & 2;
+            EvalClusterForm f, d;
+            const bool ok = eval_cluster_form(s, geom_class, stamped, true, f);
+            bad += !ok || !eval_cluster_form(s_def, geom_class, stamped, true, d);
+            // the rule, written out: a prelude to take or to leave exists behind the two-trip front (argument pointer, early durations, FRX_EVAL_FRONT not 0) with the
+            // value-major hand-off (which needs the inline tail); there the switch shows, inverted, and nowhere else
+            const bool has = A && E && !OF && (H && A && T);
+            bad += eval_form_has_prelude(f) != has;
+            bad += f.old_prelude != (OP && has);
+            bad += d.old_prelude;                                                  // unset: the shortened prelude wherever there is one
+            // the switch moves nothing else
+            EvalClusterForm g = f;
+            g.old_prelude = d.old_prelude;
+            bad += !(g == d);
+            // and two forms that differ in it alone are two forms
+            bad += (f == d) != (f.old_prelude == d.old_prelude);
+            // the form a launch takes has had its limit raised
+            int at = -1;
+            for (int i = 0; i < nr; i++) if (raised[i] == f) at = i;
+            bad += at < 0;
+            // without a device block only the by-value form launches, and it never has the switch
+            EvalClusterForm f0;
+            bad += eval_cluster_form(s, geom_class, stamped, false, f0) != !f.argp || !(f0 == f);
+            bad += !f.argp && f.old_prelude;
+            with_prelude += has;
+            taken += has && !f.old_prelude;
+            n++;
+        }
+    }
+    // a form written with the six members that were there is the default one in both inverted flags
+    const EvalClusterForm six{true, true, true, true, true, true};
+    bad += six.old_front || six.old_prelude || !eval_form_has_prelude(six);
+    n++;
+    std::printf("%d decisions enumerated, %d with a prelude to choose, %d of them take the shortened one, %d disagreements\n", n, with_prelude, taken, bad);
+    return bad ? 1 : 0;
+}
