@@ -81,7 +81,7 @@ ABI_SYMBOLS = [
 DEBUG_SYMBOLS = [
     "frx_debug_trace", "frx_resident_profile", "frx_debug_direction_log", "frx_debug_direction_log_read", "frx_debug_set_resident_retry",
     "frx_debug_resident_counts", "frx_debug_resident_clusters", "frx_debug_resident_predictions", "frx_eval_stage_times", "frx_profile_phases", "frx_dv_selftest", "frx_jps_tables", "frx_debug_host_cpu_share", "frx_debug_taken_over", "frx_debug_compact_from_history",
-    "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_eval_geometry", "frx_debug_eval_front", "frx_debug_eval_prelude", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_profile_eval_forward", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
+    "frx_debug_set_eval_fused", "frx_debug_eval_fused", "frx_debug_eval_geometry", "frx_debug_eval_front", "frx_debug_eval_prelude", "frx_debug_eval_adjoint", "frx_debug_set_eval_solo", "frx_debug_eval_solo", "frx_debug_penalty_kernel", "frx_debug_mailbox_numa", "frx_eval_launch_time", "frx_debug_profile_eval_cluster", "frx_debug_profile_eval_tail", "frx_debug_profile_eval_forward", "frx_debug_set_takeover_at", "frx_debug_shader_clock",
     "frx_debug_set_clear_chunk", "frx_debug_map_blocked_device", "frx_debug_dv_layout", "frx_debug_dv_round", "frx_debug_fold_rows", "frx_debug_lane_exchange",
     "frx_debug_set_clear_exact", "frx_debug_clear_exact_counts",
 ]
@@ -163,6 +163,7 @@ def lib():
         L.frx_debug_eval_geometry.argtypes = [C.c_void_p]
         L.frx_debug_eval_front.argtypes = [C.c_void_p]
         L.frx_debug_eval_prelude.argtypes = [C.c_void_p]
+        L.frx_debug_eval_adjoint.argtypes = [C.c_void_p]
         L.frx_debug_set_eval_solo.argtypes = [C.c_void_p, C.c_int]
         L.frx_debug_eval_solo.argtypes = [C.c_void_p]
         L.frx_debug_penalty_kernel.argtypes = [C.c_void_p]
@@ -1152,6 +1153,11 @@ class Problem:
         """1 = the forward map of this handle's one-launch evaluation takes the shortened prelude (frx_eval_kernel.hpp, PRE), 0 = the form before (FRX_EVAL_PRELUDE=0, or
         a form without the two-trip front and the value-major hand-off)."""
         return int(lib().frx_debug_eval_prelude(self.h))
+
+    def eval_adjoint(self) -> int:
+        """1 = the leader of this handle's one-launch evaluation runs the adjoint with its operands in front of the poll (frx_eval_kernel.hpp, ADJ), 0 = the form before
+        (FRX_EVAL_ADJOINT=0, or a form without the shortened prelude)."""
+        return int(lib().frx_debug_eval_adjoint(self.h))
 
     def set_eval_solo(self, mode: int):
         """Diagnostic: 0 = never the solo form (one workgroup per candidate, one launch per evaluation, frx_solo_kernel.hpp), 1 = from the handle's batch-size

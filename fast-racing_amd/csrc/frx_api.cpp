@@ -639,6 +639,7 @@ int frx_debug_eval_fused(const frx_problem *p) { return (p && p->eval_fused) ? p
 int frx_debug_eval_geometry(const frx_problem *p) { return (p && p->eval_fused) ? frx::eval_cluster_class(p->geo) : 0; }
 int frx_debug_eval_front(const frx_problem *p) { return (p && p->eval_fused) ? frx::eval_cluster_front(p->geo) : 0; }
 int frx_debug_eval_prelude(const frx_problem *p) { return (p && p->eval_fused) ? frx::eval_cluster_prelude(p->geo) : 0; }
+int frx_debug_eval_adjoint(const frx_problem *p) { return (p && p->eval_fused) ? frx::eval_cluster_adjoint(p->geo) : 0; }
 // Diagnostic (bench, tests): the solo form of an evaluation (one workgroup per candidate, one launch).  mode: 0 = never, 1 = from the handle's threshold on (the
 // default), 2 = at every batch size.  frx_debug_eval_solo: workgroups of the kernel a CU holds when the NEXT evaluation of this handle takes the form, 0 = it does not.
 int frx_debug_set_eval_solo(frx_problem *p, int mode) {

@@ -94,6 +94,7 @@ size_t eval_cluster_args_bytes();
 // front_dev: the handle's B front records in device memory (EvalFront, frx_eval_front.hpp: written by eval_front_fill from the host copies of the offset tables and uploaded
 // once at create); both argument blocks of a handle carry the pointer.
 void eval_cluster_args(const DevProblem &dp, const LaunchGeom &g, double *T, double *C, unsigned long long *ll, unsigned *words, const void *front_dev, void *out);
+int eval_cluster_adjoint(const LaunchGeom &g);                    // 1: and the leader's adjoint with its operands in front of the poll (k_eval_cluster<.., ADJ>), 0: the form before (FRX_EVAL_ADJOINT=0, or a form without it)
 int eval_cluster_prelude(const LaunchGeom &g);                    // 1: and the shortened prelude of its forward map (k_eval_cluster<.., PRE>), 0: the form before (FRX_EVAL_PRELUDE=0, or a form without it)
 int eval_cluster_front(const LaunchGeom &g);                      // 1: a handle of this geometry launches the two-trip front (k_eval_cluster<.., FR>), 0: the front that walks the tables (FRX_EVAL_FRONT=0, or a form without it)
 int launch_eval_cluster(const LaunchGeom &g, int B, const void *args_host, const void *args_dev, const double *x, double *f, double *grad,

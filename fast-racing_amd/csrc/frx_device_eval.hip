@@ -25,9 +25,11 @@ namespace frx {
 //   FRX_EVAL_FRONT=0    the front that walks the offset tables, in every form that has the argument pointer and early durations
 //   FRX_EVAL_PRELUDE=0  the forward map's prelude as it was (the axis waves' staging loads and stores each behind a test of its own), in every form that has the two-trip
 //                       front and the value-major hand-off
+//   FRX_EVAL_ADJOINT=0  the leader's adjoint as it was (its top through the offset tables, the waypoint layer's operands requested behind the solve), in every form that
+//                       has the shortened prelude on
 static const EvalSwitches &eval_switches() {
     static const EvalSwitches s{!env_off("FRX_EVAL_ARGPTR"), !env_off("FRX_EVAL_EARLY_T"), !env_off("FRX_EVAL_TAIL"), !env_off("FRX_EVAL_HANDOFF"), !env_off("FRX_EVAL_CHAIN"), !env_off("FRX_EVAL_GEOM"),
-                                env_off("FRX_EVAL_FRONT"), env_off("FRX_EVAL_PRELUDE")};
+                                env_off("FRX_EVAL_FRONT"), env_off("FRX_EVAL_PRELUDE"), env_off("FRX_EVAL_ADJOINT")};
     return s;
 }
 typedef eval_geom<EvalGeomK16> GeomK16;
@@ -48,8 +50,8 @@ int eval_cluster_prelude(const LaunchGeom &g) {
 
 // The instantiation of a form (frx_launch_forms.hpp): f(kernel).  THE list of the instantiations that exist: a new form of the kernel is one more line here and
 // its rung in eval_cluster_form.
-template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void, bool FR = false, bool PRE = false> struct eval_inst {
-    static constexpr EvalClusterForm form() { return {ARGP, ET, TAIL, HO, CH, !std::is_void<GEO>::value, ARGP && ET && !FR, ARGP && ET && FR && HO && !PRE}; }
+template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void, bool FR = false, bool PRE = false, bool ADJ = false> struct eval_inst {
+    static constexpr EvalClusterForm form() { return {ARGP, ET, TAIL, HO, CH, !std::is_void<GEO>::value, ARGP && ET && !FR, ARGP && ET && FR && HO && !PRE, ARGP && ET && FR && HO && PRE && !ADJ}; }
 };
 template <class F> static int with_eval_kernel(const EvalClusterForm &m, F &&f) {
 #define FRX_EVAL_FORM(...) if (m == eval_inst<__VA_ARGS__>::form()) return f(k_eval_cluster<__VA_ARGS__>);
@@ -74,12 +76,21 @@ template <class F> static int with_eval_kernel(const EvalClusterForm &m, F &&f) 
     FRX_EVAL_FORM(true, true, true, true, false, EvalGeomK16, true, true)
     FRX_EVAL_FORM(true, true, true, true, true, void, true, true)
     FRX_EVAL_FORM(true, true, true, true, false, void, true, true)
+    FRX_EVAL_FORM(true, true, true, true, true, EvalGeomK16, true, true, true)   // the adjoint's operands in front of the poll (ADJ): every form with the shortened prelude has one
+    FRX_EVAL_FORM(true, true, true, true, false, EvalGeomK16, true, true, true)
+    FRX_EVAL_FORM(true, true, true, true, true, void, true, true, true)
+    FRX_EVAL_FORM(true, true, true, true, false, void, true, true, true)
 #undef FRX_EVAL_FORM
     return (int)hipErrorInvalidValue;                                 // (a form nobody instantiated)
 }
 // the form of an evaluation without the stamps on a handle outside the class: the one the occupancy query asks about
 static EvalClusterForm eval_plain_form() { EvalClusterForm m; (void)eval_cluster_form(eval_switches(), false, false, true, m); return m; }
 
+int eval_cluster_adjoint(const LaunchGeom &g) {
+    EvalClusterForm m;
+    if (!g.ev_G || !eval_cluster_form(eval_switches(), eval_geom_class(g), false, true, m)) return 0;
+    return (eval_form_has_adjoint(m) && !m.old_adjoint) ? 1 : 0;
+}
 int eval_cluster_raise_limit(size_t bytes) {
     EvalClusterForm forms[4];
     const int n = eval_cluster_raised_forms(eval_switches(), forms);

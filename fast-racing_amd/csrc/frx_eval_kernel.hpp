@@ -11,7 +11,8 @@
 //                     wave - loads tau into registers as its first loads and forms the durations on its own, waves 1-3 stage xi and the polytopes (PRE below: without a
 //                     test per element; FRX_EVAL_PRELUDE=0 takes the form before); one early barrier
 //                     (counters zeroed, the status word broadcast) and the barrier in front of the coefficient collection are the only workgroup barriers of the forward map
-//   workgroup 0       LEADER: then everything of the adjoint that does not need the penalty partials, polls the partials, finishes the adjoint, writes f and the gradient
+//   workgroup 0       LEADER: then everything of the adjoint that does not need the penalty partials (ADJ below: the waypoint layer's operands and scale factors too),
+//                     polls the partials, finishes the adjoint, writes f and the gradient
 //   workgroups 1..G-1 MEMBERS, every WAVE on its own behind the forward map: the corridor blocks of its wave-task (ppw pieces; loaded behind the forward map's own loads,
 //                     in flight under it), the penalty samples out of the workgroup's (C, T) copy, the 20 partials per piece out as self-validating granules
 //                     (rk_ll_put, frx_kernels.hpp: no drain, no flag behind the payload) and leave
@@ -170,7 +171,14 @@ template <> struct eval_geom<void> { static constexpr bool fixed = false; static
 // same two chains - a member's wave 0 requesting its corridor block behind the durations, the Hermite operands under the wait for the last reduction step, the axis
 // waves' step gate without its sleep - measured level or slower on top of it and are not in the tree.  The stamped instantiation (CH = false) of either prelude carries
 // the stamps of both chains stretch by stretch: slots 80..110, frx_debug_profile_eval_forward.
-template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void, bool FR = false, bool PRE = false>
+// ADJ (the default wherever the shortened prelude is on; FRX_EVAL_ADJOINT=0 takes the adjoint before, A/B): the LEADER's adjoint gets the waypoint layer's operands in
+// front of the poll (EvalHandoff<.., AJ>, backward_knot_wsp64: frx_kernels.hpp).  From the poll to the end of the kernel only the leader works, so whatever stands
+// behind the poll is on the only chain there is; between the solve and the barrier behind the knot adjoint every axis lane requested forty LDS reads, read the forward
+// map's four sums and divided - none of which depends on a partial.  They are requested next to the 52 multipliers instead, where the leader waits anyway; behind the
+// solve only the dozen operations on mu remain in front of the barrier (0.64 -> 0.40 us on the stamps).  The place of loads only: f and the gradient are the other
+// form's bits (tests/test_gpu_eval_adjoint.py).  Measured 11.90 -> 11.43 us per evaluation (profiles/NOTES.md); the adjoint's top out of the front's registers instead
+// of through the offset tables, built with it, measured 0.08 us SLOWER on its own and is not in the tree.
+template <bool ARGP, bool ET, bool TAIL = true, bool HO = false, bool CH = false, class GEO = void, bool FR = false, bool PRE = false, bool ADJ = false>
 __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::conditional<ARGP, const EvalClusterArgs *__restrict__, EvalClusterArgs>::type arg, EvalCallArgs call,
                                                          const EvalFront *__restrict__ front) {   // (front: a kernel argument of its own - through a restrict pointer to const the record is a scalar load)
     static_assert(!CH || (ARGP && TAIL && HO), "the production form: argument pointer, inline tail, value-major hand-off");
@@ -179,6 +187,7 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
     static_assert(!GF || (ARGP && ET && TAIL && HO), "the geometry class: the default form of every other switch");
     static_assert(!FR || (ARGP && ET), "the two-trip front: the argument pointer and early durations");
     static_assert(!PRE || (FR && HO), "the shortened prelude: the two-trip front and the value-major hand-off");
+    static_assert(!ADJ || PRE, "the adjoint's operands in front of the poll: where the shortened prelude is on");
     const EvalClusterArgs &a = [&]() -> const EvalClusterArgs & { if constexpr (ARGP) return *arg; else return arg; }();
     const auto stp = [&]() -> long long * { if constexpr (CH) return nullptr; else return a.dp.stamps; };   // (CH: a constant - every stamp below folds away)
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -444,8 +453,8 @@ __global__ __launch_bounds__(256, 1) void k_eval_cluster(typename std::condition
         ch.g = (double *)q_g; t_f = (double *)q_f; t_done = (unsigned *)q_done; t_sh = (unsigned *)q_sh;
     }
     const EvalTail tl{verdict, t_f, t_done, tag, t_sh, k == 0 ? stp() : nullptr, TAIL};
-    const EvalHandoff<HO, CH> ho{k == 0 ? stp() : nullptr, ch};
-    backward_knot_body<true, 64, 0, EvalTail, EvalHandoff<HO, CH>>(a.dp, call.x, a.T, a.C, nullptr, call.f, call.g, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, nsteps, tap, c, ev, ctl, &ro, &tl, &ho);
+    const EvalHandoff<HO, CH, ADJ> ho{k == 0 ? stp() : nullptr, ch};
+    backward_knot_body<true, 64, 0, EvalTail, EvalHandoff<HO, CH, ADJ>>(a.dp, call.x, a.T, a.C, nullptr, call.f, call.g, a.maxCN, a.maxXb, a.maxVb, 64, nullptr, nsteps, tap, c, ev, ctl, &ro, &tl, &ho);
     if (stp() && k == 0 && t == 0) stp()[42] = (long long)wall_clock64();
     if constexpr (TAIL) {
         if (stp() && k == 0 && t == 0) stp()[43] = (long long)wall_clock64();

@@ -127,12 +127,22 @@ struct EvalTail { volatile __attribute__((address_space(3))) unsigned *verdict; 
 // stamps are a property of the INSTANTIATION: the diagnostics launch the CH = false one), and what the stretch behind the poll reads from the argument block - rho, the
 // fixed-time layer's switches and total, the gradient's base - comes in `ch`, loaded once in front of the poll and held in scalar registers: behind a pointer every such
 // field is a scalar load at its use, whose wait (lgkmcnt) also drains the LDS reads the wave has in flight around it.
+// AJ (with TR only; FRX_EVAL_ADJOINT=0 takes the other form, A/B): the leader's adjoint with the waypoint layer's operands IN FRONT of the poll.  An axis lane's
+// operands of that layer - the LDS reads of eight variables and of eight vertices' three coordinates, the forward map's four sums, the division 1 / (1 + |xi|^2) and the
+// three scale factors behind it - are requested next to the 52 multipliers, under the wait, instead of between the solve and the barrier behind the knot adjoint, where
+// they sat on the only chain there is.  Same expressions in the same order; none reads a partial.  256 VGPRs and 48 AGPRs instead of 232 and none: 24 of the operand
+// doubles wait in AGPRs and come back with one v_accvgpr_read per half behind the barrier (profiles/NOTES.md).  st: [77] axis wave 1 has requested the operands (100 MHz).
 struct EvalChain { double rho, sumT; int soft, c2; double *g; };
-template <bool TR, bool CH = false> struct EvalHandoff { static constexpr bool tr = TR, chain = CH; long long *st; EvalChain ch; };
+template <bool TR, bool CH = false, bool AJ = false> struct EvalHandoff {
+    static_assert(!AJ || TR, "the adjoint's operands in front of the poll: with the multipliers there");
+    static constexpr bool tr = TR, chain = CH, adjoint = AJ; long long *st; EvalChain ch;
+};
 template <class HO> struct ho_transposed { static constexpr bool value = HO::tr; };
 template <> struct ho_transposed<void> { static constexpr bool value = false; };
 template <class HO> struct ho_chain { static constexpr bool value = HO::chain; };
 template <> struct ho_chain<void> { static constexpr bool value = false; };
+template <class HO> struct ho_adjoint_early { static constexpr bool value = HO::adjoint; };
+template <> struct ho_adjoint_early<void> { static constexpr bool value = false; };
 // (the early-duration form's sync object, EvalEarlySync: ES::nostamps - no cycle stamps compiled into forward_knot_body)
 template <class ES> struct es_nostamps { static constexpr bool value = ES::nostamps; };
 template <> struct es_nostamps<void> { static constexpr bool value = false; };
@@ -2189,8 +2199,30 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
     constexpr bool TAIL = !std::is_void<TL>::value;     // the one-launch evaluation's tail (EvalTail); nothing of it is compiled into the other callers
     constexpr bool HOST = !std::is_void<HO>::value, HOTR = ho_transposed<HO>::value;   // its hand-off of the partials (EvalHandoff): the stamps; the transposed granules
     constexpr bool CHN = ho_chain<HO>::value;           // (EvalChain) no stamps in this instantiation, the argument block's scalars from ho->ch
+    constexpr bool AJ = ho_adjoint_early<HO>::value;    // (EvalHandoff, AJ) the waypoint layer's operands in front of the poll
 #define BK_STAMP(slot) do { if constexpr (!CHN) FRX_STAMP(slot); } while (0)
 #define BK_STAMP_AX(slot) do { if constexpr (!CHN) FRX_STAMP_AX(slot); } while (0)
+// the waypoint layer's operands of an axis lane (one text for its two places: behind the solve, or - AJ - in front of the poll)
+#define BK_WAYPOINT_OPERANDS() \
+        if (wact0) { \
+            nv1w = r_wnv - 1; xbw = r_wxb; \
+            Vw = vs + 3 * (r_wvb - cv0) + (ro ? ro->vskew * wpt : 0); \
+            xiw = xs + (xbw - x0); \
+            if (cached_lds) { const double *wq = ro->wq + 4 * wpt; qn0 = wq[0]; wq1 = wq[1]; wq2 = wq[2]; wq3 = wq[3]; } \
+            else if (cached0) { qn0 = r_wq0.x; wq1 = r_wq0.y; wq2 = r_wq1.x; wq3 = r_wq1.y; } \
+            _Pragma("unroll") \
+            for (int j = 0; j < WPF; j++) { \
+                const int a = min(sub + 2 * j, nv1w - 1); \
+                pxv[j] = xiw[a]; pvx[j] = Vw[3 * (a + 1)]; pvy[j] = Vw[3 * (a + 1) + 1]; pvz[j] = Vw[3 * (a + 1) + 2]; \
+                pdd[j] = tapped ? dsv[xbw - x0 + a] : 0.0; \
+            } \
+            if (cached0) { \
+                const double qp1 = qn0 + 1.0, iq = 1.0 / qp1, sc = 2.0 * iq; \
+                w_c2sc = 2.0 * sc; w_iq2 = iq * iq; w_sc22 = 2.0 * sc * sc; \
+                _Pragma("unroll") \
+                for (int j = 0; j < WPF; j++) if (sub + 2 * j < nv1w) t_xx += pxv[j] * pxv[j]; \
+            } \
+        }
     const auto a_rho = [&]() -> double { if constexpr (CHN) return ho->ch.rho; else return dp.rho; };       // (each read at its use, as ever, where they do not come in `ch`)
     const auto a_sumT = [&]() -> double { if constexpr (CHN) return ho->ch.sumT; else return dp.sumT; };
     const auto a_soft = [&]() -> int { if constexpr (CHN) return ho->ch.soft; else return dp.soft; };
@@ -2369,6 +2401,12 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
 #pragma unroll
             for (int i = 0; i < 4; i++) Di[i] = pw[kc * pws + nsteps * 8 + i];
         }
+        // (AJ) and the waypoint layer's operands and scale factors with them: nothing of it reads a partial, and behind the solve it sat on the leader's chain
+        if constexpr (AJ) {
+            if (wave != 0) { BK_WAYPOINT_OPERANDS() }
+            // (the stamp waits for nothing: with the operands forced into their registers here the stamped wave reached its poll 0.36 us later than the production one has to)
+            if constexpr (HOST && !CHN) { if (ho->st && k == 64) ho->st[77] = (long long)wall_clock64(); }
+        }
     }
     if (SH && ro && ro->o20ll) {
         // Resident caller: the 20 partials of piece kp arrive as granules tagged with the number of this evaluation; lane kk of wave 0 polls {cost, d/dT},
@@ -2511,26 +2549,8 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
         BK_STAMP_AX(27);
         // The waypoint layer's operands - this lane's vertices, variables and direction elements, the forward map's two sums - are requested HERE, where the
         // solve's 52 multipliers are dead: their LDS round trips run under the knot adjoint and the barrier instead of behind it (in front of the
-        // poll, next to the multipliers, they cost the resident kernel's leader 190 spilled registers).
-        if (wact0) {                                                  // (<= 64 pieces: 63 waypoints on the 96 lane pairs of the axis waves - one pass)
-            nv1w = r_wnv - 1; xbw = r_wxb;
-            Vw = vs + 3 * (r_wvb - cv0) + (ro ? ro->vskew * wpt : 0);
-            xiw = xs + (xbw - x0);
-            if (cached_lds) { const double *wq = ro->wq + 4 * wpt; qn0 = wq[0]; wq1 = wq[1]; wq2 = wq[2]; wq3 = wq[3]; }
-            else if (cached0) { qn0 = r_wq0.x; wq1 = r_wq0.y; wq2 = r_wq1.x; wq3 = r_wq1.y; }
-#pragma unroll
-            for (int j = 0; j < WPF; j++) {
-                const int a = min(sub + 2 * j, nv1w - 1);
-                pxv[j] = xiw[a]; pvx[j] = Vw[3 * (a + 1)]; pvy[j] = Vw[3 * (a + 1) + 1]; pvz[j] = Vw[3 * (a + 1) + 2];
-                pdd[j] = tapped ? dsv[xbw - x0 + a] : 0.0;
-            }
-            if (cached0) {
-                const double qp1 = qn0 + 1.0, iq = 1.0 / qp1, sc = 2.0 * iq;
-                w_c2sc = 2.0 * sc; w_iq2 = iq * iq; w_sc22 = 2.0 * sc * sc;
-#pragma unroll
-                for (int j = 0; j < WPF; j++) if (sub + 2 * j < nv1w) t_xx += pxv[j] * pxv[j];
-            }
-        }
+        // poll, next to the multipliers, they cost the resident kernel's leader 190 spilled registers; the one-launch evaluation's leader has the registers: AJ above).
+        if constexpr (!AJ) { BK_WAYPOINT_OPERANDS() }               // (<= 64 pieces: 63 waypoints on the 96 lane pairs of the axis waves - one pass)
         // ---- through the knot system (knot_adjoint_piece, rows from above): duration term and d f / d(p_{k+1} - p_k) ----
         double mu1v = lane_down1(muv), mu1a = lane_down1(mua);
         if (kk >= N - 1) { mu1v = 0.0; mu1a = 0.0; }
@@ -2714,6 +2734,7 @@ __device__ __forceinline__ void backward_knot_wsp64(const DevProblem &dp, const 
     BK_STAMP(24);
 #undef BK_STAMP
 #undef BK_STAMP_AX
+#undef BK_WAYPOINT_OPERANDS
 }
 
 // SH: out20 (and T, C) were written by workgroups of the same launch.  TL, HO (EvalTail, EvalHandoff: the one-launch evaluation only): see backward_knot_wsp64.

@@ -96,21 +96,26 @@ public:
     }
 };
 
-// ---- k_eval_cluster<ARGP, ET, TAIL, HO, CH, GEO, FR, PRE> ----
+// ---- k_eval_cluster<ARGP, ET, TAIL, HO, CH, GEO, FR, PRE, ADJ> ----
 // geo: the geometry class EvalGeomK16.  old_front (FR = false; only with argp and et - false in every other form): the front that walks the offset tables, FRX_EVAL_FRONT=0;
 // an inverted flag, so that a form written with the six members in front of it is the default one.  old_prelude (PRE = false; only where the shortened prelude of the
-// forward map exists - the two-trip front with the value-major hand-off - and false in every other form): the prelude before, FRX_EVAL_PRELUDE=0; inverted likewise
-struct EvalClusterForm { bool argp, et, tail, ho, ch, geo; bool old_front = false; bool old_prelude = false; };
+// forward map exists - the two-trip front with the value-major hand-off - and false in every other form): the prelude before, FRX_EVAL_PRELUDE=0; inverted likewise.
+// old_adjoint (ADJ = false; only where the shortened prelude is on - and false in every other form): the leader's adjoint as it was, FRX_EVAL_ADJOINT=0; inverted likewise
+struct EvalClusterForm { bool argp, et, tail, ho, ch, geo; bool old_front = false; bool old_prelude = false; bool old_adjoint = false; };
 inline bool operator==(const EvalClusterForm &a, const EvalClusterForm &b) {
-    return a.argp == b.argp && a.et == b.et && a.tail == b.tail && a.ho == b.ho && a.ch == b.ch && a.geo == b.geo && a.old_front == b.old_front && a.old_prelude == b.old_prelude;
+    return a.argp == b.argp && a.et == b.et && a.tail == b.tail && a.ho == b.ho && a.ch == b.ch && a.geo == b.geo && a.old_front == b.old_front && a.old_prelude == b.old_prelude &&
+           a.old_adjoint == b.old_adjoint;
 }
 // has this form a shortened prelude to take or to leave?  (the two-trip front - argp, et, not old_front - and the value-major hand-off)
 constexpr bool eval_form_has_prelude(const EvalClusterForm &f) { return f.argp && f.et && !f.old_front && f.ho; }
+// has this form the adjoint's operands in front of the poll to take or to leave?  (the two-trip front, the value-major hand-off and the shortened prelude all on)
+constexpr bool eval_form_has_adjoint(const EvalClusterForm &f) { return eval_form_has_prelude(f) && !f.old_prelude; }
 // the six FRX_EVAL_* switches as set (true unless the variable begins with '0'); a switch only counts with the ones in front of it at their defaults.
 // old_front: FRX_EVAL_FRONT begins with '0' (inverted: unset is false) - it shows in every form with the argument pointer and early durations, and selects no other form.
-// old_prelude: FRX_EVAL_PRELUDE begins with '0' (inverted likewise) - it shows in every form with the two-trip front and the value-major hand-off, and selects no other form
+// old_prelude: FRX_EVAL_PRELUDE begins with '0' (inverted likewise) - it shows in every form with the two-trip front and the value-major hand-off, and selects no other form.
+// old_adjoint: FRX_EVAL_ADJOINT begins with '0' (inverted likewise) - it shows in every form that has the shortened prelude on, and selects no other form
 struct EvalSwitches {
-    bool argptr, early_t, tail, handoff, chain, geom; bool old_front = false; bool old_prelude = false;
+    bool argptr, early_t, tail, handoff, chain, geom; bool old_front = false; bool old_prelude = false; bool old_adjoint = false;
     constexpr bool handoff_on() const { return handoff && argptr && tail; }
     constexpr bool chain_on() const { return chain && handoff_on(); }
     constexpr bool geom_on() const { return geom && handoff_on() && early_t; }
@@ -126,10 +131,11 @@ inline bool eval_cluster_form(const EvalSwitches &s, bool geom_class, bool stamp
     else f = {false, s.early_t, true, false, false, false};
     f.old_front = s.old_front && f.argp && f.et;
     f.old_prelude = s.old_prelude && eval_form_has_prelude(f);
+    f.old_adjoint = s.old_adjoint && eval_form_has_adjoint(f);
     return !f.argp || have_dev_args;
 }
 // The forms whose dynamic-LDS limit a process raises: every form eval_cluster_form can give under these switches.  Returns their number: at most 4, one per
-// value of (geom_class, stamped); old_front and old_prelude are per-process switches, not inputs - an input added to eval_cluster_form is one more loop here and doubles the bound.
+// value of (geom_class, stamped); old_front, old_prelude and old_adjoint are per-process switches, not inputs - an input added to eval_cluster_form is one more loop here and doubles the bound.
 inline int eval_cluster_raised_forms(const EvalSwitches &s, EvalClusterForm out[4]) {
     int n = 0;
     for (int geom_class = 0; geom_class <= (s.geom_on() ? 1 : 0); geom_class++)

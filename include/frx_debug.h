@@ -68,6 +68,10 @@ int frx_debug_eval_front(const frx_problem *p);
 /* Which prelude the forward map of the handle's one-launch form takes: 1 = the shortened one (the axis waves store what they staged without predication, each
  * value at the clamped index it was loaded from, and load it in one basic block), 0 = the form before (FRX_EVAL_PRELUDE=0, a form without the two-trip front or the value-major hand-off, or no one-launch form at all).  The two give the same bits. */
 int frx_debug_eval_prelude(const frx_problem *p);
+/* Which adjoint the leader of the handle's one-launch form runs: 1 = the one with its operands in front of the poll for the penalty partials (its top reads no offset
+ * table - the front's record and lanes hold the values - and an axis lane's waypoint-layer operands and scale factors are requested next to the multipliers), 0 = the
+ * form before (FRX_EVAL_ADJOINT=0, a form without the shortened prelude, or no one-launch form at all).  The two give the same bits. */
+int frx_debug_eval_adjoint(const frx_problem *p);
 /* The solo form of an evaluation (one workgroup per candidate runs forward map, penalty integral and adjoint in ONE launch; batches larger than the clusters of the
  * one-launch form reach; the per-stage rounds of frx_optimize take it too).  mode 0 = never, 1 = from the handle's batch-size threshold on (default; FRX_EVAL_SOLO_MIN_B),
  * 2 = at every batch size, also where the cluster form would apply.  Results are bit-identical to the three stage launches (replaces the same objectiveFunc,
@@ -85,7 +89,8 @@ int frx_debug_profile_eval_cluster(frx_problem *p, const double *x, long long *o
 /* The same with the stamps of the evaluation's tail behind the first 64 (100 MHz counter, as 40..48): out80[64] wave 0 of the leader behind the barrier that follows
  * the knot adjoint, [65] its last gradient store issued, [66] axis wave 1's last store issued, [67] thread 0 has the verdict, [68] thread 0 has issued `done`;
  * the hand-off of the penalty partials: [69] wave 0 of the first member has the gate word's value, [70] / [71] wave 0 of the leader enters / has left its poll for the
- * partials, [72] / [73] the same for axis wave 1, [74] axis wave 1's Hermite adjoint is done, [75] / [76] NOT times: the spins of lane 0 of wave 0 / of axis wave 1. */
+ * partials, [72] / [73] the same for axis wave 1, [74] axis wave 1's Hermite adjoint is done, [75] / [76] NOT times: the spins of lane 0 of wave 0 / of axis wave 1;
+ * [77] (frx_debug_eval_adjoint = 1 only, else 0) axis wave 1 has requested its waypoint-layer operands and formed the scale factors, in front of its poll. */
 int frx_debug_profile_eval_tail(frx_problem *p, const double *x, long long *out80);
 /* The same with the stamps of the forward map's prelude behind those (100 MHz counter).  Wave 0 of the leader, out112[80..84]: at the early barrier, out of it, tau in
  * its register, the coarse durations written, the knot rows built and the first inverse done (the durations formed and the matrix steps: [50], [53..58]); wave 0 of the

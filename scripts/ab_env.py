@@ -8,7 +8,8 @@ Known switches of the one-launch evaluation, each read once per process ("0" = t
 (value-major granules of the penalty partials, 16-byte polls, multipliers ahead of the poll), FRX_EVAL_CHAIN (the production instantiation: no cycle stamps compiled in,
 the argument block's scalars loaded once and pinned in scalar registers), FRX_EVAL_GEOM (the compile-time geometry class of the headline handle: 17 samples per piece, 3 pieces
 per wave-task, Kmax = 8, six reduction steps), FRX_EVAL_FRONT (two trips behind the kernel's entry: front records and the argument block's leading lines), FRX_EVAL_PRELUDE (the forward map's axis waves stage xi and the
-polytopes without a test per element: loads in one basic block, stores at the clamped index); FRX_EVAL_FUSED_WT=1 forces write-through payload."""
+polytopes without a test per element: loads in one basic block, stores at the clamped index), FRX_EVAL_ADJOINT (the leader's waypoint-layer operands requested in front of
+its poll for the penalty partials); FRX_EVAL_FUSED_WT=1 forces write-through payload."""
 import hashlib, json, os, subprocess, sys
 child = r'''
 import os, sys, json, hashlib
