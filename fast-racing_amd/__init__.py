@@ -76,6 +76,7 @@ ABI_SYMBOLS = [
     "frx_enumerate_vertices_batch", "frx_enumerate_vertices_batch_device", "frx_corridor_slots_to_tasks_device",
     "frx_map_esdf", "frx_map_esdf_workspace", "frx_map_esdf_device", "frx_map_esdf_on_device", "frx_map_mark_cloud_device",
     "frx_trajectory_map_distance", "frx_trajectory_map_distance_device", "frx_map_distance_fold",
+    "frx_grid_search_levels", "frx_route_plan_levels_batch", "frx_route_search_workspace", "frx_route_plan_batch_device", "frx_route_plan_batch",
 ]
 # diagnostics, include/frx_debug.h: not part of the drop-in boundary
 DEBUG_SYMBOLS = [
@@ -243,6 +244,11 @@ def lib():
         L.frx_trajectory_map_distance.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_double, _vp, _vp, _vp]
         L.frx_trajectory_map_distance_device.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]
         L.frx_map_distance_fold.argtypes = [C.c_int, _vp, _vp, _vp, C.c_double, _vp, _vp]
+        L.frx_grid_search_levels.argtypes = [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]
+        L.frx_route_plan_levels_batch.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 7
+        L.frx_route_search_workspace.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.frx_route_plan_batch_device.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 8
+        L.frx_route_plan_batch.argtypes = [C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 7
         for name in ABI_SYMBOLS + DEBUG_SYMBOLS:
             fn = getattr(L, name)
             if name not in ("frx_version", "frx_last_error", "frx_device_count", "frx_lbfgs_default_params",
@@ -525,6 +531,65 @@ class VoxelMap:
         _check(lib().frx_route_plan(C.byref(self._s), start.ctypes.data, goal.ctypes.data, len(gates), gates.ctypes.data if len(gates) else None,
                                     float(eps), int(use_jps), int(threads), cap, C.byref(n), out.ctypes.data, st.ctypes.data, ex.ctypes.data))
         return out[:n.value].copy(), st, ex
+
+    def _route_batch(self, routes, call, cap_level, cap_raw, cap_pts, cap_total):
+        off, pts = pack_routes(routes)
+        R = len(routes); NL = max(int(off[-1]) - R, 1)
+        cap_total = int(cap_total) if cap_total is not None else max(2 * R, NL * int(cap_pts))
+        path_off = np.zeros(R + 1, np.int32); path = np.zeros((max(cap_total, 1), 3)); rst = np.zeros(max(R, 1), np.int32)
+        lst = np.zeros(NL, np.int32); lev = np.zeros(NL, np.int32); mx = np.zeros(NL, np.int32); need = C.c_int()
+        rc = call(C.byref(self._s), R, off.ctypes.data, pts.ctypes.data, int(cap_level), int(cap_raw), int(cap_pts), cap_total, path_off.ctypes.data, path.ctypes.data,
+                  rst.ctypes.data, lst.ctypes.data, lev.ctypes.data, mx.ctypes.data, C.addressof(need))
+        if rc != -5:                                                      # FRX_ERR_CAPACITY: every output is valid, `need` says what the routes would take
+            _check(rc)
+        n_legs = int(off[-1]) - R
+        return dict(path_off=path_off, path=path[:path_off[-1]].copy(), paths=[path[path_off[r]:path_off[r + 1]].copy() for r in range(R)], route_status=rst[:R],
+                    leg_status=lst[:n_legs], levels=lev[:n_legs], max_level_cells=mx[:n_legs], need=need.value, fits=rc == 0)
+
+    def route_batch_host(self, routes, cap_level: int = 1 << 16, cap_raw: int = 1 << 16, cap_pts: int = 1 << 12, cap_total=None):
+        """frx_route_plan_levels_batch on one host thread, the referee of route_batch: routes = a list of (n_i, 3) waypoint arrays (start, gates, goal).
+        dict(path_off, path, paths (per route), route_status, leg_status, levels, max_level_cells, need, fits); cap_total None: room for every leg's cap_pts."""
+        return self._route_batch(routes, lib().frx_route_plan_levels_batch, cap_level, cap_raw, cap_pts, cap_total)
+
+    def route_batch(self, routes, device: int = 0, cap_level: int = 1 << 16, cap_raw: int = 1 << 16, cap_pts: int = 1 << 12, cap_total=None):
+        """frx_route_plan_batch: the same batch searched on the device (upload, four launches, download); the same dict, bit for bit."""
+        return self._route_batch(routes, lambda *a: lib().frx_route_plan_batch(int(device), *a), cap_level, cap_raw, cap_pts, cap_total)
+
+
+def pack_routes(routes):
+    """(pt_off int32 [n + 1], pts float64 [sum, 3]) of a list of routes, each an (n_i, 3) array of waypoints: start, gates in order, goal."""
+    routes = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 3) for r in routes]
+    off = np.zeros(len(routes) + 1, np.int32); off[1:] = np.cumsum([len(r) for r in routes])
+    return off, (np.ascontiguousarray(np.concatenate(routes)) if routes else np.zeros((0, 3)))
+
+
+def route_search_workspace(dim, n_legs: int, cap_level: int, cap_raw: int, cap_pts: int) -> int:
+    """frx_route_search_workspace: bytes of device scratch route_plan_batch_device needs; FrxError with code -1 / -5 for arguments it refuses."""
+    d = (C.c_int * 3)(*[int(v) for v in dim])
+    n = C.c_size_t(0)
+    _check(lib().frx_route_search_workspace(d, int(n_legs), int(cap_level), int(cap_raw), int(cap_pts), C.byref(n)))
+    return int(n.value)
+
+
+def route_plan_batch_device(map_struct: VoxelMapStruct, n_routes: int, n_legs: int, pt_off_dev: int, pts_dev: int, cap_level: int, cap_raw: int, cap_pts: int,
+                            cap_total: int, work_dev: int, path_off_dev: int, path_dev: int, route_status_dev: int, leg_status_dev: int, leg_levels_dev: int,
+                            leg_max_level_dev: int, stream: int = 0):
+    """frx_route_plan_batch_device: four launches on `stream`; map_struct's cells and the other addresses (integers) are device memory.  Outputs: the CSR
+    path_off [n_routes + 1] / path [cap_total][3] that corridor_generate_batch_device takes, route_status [n_routes], and per leg status, levels, max level."""
+    _check(lib().frx_route_plan_batch_device(C.byref(map_struct), int(n_routes), int(n_legs), pt_off_dev or None, pts_dev or None, int(cap_level), int(cap_raw),
+                                             int(cap_pts), int(cap_total), work_dev or None, path_off_dev or None, path_dev or None, route_status_dev or None,
+                                             leg_status_dev or None, leg_levels_dev or None, leg_max_level_dev or None, stream))
+
+
+def grid_search_levels(cmap, dim, start, goal, cap: int = 1 << 20):
+    """frx_grid_search_levels on an int8 occupancy array (x fastest, 3-D): (path START-first k x 3 int, levels, max_level_cells) of the canonical level search;
+    an empty path and levels = -1 when there is none."""
+    cmap = np.ascontiguousarray(cmap, dtype=np.int8).reshape(-1)
+    dim = np.asarray(dim, dtype=np.int32); start = np.asarray(start, dtype=np.int32); goal = np.asarray(goal, dtype=np.int32)
+    path = np.zeros((cap, 3), dtype=np.int32); n = C.c_int(); lev = C.c_int(); mx = C.c_int()
+    _check(lib().frx_grid_search_levels(cmap.ctypes.data, dim.ctypes.data, start.ctypes.data, goal.ctypes.data, cap, C.byref(n), path.ctypes.data, C.byref(lev),
+                                        C.byref(mx)))
+    return path[:n.value].copy(), lev.value, mx.value
 
 
 def map_esdf(vmap: VoxelMap, fields=("pos", "neg", "all")):

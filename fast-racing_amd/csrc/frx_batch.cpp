@@ -18,6 +18,7 @@
 #include "frx_esdf_plan.hpp"
 #include "frx_hip_scope.hpp"
 #include "frx_internal.hpp"
+#include "frx_route_host.hpp"
 
 namespace {
 
@@ -279,6 +280,85 @@ int frx_map_mark_cloud_device(const frx_voxel_map *map, signed char *cells_dev, 
     if (frx_device_count() < 1) return no_device();
     const hipError_t e = (hipError_t)frx::launch_mark_cloud(map->origin, map->dim, map->res, cells_dev, n_pts, pts_dev, n_inside_dev, hip_stream);
     return e == hipSuccess ? FRX_OK : hip_failed(who, e);
+}
+
+// ---- a batch of routes through the voxel map (frx_route_kernel.hpp): the device form is four launches, the blocking form is those between an upload and a
+// download; the splice into one CSR happens on the device in both ----
+int frx_route_plan_batch_device(const frx_voxel_map *map, int n_routes, int n_legs, const int *pt_off_dev, const double *pts_dev, int cap_level, int cap_raw,
+                                int cap_pts, int cap_total, void *work_dev, int *path_off_dev, double *path_dev, int *route_status_dev, int *leg_status_dev,
+                                int *leg_levels_dev, int *leg_max_level_dev, void *hip_stream) {
+    const char *who = "frx_route_plan_batch_device";
+    if (!pt_off_dev || !pts_dev || !work_dev || !path_off_dev || !path_dev || !route_status_dev || !leg_status_dev || !leg_levels_dev || !leg_max_level_dev)
+        return invalid(who, "null argument");
+    if (int rc = frx::route_batch_args(map, who, n_routes, cap_level, cap_raw, cap_pts, cap_total)) return rc;
+    if (n_legs < n_routes) return invalid(who, "n_legs < n_routes (every route has at least two waypoints)");
+    if ((size_t)work_dev % 8 != 0) return invalid(who, "work_dev is not 8-byte aligned (the workspace begins with doubles and its labels are cleared as 64-bit words)");
+    if (frx::route_work(map->dim, n_legs, cap_level, cap_raw, cap_pts).verdict != frx::ROUTE_WORK_FITS)
+        return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": the workspace exceeds 4e18 bytes");
+    if (frx_device_count() < 1) return no_device();
+    frx::RouteLaunch L;
+    for (int i = 0; i < 3; i++) { L.origin[i] = map->origin[i]; L.dim[i] = map->dim[i]; }
+    L.res = map->res; L.cells = map->cells; L.pt_off = pt_off_dev; L.pts = pts_dev;
+    L.n_routes = n_routes; L.n_legs = n_legs; L.cap_level = cap_level; L.cap_raw = cap_raw; L.cap_pts = cap_pts; L.cap_total = cap_total;
+    L.work = work_dev; L.path_off = path_off_dev; L.path = path_dev; L.route_status = route_status_dev; L.leg_status = leg_status_dev;
+    L.leg_levels = leg_levels_dev; L.leg_max_level = leg_max_level_dev;
+    const hipError_t e = (hipError_t)frx::launch_route(L, hip_stream);
+    return e == hipSuccess ? FRX_OK : hip_failed(who, e);
+}
+
+int frx_route_plan_batch(int device, const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
+                         int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels, int *leg_max_level, int *n_pts) {
+    const char *who = "frx_route_plan_batch";
+    if (!pt_off || !pts || !path_off || !path || !route_status || !leg_status || !leg_levels || !leg_max_level || !n_pts) return invalid(who, "null argument");
+    if (int rc = frx::route_batch_args(map, who, n_routes, cap_level, cap_raw, cap_pts, cap_total)) return rc;
+    long long legs = 0;
+    if (int rc = frx::route_offset_args(who, n_routes, pt_off, &legs)) return rc;
+    const frx::RouteWork w = frx::route_work(map->dim, legs, cap_level, cap_raw, cap_pts);
+    if (w.verdict != frx::ROUTE_WORK_FITS) return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": the workspace exceeds 4e18 bytes");
+    if (frx_device_count() < 1) return no_device();
+    DeviceGuard restore_device;
+    if (hipSetDevice(device) != hipSuccess) return invalid(who, "device ordinal out of range");
+    const size_t R = (size_t)n_routes, NL = (size_t)legs, n_wp = (size_t)pt_off[n_routes], n_cells = (size_t)w.cells;
+    DevBuf<signed char> d_cells;
+    DevBuf<unsigned char> d_work;
+    DevBuf<int> d_off, d_poff, d_rst, d_lst, d_lev, d_max;
+    DevBuf<double> d_pts, d_path;
+    int rc;
+    if ((rc = dev_alloc(d_cells, n_cells, who)) || (rc = dev_alloc(d_work, w.bytes, who)) || (rc = dev_alloc(d_off, R + 1, who)) || (rc = dev_alloc(d_poff, R + 1, who)) ||
+        (rc = dev_alloc(d_rst, R, who)) || (rc = dev_alloc(d_lst, NL, who)) || (rc = dev_alloc(d_lev, NL, who)) || (rc = dev_alloc(d_max, NL, who)) ||
+        (rc = dev_alloc(d_pts, 3 * n_wp, who)) || (rc = dev_alloc(d_path, 3 * (size_t)cap_total, who)))
+        return rc;
+    hipError_t e = to_device(d_cells.p, map->cells, n_cells);
+    if (e == hipSuccess) e = to_device(d_off.p, pt_off, R + 1);
+    if (e == hipSuccess) e = to_device(d_pts.p, pts, 3 * n_wp);
+    if (e != hipSuccess) return hip_failed(who, e);
+    frx_voxel_map dmap = *map;
+    dmap.cells = d_cells.p;
+    rc = frx_route_plan_batch_device(&dmap, n_routes, (int)legs, d_off.p, d_pts.p, cap_level, cap_raw, cap_pts, cap_total, d_work.p, d_poff.p, d_path.p, d_rst.p,
+                                     d_lst.p, d_lev.p, d_max.p, nullptr);
+    if (rc != FRX_OK) return rc;
+    std::vector<int> npts(NL);
+    e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = to_host(path_off, d_poff.p, R + 1);
+    if (e == hipSuccess) e = to_host(route_status, d_rst.p, R);
+    if (e == hipSuccess) e = to_host(leg_status, d_lst.p, NL);
+    if (e == hipSuccess) e = to_host(leg_levels, d_lev.p, NL);
+    if (e == hipSuccess) e = to_host(leg_max_level, d_max.p, NL);
+    if (e == hipSuccess) e = to_host(npts.data(), (const int *)(d_work.p + w.npts_off), NL);
+    if (e == hipSuccess && path_off[n_routes] > 0) e = to_host(path, d_path.p, 3 * (size_t)path_off[n_routes]);
+    if (e != hipSuccess) return hip_failed(who, e);
+    // the room all routes would take: a route with a failed leg takes its placeholder whatever the room
+    long long need = 0;
+    for (int r = 0, leg = 0; r < n_routes; r++) {
+        const int nl = pt_off[r + 1] - pt_off[r] - 1;
+        bool whole = true;
+        for (int l = 0; l < nl; l++) whole = whole && leg_status[leg + l] == 0;
+        need += whole ? frx::route_points(nl, &npts[leg]) : 2;
+        leg += nl;
+    }
+    if (!frx::need_fits(need, cap_total, n_pts))
+        return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": " + std::to_string(need) + " points, cap_total is " + std::to_string(cap_total));
+    return FRX_OK;
 }
 
 // Tests: the device's sight line (map_blocked, frx_chain_kernel.hpp) on n_pairs pairs of points, host buffers in and out; out[i] = 0 / 1 as frx_map_is_blocked.

@@ -22,6 +22,28 @@ static inline int voxel_map_args(const frx_voxel_map *map, const char *who, bool
     return FRX_OK;
 }
 
+// ---- the route batch ----
+// The rules every form of the route batch shares: the map (cells included), the count of routes and the four capacities; cap_total holds a two-point
+// placeholder for every route.
+static inline int route_batch_args(const frx_voxel_map *map, const char *who, int n_routes, int cap_level, int cap_raw, int cap_pts, int cap_total) {
+    if (!map) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null map");
+    if (int rc = voxel_map_args(map, who, true)) return rc;
+    if (n_routes < 1) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": n_routes < 1");
+    if (cap_level < 1 || cap_raw < 1 || cap_pts < 1) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": cap_level, cap_raw and cap_pts must be at least 1");
+    if ((long long)cap_total < 2LL * n_routes) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": cap_total < 2 n_routes (every route keeps room for its two-point placeholder)");
+    return FRX_OK;
+}
+// The rules that walk the waypoint offsets of host forms; *n_legs: the legs of all routes.
+static inline int route_offset_args(const char *who, int n_routes, const int *pt_off, long long *n_legs) {
+    if (pt_off[0] < 0) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": pt_off[0] < 0");
+    for (int r = 0; r < n_routes; r++) {
+        if (pt_off[r + 1] < pt_off[r]) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": pt_off is not monotone at route " + std::to_string(r));
+        if (pt_off[r + 1] - pt_off[r] < 2) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": route " + std::to_string(r) + " has fewer than 2 waypoints");
+    }
+    *n_legs = (long long)pt_off[n_routes] - pt_off[0] - n_routes;
+    return FRX_OK;
+}
+
 // ---- the vertex enumeration's tasks ----
 // The rules that walk coarse_n [B] and the CSR offsets of its polytopes; *n_poly: their number.
 static inline int enum_csr_args(const char *who, int B, const int *coarse_n, const int *h_off, long long *n_poly) {

@@ -210,6 +210,18 @@ int launch_mark_cloud(const double *origin, const int *dim, double res, signed c
 int launch_map_distance(int P, const double *T, const double *C, int intervals, const double *origin, const int *dim, double res, const double *field,
                         double *rows, void *stream);
 
+// ---- a batch of routes through the voxel map (frx_route_kernel.hpp) ----
+struct RouteLaunch {
+    double origin[3], res; int dim[3]; const signed char *cells;   // cells: device pointer, x fastest
+    const int *pt_off; const double *pts;                           // device pointers: [n_routes + 1], waypoints [..][3]
+    int n_routes, n_legs, cap_level, cap_raw, cap_pts, cap_total;
+    void *work;                                                     // route_work(dim, n_legs, caps).bytes of device scratch (frx_route_host.hpp)
+    int *path_off; double *path;                                    // [n_routes + 1], [cap_total][3]
+    int *route_status, *leg_status, *leg_levels, *leg_max_level;    // [n_routes], [n_legs] x 3
+};
+// Pure launches: four kernels (label clear, search and tail per leg, the splice's offsets, the splice).  hipErrorInvalidValue for arguments route_work refuses.
+int launch_route(const RouteLaunch &r, void *stream);
+
 // ---- device-vector L-BFGS (frx_lbfgs_kernels.hpp) ----
 struct DvBuffers;
 struct DvLaunch {

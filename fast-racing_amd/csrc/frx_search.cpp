@@ -1,7 +1,10 @@
 // Path-search front end on the voxel grid: the step of MavGlobalPlanner::plan upstream of the corridor
-// (MinCoPlan_CPU.cpp:13-35).  Host code by design: a best-first search is one long dependent chain of heap operations, there
-// is nothing in it for 256 CUs, and the reference's own tie order (which decides WHICH of the equally short grid paths comes
-// back, and with it every corridor cell downstream) is defined by the exact sequence of those heap operations.
+// (MinCoPlan_CPU.cpp:13-35).  The searches that return the reference's own path are host code by design: a best-first search
+// is one long dependent chain of heap operations, there is nothing in it for 256 CUs, and the reference's own tie order (which
+// decides WHICH of the equally short grid paths comes back, and with it every corridor cell downstream) is defined by the exact
+// sequence of those heap operations.  A caller that needs a shortest path of that length, not that very path, has the level
+// search (frx_route_host.hpp): its host entries are here, beside the tail they share with plan_leg, and its device form is
+// frx_route_kernel.hpp.
 //
 //   GridSearch            = JPS::GraphSearch (graph_search.h:129-264, graph_search.cpp:6-236): A* on the dense occupancy array
 //                           with the reference's successor order, its tolerance comparator (graph_search.h:20-33) and an
@@ -22,8 +25,10 @@
 // across faces.  The test suite's restatement evaluates the same expressions in IEEE double without fusing.
 #include "../../include/frx.h"
 #include "../../include/frx_debug.h"
+#include "frx_batch_host.hpp"
 #include "frx_esdf_host.hpp"
 #include "frx_internal.hpp"
+#include "frx_route_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -686,6 +691,41 @@ void plan_leg(const frx_voxel_map *m, const signed char *cmap, V3 start, V3 goal
     r.sample = sample_path(map, r.path);
 }
 
+// A leg of the level search (frx_route_host.hpp) with plan_leg's tail on the cell centres: the same checks of start and goal, the same three simplification
+// passes and the same sampling, and the three capacities of the device form as statuses.  r.sample holds the leg's points when r.status is 0.
+void plan_leg_levels(const frx_voxel_map *m, V3 start, V3 goal, int cap_level, int cap_raw, int cap_pts, frx::RouteScratch &w, std::vector<int> &raw,
+                     LegResult &r, frx::RouteSearchOut &o) {
+    VoxelMap map{m};
+    o = frx::RouteSearchOut();
+    int s[3], g[3];
+    map.to_cell(start, s);
+    if (!map.is_free(s)) {
+        r.status = o.status = frx::ROUTE_START;
+        return;
+    }
+    map.to_cell(goal, g);
+    if (!map.is_free(g)) {
+        r.status = o.status = frx::ROUTE_GOAL;
+        return;
+    }
+    o = frx::route_search(m->cells, m->dim, s, g, cap_level, cap_raw, w, raw);
+    r.status = o.status;
+    if (o.status != frx::ROUTE_OK) return;
+    const int nx = m->dim[0], ny = m->dim[1];
+    r.raw.reserve(raw.size());
+    for (const int id : raw) {
+        const int c[3] = {id % nx, (id / nx) % ny, id / (nx * ny)};
+        r.raw.push_back(map.to_point(c));
+    }
+    std::vector<V3> q = remove_corner_pts(map, r.raw);
+    std::reverse(q.begin(), q.end());
+    q = remove_corner_pts(map, q);
+    std::reverse(q.begin(), q.end());
+    r.path = remove_line_pts(q);
+    r.sample = sample_path(map, r.path);
+    if ((long long)r.sample.size() > cap_pts) r.status = o.status = frx::ROUTE_CAP_PTS;
+}
+
 int check_map(const frx_voxel_map *m, const char *who) {
     if (!m || !m->cells) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null map");
     if (!(m->res > 0) || m->dim[0] <= 0 || m->dim[1] <= 0 || m->dim[2] <= 0)
@@ -763,6 +803,96 @@ int frx_grid_search(const signed char *cmap, const int *dim, const int *start, c
         }
     if (path_xyz && int(p.size()) > cap)
         return frx::set_error(FRX_ERR_CAPACITY, "frx_grid_search: path longer than cap");
+    return FRX_OK;
+}
+
+int frx_grid_search_levels(const signed char *cmap, const int *dim, const int *start, const int *goal, int cap, int *n_path, int *path_xyz, int *levels,
+                           int *max_level_cells) {
+    const char *who = "frx_grid_search_levels";
+    if (!cmap || !dim || !start || !goal || !n_path) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    if (dim[0] <= 0 || dim[1] <= 0 || dim[2] <= 0) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": dim must be positive on all three axes");
+    if ((long long)dim[0] * dim[1] > 0x7fffffffLL || (long long)dim[0] * dim[1] * dim[2] > 0x7fffffffLL)
+        return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": more than 2^31 - 1 cells");
+    for (int i = 0; i < 3; i++)
+        if (start[i] < 0 || start[i] >= dim[i] || goal[i] < 0 || goal[i] >= dim[i])
+            return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": start or goal outside the grid");
+    const auto at = [&](const int *c) { return cmap[size_t(c[0]) + size_t(dim[0]) * c[1] + size_t(dim[0]) * dim[1] * c[2]]; };
+    frx::RouteSearchOut o;
+    std::vector<int> raw;
+    if (at(start) > 0 || at(goal) > 0)
+        o.status = frx::ROUTE_NO_PATH;                       // an occupied end: no path, as a goal behind a wall
+    else {
+        frx::RouteScratch w;
+        o = frx::route_search(cmap, dim, start, goal, 0, 0, w, raw);
+    }
+    *n_path = int(raw.size());
+    if (levels) *levels = o.levels;
+    if (max_level_cells) *max_level_cells = o.max_level_cells;
+    if (path_xyz)
+        for (int i = 0; i < int(raw.size()) && i < cap; i++)
+            path_xyz[3 * i] = raw[i] % dim[0], path_xyz[3 * i + 1] = (raw[i] / dim[0]) % dim[1], path_xyz[3 * i + 2] = raw[i] / (dim[0] * dim[1]);
+    if (path_xyz && int(raw.size()) > cap) return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": path longer than cap");
+    return FRX_OK;
+}
+
+int frx_route_plan_levels_batch(const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
+                                int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels, int *leg_max_level,
+                                int *n_pts) {
+    const char *who = "frx_route_plan_levels_batch";
+    if (!pt_off || !pts || !path_off || !path || !route_status || !leg_status || !leg_levels || !leg_max_level || !n_pts)
+        return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    if (int rc = frx::route_batch_args(map, who, n_routes, cap_level, cap_raw, cap_pts, cap_total)) return rc;
+    long long n_legs = 0;
+    if (int rc = frx::route_offset_args(who, n_routes, pt_off, &n_legs)) return rc;
+    frx::RouteScratch w;
+    std::vector<int> raw, count;
+    std::vector<V3> out;
+    long long used = 0, need = 0;
+    int leg = 0;
+    path_off[0] = 0;
+    for (int r = 0; r < n_routes; r++) {
+        const int legs = pt_off[r + 1] - pt_off[r] - 1;
+        const double *p = pts + 3 * size_t(pt_off[r]);
+        out.clear();
+        count.assign(legs, 0);
+        bool whole = true;
+        for (int l = 0; l < legs; l++, leg++) {
+            LegResult lr;
+            frx::RouteSearchOut o;
+            plan_leg_levels(map, {p[3 * l], p[3 * l + 1], p[3 * l + 2]}, {p[3 * l + 3], p[3 * l + 4], p[3 * l + 5]}, cap_level, cap_raw, cap_pts, w, raw, lr, o);
+            leg_status[leg] = o.status, leg_levels[leg] = o.levels, leg_max_level[leg] = o.max_level_cells;
+            if (o.status != frx::ROUTE_OK) {
+                whole = false;
+                continue;
+            }
+            count[l] = int(lr.sample.size());
+            if (l > 0 && !out.empty()) out.pop_back();         // the shared point once, as frx_route_plan splices
+            out.insert(out.end(), lr.sample.begin(), lr.sample.end());
+        }
+        const long long want = whole ? frx::route_points(legs, count.data()) : 2;
+        need += want;
+        route_status[r] = whole ? frx::ROUTE_WHOLE : frx::ROUTE_LEG_FAILED;
+        if (whole && !frx::route_fits(used, want, n_routes - 1 - r, cap_total)) route_status[r] = frx::ROUTE_NO_ROOM;
+        if (route_status[r] != frx::ROUTE_WHOLE) {
+            // the placeholder: the route's first and last waypoint as given
+            out.assign({V3{p[0], p[1], p[2]}, V3{p[3 * legs], p[3 * legs + 1], p[3 * legs + 2]}});
+        }
+        for (const V3 &q : out) path[3 * used] = q.x, path[3 * used + 1] = q.y, path[3 * used + 2] = q.z, used++;
+        path_off[r + 1] = int(used);
+    }
+    if (!frx::need_fits(need, cap_total, n_pts))
+        return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": " + std::to_string(need) + " points, cap_total is " + std::to_string(cap_total));
+    return FRX_OK;
+}
+
+int frx_route_search_workspace(const int *dim, int n_legs, int cap_level, int cap_raw, int cap_pts, size_t *bytes) {
+    const char *who = "frx_route_search_workspace";
+    if (!dim || !bytes) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    const frx::RouteWork w = frx::route_work(dim, n_legs, cap_level, cap_raw, cap_pts);
+    if (w.verdict == frx::ROUTE_WORK_INVALID)
+        return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": dim > 0 on all three axes, at most 2^31 - 1 cells, n_legs and every cap at least 1");
+    if (w.verdict == frx::ROUTE_WORK_CAPACITY) return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": the workspace exceeds 4e18 bytes");
+    *bytes = w.bytes;
     return FRX_OK;
 }
 

@@ -225,8 +225,10 @@ int frx_traj_to_msg(int n_pieces, const double *T, const double *C, double *coef
 int frx_msg_sample(int n_segment, const double *coef_x, const double *coef_y, const double *coef_z, const double *time,
                    const unsigned *order, double t, double *pos, double *vel, double *acc, double *jerk);
 
-/* Path-search front end on the voxel grid, host code (csrc/frx_search.cpp) -- the step of
- * MavGlobalPlanner::plan that produces the polyline frx_corridor_generate takes (MinCoPlan_CPU.cpp:13-35).
+/* Path-search front end on the voxel grid -- the step of MavGlobalPlanner::plan that produces the polyline
+ * frx_corridor_generate takes (MinCoPlan_CPU.cpp:13-35).  The searches that return the reference's OWN path (frx_grid_search,
+ * frx_jps_plan, frx_route_plan: its heap order, JPS, any eps) are host code (csrc/frx_search.cpp); a batch of routes that needs
+ * a shortest path of the reference's length, not that very path, is searched on the device (frx_route_plan_batch below).
  * frx_voxel_map = what JPS::MapUtil<3> holds (map_util.h:48-75, setMap :365): cell (i,j,k) covers
  * origin + [i,i+1) x [j,j+1) x [k,k+1) * res, stored x fastest; 0 = free, 100 = occupied, -1 = unknown (:322-327). */
 typedef struct frx_voxel_map {
@@ -290,6 +292,47 @@ int frx_jps_plan(const frx_voxel_map *map, const double *start, const double *go
  * splices stale samples there). */
 int frx_route_plan(const frx_voxel_map *map, const double *start, const double *goal, int n_gates, const double *gates, double eps,
                    int use_jps, int n_threads, int cap, int *n_out, double *path_out, int *leg_status, int *leg_expanded);
+/* A BATCH of routes through the map, searched on the device (csrc/frx_route_kernel.hpp).  The reference's plan mode is A* with eps = 1 over the six
+ * face neighbours at unit step cost: the length of its path is the breadth-first distance, an integer, and only WHICH of the equally short paths comes back
+ * depends on the order of its heap operations.  These entries return one well-defined path of that length instead, the canonical level search
+ * (csrc/frx_route_host.hpp): level 0 is the goal's cell, level L + 1 every traversable (inside, cells <= 0: unknown cells are crossed), unlabelled face neighbour
+ * of a level-L cell, built whole until a level labels the start's cell; the path descends from the start, each step to the face neighbour one level down whose
+ * squared cell distance to the goal (64-bit integers) is smallest, ties in the order -x, -y, -z, +z, +y, +x.  Then frx_jps_plan's tail, the same operations in the
+ * same order: removeCornerPts forwards and backwards, removeLinePts, samplePath.  Host and device forms agree bit for bit.
+ * Route r has the waypoints pts[pt_off[r] .. pt_off[r + 1]) - start, gates in order, goal - at least two; its legs are the consecutive pairs, all legs of all routes
+ * are independent.  Per leg (in route order): leg_status = 0 ok; 1 start not free; 2 goal not free; -1 no path; 3 a level holds more than cap_level cells; 4 the
+ * raw path holds more than cap_raw cells; 5 more than cap_pts sample points.  leg_levels = the start's level (the raw path holds that many cells plus one), -1
+ * when the search did not label the start; leg_max_level = the largest level built, the last one included (level 0 counts).  A failed leg does not disturb any
+ * other leg and the call still returns FRX_OK.
+ * The routes come back as one CSR in route order, path_off[n_routes + 1] and path[cap_total][3], the layout frx_corridor_generate_batch_device takes: the legs'
+ * sample paths with the shared point kept once.  route_status = 0 whole; 1 a leg failed; 2 the route does not fit the room left in cap_total once every later
+ * route has kept room for two points; 3 fewer than two waypoints (device form only).  A route with a non-zero status gets a two-point placeholder, its first and
+ * last waypoint as given, so the CSR stays valid for the corridor kernel; the caller reads the status.
+ *   frx_grid_search_levels        host: the search alone on an occupancy array, as frx_grid_search takes it (3-D only).  The path comes back START first;
+ *                                 *n_path = 0, *levels = -1 when there is none (an occupied start or goal included).  levels, max_level_cells may be NULL.
+ *   frx_route_plan_levels_batch   host, one thread: the whole batch; the referee of the device form.
+ *   frx_route_search_workspace    bytes of scratch the device form needs: per leg cap_pts points, two lists of cap_level cells, cap_raw cells and one label
+ *                                 byte per map cell.  A function of its arguments alone, answered without a device.
+ *   frx_route_plan_batch_device   pure launches on hip_stream of the current device (four kernels: label clear, search and tail, splice offsets, splice): no
+ *                                 copy, no synchronisation, no allocation (capturable).  map is a host struct whose cells point to device memory; every other
+ *                                 pointer is a device pointer.  n_legs = pt_off[n_routes] - pt_off[0] - n_routes; the caller vouches for pt_off.
+ *                                 work_dev holds frx_route_search_workspace bytes and is 8-byte aligned (FRX_ERR_INVALID_ARG otherwise).
+ *   frx_route_plan_batch          blocking, host pointers: upload, the device form, download.
+ * The batch forms report in *n_pts the points all routes need and return FRX_ERR_CAPACITY only when that exceeds cap_total (every output is valid then).
+ * FRX_ERR_INVALID_ARG (reported before a device is looked for): NULL arguments, n_routes < 1, a route with fewer than two waypoints, non-monotone pt_off, a cap
+ * < 1, cap_total < 2 n_routes, res <= 0, a dim <= 0, more than 2^31 - 1 cells.  FRX_ERR_NO_DEVICE without a device (the device forms).  Not built: 2-bit labels, a
+ * search window for very large maps, one leg split over several workgroups, JPS and eps != 1 (frx_grid_search, frx_jps_plan and frx_route_plan keep those). */
+int frx_grid_search_levels(const signed char *cmap, const int *dim, const int *start, const int *goal, int cap, int *n_path, int *path_xyz, int *levels,
+                           int *max_level_cells);
+int frx_route_plan_levels_batch(const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
+                                int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels, int *leg_max_level,
+                                int *n_pts);
+int frx_route_search_workspace(const int *dim, int n_legs, int cap_level, int cap_raw, int cap_pts, size_t *bytes);
+int frx_route_plan_batch_device(const frx_voxel_map *map, int n_routes, int n_legs, const int *pt_off_dev, const double *pts_dev, int cap_level, int cap_raw,
+                                int cap_pts, int cap_total, void *work_dev, int *path_off_dev, double *path_dev, int *route_status_dev, int *leg_status_dev,
+                                int *leg_levels_dev, int *leg_max_level_dev, void *hip_stream);
+int frx_route_plan_batch(int device, const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
+                         int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels, int *leg_max_level, int *n_pts);
 
 /* Asynchronous evaluation on host buffers (blocking and asynchronous variants): frx_objective_eval_async returns once
  * the work is enqueued on the handle's stream, frx_wait completes it and fills f and g (valid until then; one evaluation in flight per
