@@ -14,6 +14,7 @@
 // The label of a cell is one byte, 0 = unlabelled, else 1 + (level mod 3): face neighbours differ by at most one level, so three values tell the level below
 // from the level itself and the level above.  Nothing here is floating point.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -32,6 +33,19 @@ enum { ROUTE_WHOLE = 0, ROUTE_LEG_FAILED = 1, ROUTE_NO_ROOM = 2, ROUTE_NO_POINTS
 
 // the successor order of GridSearch::successors in 3-D
 constexpr int ROUTE_STEP[6][3] = {{-1, 0, 0}, {0, -1, 0}, {0, 0, -1}, {0, 0, 1}, {0, 1, 0}, {1, 0, 0}};
+
+// An end of a leg: waypoint -> cell, or outside.  The quotient is the one of floatToInt (VoxelMap::to_cell); the verdict is taken on the rounded double, before
+// any conversion to int, so a coordinate far beyond the map, infinite or not a number is outside on the host and on the device alike (the conversion of such
+// a double to int is undefined on the host and gives 0, a cell of the map, on the device).  c is written only for an end inside.
+FRX_ROUTE_HD inline bool route_end_cell(const double *origin, double res, const int *dim, const double *p, int *c) {
+    double q[3];                                                                  // a difference, a quotient, a difference: nothing to contract
+    for (int i = 0; i < 3; i++) {
+        q[i] = std::round((p[i] - origin[i]) / res - 0.5);
+        if (!(q[i] >= 0.0 && q[i] < (double)dim[i])) return false;
+    }
+    for (int i = 0; i < 3; i++) c[i] = (int)q[i];
+    return true;
+}
 
 // label bytes of one leg, padded to whole 32-bit words (the device claims a cell with an atomic on the word that holds its byte)
 inline size_t route_label_words(long long n_cells) { return (size_t)((n_cells + 3) / 4); }

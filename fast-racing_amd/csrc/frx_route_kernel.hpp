@@ -2,7 +2,8 @@
 // frx_route_plan, for every leg of every route at once.  Four launches:
 //   k_route_clear         zeroes the label bytes of all legs
 //   k_route_search        one 256-thread workgroup per leg: levels, descent, removeCornerPts twice, removeLinePts, samplePath into the leg's slot
-//   k_route_splice_plan   one workgroup: the points of every route, then - one lane, in route order - its offset and whether it fits
+//   k_route_splice_plan   one workgroup: refuses the batch when a route has no waypoint; the points of every route, then - one lane, in route order - its
+//                         offset and whether it fits
 //   k_route_splice        one workgroup per route: the legs' slots (or the placeholder) into the CSR frx_corridor_generate_batch_device takes
 //
 // The levels.  A cell's label is one byte, 0 or 1 + (level mod 3), four cells to a 32-bit word across row ends.  A lane that finds a traversable neighbour whose
@@ -228,9 +229,9 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route_search(RouteArgs a) {
     if (wp < a.pt_off[lo] || wp + 1 >= a.pt_off[lo + 1]) status = ROUTE_NO_PATH;   // offsets the caller vouched for do not hold this leg
     else {
         const double *ps = a.pts + 3 * (size_t)wp;
-        for (int i = 0; i < 3; i++) { s[i] = route_cell(a, ps[i], i); g[i] = route_cell(a, ps[3 + i], i); }
-        if (!route_inside(a, s[0], s[1], s[2]) || a.cells[sid = route_id(a, s[0], s[1], s[2])] != 0) status = ROUTE_START;
-        else if (!route_inside(a, g[0], g[1], g[2]) || a.cells[gid = route_id(a, g[0], g[1], g[2])] != 0) status = ROUTE_GOAL;
+        // route_end_cell decides on the rounded double: an end far outside or not a number never becomes a cell index
+        if (!route_end_cell(a.origin, a.res, a.dim, ps, s) || a.cells[sid = route_id(a, s[0], s[1], s[2])] != 0) status = ROUTE_START;
+        else if (!route_end_cell(a.origin, a.res, a.dim, ps + 3, g) || a.cells[gid = route_id(a, g[0], g[1], g[2])] != 0) status = ROUTE_GOAL;
     }
     if (status != ROUTE_OK) {                                                     // the same verdict in every lane: nobody reaches a barrier
         if (tid == 0) { a.leg_status[leg] = status; a.leg_levels[leg] = -1; a.leg_max_level[leg] = 0; a.npts[leg] = 0; }
@@ -347,12 +348,24 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route_search(RouteArgs a) {
 
 // The points of every route (all lanes), then the offsets in route order (one lane): path_off[r + 1] carries a route's want between the two.
 __global__ __launch_bounds__(ROUTE_THREADS) void k_route_splice_plan(RouteArgs a) {
+    __shared__ int s_empty;
     const int tid = threadIdx.x, p0 = a.pt_off[0];
+    // A route without a waypoint (or offsets that step back) takes a leg slot away from the routes behind it: first = pt_off[r] - p0 - r is no longer monotone
+    // and the caller's leg arrays hold fewer slots than legs exist.  The batch is refused whole: every route ROUTE_NO_POINTS with its placeholder, every leg
+    // ROUTE_NO_PATH with no points, over whatever k_route_search wrote.
+    if (tid == 0) s_empty = 0;
+    __syncthreads();
+    for (int r = tid; r < a.n_routes; r += ROUTE_THREADS)
+        if (a.pt_off[r + 1] - a.pt_off[r] < 1) s_empty = 1;
+    __syncthreads();
+    const bool refused = s_empty != 0;
+    if (refused)
+        for (int l = tid; l < a.n_legs; l += ROUTE_THREADS) { a.leg_status[l] = ROUTE_NO_PATH; a.leg_levels[l] = -1; a.leg_max_level[l] = 0; a.npts[l] = 0; }
     for (int r = tid; r < a.n_routes; r += ROUTE_THREADS) {
         const int legs = a.pt_off[r + 1] - a.pt_off[r] - 1, first = a.pt_off[r] - p0 - r;
         int st = ROUTE_WHOLE;
         long long want = 0;
-        if (legs < 1 || first < 0 || first + legs > a.n_legs) st = ROUTE_NO_POINTS;
+        if (refused || legs < 1 || first < 0 || first + legs > a.n_legs) st = ROUTE_NO_POINTS;
         else {
             for (int l = 0; l < legs; l++) {
                 if (a.leg_status[first + l] != ROUTE_OK) st = ROUTE_LEG_FAILED;

@@ -691,20 +691,19 @@ void plan_leg(const frx_voxel_map *m, const signed char *cmap, V3 start, V3 goal
     r.sample = sample_path(map, r.path);
 }
 
-// A leg of the level search (frx_route_host.hpp) with plan_leg's tail on the cell centres: the same checks of start and goal, the same three simplification
+// A leg of the level search (frx_route_host.hpp) with plan_leg's tail on the cell centres: the checks of start and goal by route_end_cell, the same three simplification
 // passes and the same sampling, and the three capacities of the device form as statuses.  r.sample holds the leg's points when r.status is 0.
 void plan_leg_levels(const frx_voxel_map *m, V3 start, V3 goal, int cap_level, int cap_raw, int cap_pts, frx::RouteScratch &w, std::vector<int> &raw,
                      LegResult &r, frx::RouteSearchOut &o) {
     VoxelMap map{m};
     o = frx::RouteSearchOut();
     int s[3], g[3];
-    map.to_cell(start, s);
-    if (!map.is_free(s)) {
+    const double ps[3] = {start.x, start.y, start.z}, pg[3] = {goal.x, goal.y, goal.z};
+    if (!frx::route_end_cell(m->origin, m->res, m->dim, ps, s) || m->cells[map.index(s)] != 0) {   // the rule of an end, the device's as well
         r.status = o.status = frx::ROUTE_START;
         return;
     }
-    map.to_cell(goal, g);
-    if (!map.is_free(g)) {
+    if (!frx::route_end_cell(m->origin, m->res, m->dim, pg, g) || m->cells[map.index(g)] != 0) {
         r.status = o.status = frx::ROUTE_GOAL;
         return;
     }

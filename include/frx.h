@@ -300,14 +300,19 @@ int frx_route_plan(const frx_voxel_map *map, const double *start, const double *
  * squared cell distance to the goal (64-bit integers) is smallest, ties in the order -x, -y, -z, +z, +y, +x.  Then frx_jps_plan's tail, the same operations in the
  * same order: removeCornerPts forwards and backwards, removeLinePts, samplePath.  Host and device forms agree bit for bit.
  * Route r has the waypoints pts[pt_off[r] .. pt_off[r + 1]) - start, gates in order, goal - at least two; its legs are the consecutive pairs, all legs of all routes
- * are independent.  Per leg (in route order): leg_status = 0 ok; 1 start not free; 2 goal not free; -1 no path; 3 a level holds more than cap_level cells; 4 the
+ * are independent.  An end of a leg is a cell of the map or outside it, decided on the rounded quotient before it becomes an integer: a coordinate beyond the
+ * map, infinite or not a number is outside, and an end outside is not free.  Per leg (in route order): leg_status = 0 ok; 1 start not free; 2 goal not free; -1 no path; 3 a level holds more than cap_level cells; 4 the
  * raw path holds more than cap_raw cells; 5 more than cap_pts sample points.  leg_levels = the start's level (the raw path holds that many cells plus one), -1
  * when the search did not label the start; leg_max_level = the largest level built, the last one included (level 0 counts).  A failed leg does not disturb any
  * other leg and the call still returns FRX_OK.
  * The routes come back as one CSR in route order, path_off[n_routes + 1] and path[cap_total][3], the layout frx_corridor_generate_batch_device takes: the legs'
  * sample paths with the shared point kept once.  route_status = 0 whole; 1 a leg failed; 2 the route does not fit the room left in cap_total once every later
  * route has kept room for two points; 3 fewer than two waypoints (device form only).  A route with a non-zero status gets a two-point placeholder, its first and
- * last waypoint as given, so the CSR stays valid for the corridor kernel; the caller reads the status.
+ * last waypoint as given, so the CSR stays valid for the corridor kernel; the caller reads the status.  The device form, which cannot refuse what it has not
+ * read: a route of ONE waypoint gets status 3 and that waypoint twice, and no other route is disturbed; a route WITHOUT a waypoint (or offsets that step back)
+ * leaves fewer leg slots than legs, so the whole batch is refused on the device - every route_status 3 with its placeholder (zeros for the route without a
+ * waypoint), every leg_status -1, leg_levels -1, leg_max_level 0 - and every entry of every output is written.  A whole route of one leg whose start and goal
+ * share a cell has ONE point.
  *   frx_grid_search_levels        host: the search alone on an occupancy array, as frx_grid_search takes it (3-D only).  The path comes back START first;
  *                                 *n_path = 0, *levels = -1 when there is none (an occupied start or goal included).  levels, max_level_cells may be NULL.
  *   frx_route_plan_levels_batch   host, one thread: the whole batch; the referee of the device form.

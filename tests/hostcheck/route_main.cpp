@@ -2,10 +2,12 @@
 // definition.  Distances to the goal come from repeated relaxation over the whole grid until nothing changes; then every property of the path is checked: it
 // starts at the start, ends at the goal, moves by face neighbours through traversable cells, holds distance + 1 cells, and each step is the neighbour one level
 // down with the smallest squared distance to the goal, first in the order -x, -y, -z, +z, +y, +x.  The level sizes, the three verdicts of the capacities and the
-// workspace layout are checked as well.  Host code only: a program of its own, never loaded into Python and never run on a GPU machine
-// (make -C fast-racing_amd/csrc route_san && tests/hostcheck/route_san).
+// workspace layout are checked as well, and the rule of a leg's end (route_end_cell) on inputs far outside, infinite and not a number.  Host code only: a
+// program of its own, never loaded into Python and never run on a GPU machine (make -C fast-racing_amd/csrc route_san && tests/hostcheck/route_san).
 #include <cstdio>
+#include <cmath>
 #include <cstdlib>
+#include <limits>
 #include <random>
 #include <vector>
 
@@ -124,6 +126,52 @@ void workspace() {
     CHECK(frx::route_points(3, n3) == 8 && frx::route_fits(10, 8, 1, 20) && !frx::route_fits(10, 8, 1, 19), "splice bookkeeping");
 }
 
+// The rule of a leg's end (route_end_cell): where floatToInt's conversion is defined (a rounded quotient that an int holds) the verdict and the cell are
+// floatToInt's; far beyond the map, infinite and not a number are outside, without a conversion the sanitizer could object to.
+void ends() {
+    const double origin[3] = {-1.2, -2.0, 0.5}, res = 0.1;
+    const int dim[3] = {24, 40, 6};
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const double inside[3] = {0.03, 0.41, 0.77};
+    int c[3] = {-9, -9, -9};
+    CHECK(frx::route_end_cell(origin, res, dim, inside, c) && c[0] == 12 && c[1] == 24 && c[2] == 2, "inside: %d %d %d", c[0], c[1], c[2]);
+    std::mt19937 rng(7u);
+    std::uniform_real_distribution<double> u(-1.0, 1.0);
+    for (int t = 0; t < 20000; t++) {                                             // around the map and a little beyond every face: the defined conversions
+        double p[3];
+        int want[3];
+        bool in = true;
+        for (int i = 0; i < 3; i++) {
+            p[i] = origin[i] + res * dim[i] * (0.5 + 0.6 * u(rng));
+            if (t % 7 == 0) p[i] = origin[i] + res * (double)(int)(rng() % (unsigned)(dim[i] + 3)) - res;   // on cell faces, one cell out included
+            want[i] = (int)std::round((p[i] - origin[i]) / res - 0.5);
+            in = in && want[i] >= 0 && want[i] < dim[i];
+        }
+        int got[3] = {-9, -9, -9};
+        const bool ok = frx::route_end_cell(origin, res, dim, p, got);
+        CHECK(ok == in, "verdict at %.17g %.17g %.17g", p[0], p[1], p[2]);
+        if (ok && in) CHECK(got[0] == want[0] && got[1] == want[1] && got[2] == want[2], "cell at %.17g %.17g %.17g", p[0], p[1], p[2]);
+        if (!ok) CHECK(got[0] == -9 && got[1] == -9 && got[2] == -9, "an end outside leaves the cell alone");
+    }
+    const double far[] = {1e6, -1e6, 3e9, -3e9, 1e19, -1e19, 1e300, -1e300, inf, -inf, nan, -nan};
+    for (const double v : far)
+        for (int axis = 0; axis < 3; axis++) {
+            double p[3] = {inside[0], inside[1], inside[2]};
+            p[axis] = v;
+            int got[3] = {-9, -9, -9};
+            CHECK(!frx::route_end_cell(origin, res, dim, p, got) && got[0] == -9 && got[1] == -9 && got[2] == -9, "%g on axis %d is outside", v, axis);
+        }
+    // one cell beyond dim - 1 on x, where x + dim[0] * y would still index the array
+    const double wrap[3] = {origin[0] + res * (dim[0] + 0.5), origin[1] + res * 3.5, origin[2] + res * 1.5};
+    CHECK(!frx::route_end_cell(origin, res, dim, wrap, c), "beyond the last cell of a row");
+    // a quarter cell beyond either outer face rounds to -1 and to dim (outside); just inside the low face the quotient rounds to -0.0, which is cell 0
+    const double lo[3] = {origin[0] - 0.25 * res, inside[1], inside[2]}, hi[3] = {origin[0] + res * (dim[0] + 0.25), inside[1], inside[2]};
+    const double lo_in[3] = {origin[0] + 1e-9, inside[1], inside[2]}, hi_in[3] = {origin[0] + res * (dim[0] - 0.25), inside[1], inside[2]};
+    CHECK(!frx::route_end_cell(origin, res, dim, lo, c) && !frx::route_end_cell(origin, res, dim, hi, c), "beyond the outer faces");
+    CHECK(frx::route_end_cell(origin, res, dim, lo_in, c) && c[0] == 0, "just inside the low face: %d", c[0]);
+    CHECK(frx::route_end_cell(origin, res, dim, hi_in, c) && c[0] == dim[0] - 1, "just inside the high face: %d", c[0]);
+}
+
 } // namespace
 
 int main() {
@@ -131,6 +179,7 @@ int main() {
     frx::RouteScratch w;
     for (int m = 0; m < 1500; m++) one_map(rng, w);
     workspace();
+    ends();
     if (failures) { std::printf("route_san: %d checks FAILED\n", failures); return 1; }
     std::printf("route_san: ok\n");
     return 0;

@@ -2,7 +2,10 @@
 
 Levels: numpy, whole level by whole level, on an array of integer levels (the library keeps 1 + level mod 3 in a byte).  Descent: the face neighbour one level
 down whose squared cell distance to the goal is smallest, ties in the order -x, -y, -z, +z, +y, +x.  The tail is the oracle's restatement of the reference's
-removeCornerPts, removeLinePts and samplePath (oracle/jps_oracle.py), the splice is frx_route_plan's: the shared point once."""
+removeCornerPts, removeLinePts and samplePath (oracle/jps_oracle.py), the splice is frx_route_plan's: the shared point once.  An end of a leg becomes a cell by
+route_end_cell's rule (end_cell).  For the crafted states (route_states.py): the samples of an edge as samplePath's accumulated d counts them (edge_samples), and
+a log of every chord the corner passes walk, with its max_diff and its first blocked sample (leg_log)."""
+import math
 import os
 import sys
 
@@ -11,7 +14,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-from oracle.jps_oracle import Map, remove_corner_pts, remove_line_pts, sample_path  # noqa: E402
+from oracle.jps_oracle import Map, c_round, remove_corner_pts, remove_line_pts, sample_path  # noqa: E402
 
 STEPS = ((-1, 0, 0), (0, -1, 0), (0, 0, -1), (0, 0, 1), (0, 1, 0), (1, 0, 0))
 OK, START, GOAL, NO_PATH, CAP_LEVEL, CAP_RAW, CAP_PTS = 0, 1, 2, -1, 3, 4, 5
@@ -61,13 +64,28 @@ def level_search(cells, dim, start, goal, cap_level=None, cap_raw=None):
     return OK, path, level, max_cells
 
 
+def end_cell(m: Map, p):
+    """route_end_cell of csrc/frx_route_host.hpp: the cell of a leg's end, or None for an end outside the map.  The verdict is taken on the rounded quotient
+    as a number, never on a converted int: beyond the map, infinite and not a number are outside.  Inside the map the cell is Map.float_to_int's."""
+    c = []
+    for i in range(3):
+        q = (p[i] - m.origin[i]) / m.res - 0.5
+        if not math.isfinite(q):
+            return None
+        r = c_round(q)                                                                             # a Python integer: no range to leave
+        if r < 0 or r >= m.dim[i]:
+            return None
+        c.append(r)
+    return c
+
+
 def plan_leg(m: Map, start, goal, cap_level=None, cap_raw=None, cap_pts=None):
-    """(status, sample points as an (n, 3) array, levels, max_level_cells) of one leg: plan_leg of frx_search.cpp on the level search."""
-    s = m.float_to_int(start)
-    if not m.is_free(s):
+    """(status, sample points as an (n, 3) array, levels, max_level_cells) of one leg: plan_leg_levels of frx_search.cpp on the level search."""
+    s = end_cell(m, start)
+    if s is None or not m.is_free(s):
         return START, np.zeros((0, 3)), -1, 0
-    g = m.float_to_int(goal)
-    if not m.is_free(g):
+    g = end_cell(m, goal)
+    if g is None or not m.is_free(g):
         return GOAL, np.zeros((0, 3)), -1, 0
     st, cells, levels, mx = level_search(m.cells, m.dim, s, g, cap_level, cap_raw)
     if st != OK:
@@ -180,6 +198,71 @@ def simplified_path(m: Map, start, goal):
 def walk_samples(m: Map, a, b):
     """max_diff of the sight-line walk from a to b (Map.ray_trace): the walk takes max_diff - 1 samples"""
     return int(max(abs((b[i] - a[i]) / m.res) for i in range(3)) / 0.8)
+
+
+def edge_samples(p1, p2):
+    """The samples samplePath takes on the edge p1 -> p2: its d accumulates 0.02 (it is not i * 0.02) for as long as d <= |p2 - p1|."""
+    l = math.sqrt((p2[0] - p1[0]) ** 2 + (p2[1] - p1[1]) ** 2 + (p2[2] - p1[2]) ** 2)
+    d, n = 0.0, 0
+    while d <= l:
+        n += 1
+        d += 0.02
+    return n
+
+
+def walk_first_hit(m: Map, a, b, val=100):
+    """(max_diff, the number n of the first sample of the sight-line walk a -> b on a cell >= val, or None): Map.ray_trace sample for sample, stopped at the
+    first sample outside the map.  The walk's de-duplication of repeated cells cannot change the first hit."""
+    diff = [b[i] - a[i] for i in range(3)]
+    max_diff = int(max(abs(d / m.res) for d in diff) / 0.8)
+    if max_diff == 0:
+        return 0, None
+    s = 1.0 / max_diff
+    step = [d * s for d in diff]
+    for n in range(1, max_diff):
+        c = m.float_to_int([a[i] + step[i] * n for i in range(3)])
+        if m.outside(c):
+            break
+        if m.cells[m.index(c)] >= val:
+            return max_diff, n
+    return max_diff, None
+
+
+def corner_pass_logged(m: Map, path, log):
+    """remove_corner_pts of the oracle, statement for statement, appending (a, b, max_diff, first blocked sample or None) to `log` for every chord it walks"""
+    def cost(a, b):
+        md, hit = walk_first_hit(m, a, b)
+        log.append((a, b, md, hit))
+        return math.inf if hit is not None else math.sqrt((a[0] - b[0]) ** 2 + (a[1] - b[1]) ** 2 + (a[2] - b[2]) ** 2)
+    if len(path) < 2:
+        return list(path)
+    out = [path[0]]; prev = path[0]
+    cost1 = cost(path[0], path[1])
+    for i in range(1, len(path) - 1):
+        p1, p2 = path[i], path[i + 1]
+        cost2 = cost(p1, p2)
+        cost3 = cost(prev, p2)
+        if cost3 < cost1 + cost2:
+            cost1 = cost3
+        else:
+            out.append(p1); cost1 = math.sqrt((p1[0] - p2[0]) ** 2 + (p1[1] - p2[1]) ** 2 + (p1[2] - p2[2]) ** 2); prev = p1
+    out.append(path[-1])
+    return out
+
+
+def leg_log(m: Map, start, goal):
+    """dict(raw, path, samples, chords) of one leg that the search finds: the raw cell centres, the vertices after the three passes, the sample points and
+    the chords both corner passes walked.  The logged passes are held to the oracle's own (remove_corner_pts) here, vertex for vertex."""
+    st, cells, _, _ = level_search(m.cells, m.dim, m.float_to_int(start), m.float_to_int(goal))
+    assert st == OK, st
+    raw = [m.int_to_float(c) for c in cells]
+    chords = []
+    q = corner_pass_logged(m, raw, chords)
+    assert q == remove_corner_pts(m, raw)
+    back = corner_pass_logged(m, q[::-1], chords)
+    assert back == remove_corner_pts(m, q[::-1])
+    path = remove_line_pts(back[::-1])
+    return dict(raw=raw, path=path, samples=np.array(sample_path(m, path), dtype=np.float64).reshape(-1, 3), chords=chords)
 
 
 def same_bits(a, b):

@@ -27,11 +27,12 @@ def assert_same(got, want, label=""):
     assert got["need"] == want["need"] and got["fits"] == want["fits"], label
 
 
-def device_form(frx, vm, routes, cap_level, cap_raw, cap_pts, cap_total, stream=0, launch=None, repeat=1, keep=None):
+def device_form(frx, vm, routes, cap_level, cap_raw, cap_pts, cap_total, stream=0, launch=None, repeat=1, keep=None, packed=None, min_pts=2):
     """The outputs of the device form as route_batch_host lays them out; outputs and scratch are pre-filled with a sentinel and nothing is written behind either
-    at the sizes the entry was given.  launch(call) runs the enqueueing call (default: directly), `repeat` times into the same buffers."""
-    off, pts = frx.pack_routes(routes)
-    R, NL = len(routes), int(off[-1]) - len(routes)
+    at the sizes the entry was given.  launch(call) runs the enqueueing call (default: directly), `repeat` times into the same buffers.  packed: (pt_off, pts)
+    where the offsets are not frx.pack_routes' (they may begin above 0); min_pts: 1 where a whole route of one one-cell leg is one point."""
+    off, pts = packed if packed is not None else frx.pack_routes(routes)
+    R, NL = len(routes), int(off[-1]) - int(off[0]) - len(routes)
     nbytes = frx.route_search_workspace(vm.dim, NL, cap_level, cap_raw, cap_pts)
     host = dict(work=np.full(nbytes // 4 + PAD, ISENT, np.int32), path_off=np.full(R + 1 + PAD, ISENT, np.int32), path=np.full(3 * cap_total + PAD, SENTINEL),
                 rst=np.full(R + PAD, ISENT, np.int32), lst=np.full(NL + PAD, ISENT, np.int32), lev=np.full(NL + PAD, ISENT, np.int32),
@@ -52,7 +53,7 @@ def device_form(frx, vm, routes, cap_level, cap_raw, cap_pts, cap_total, stream=
             for k, n in (("path_off", R + 1), ("rst", R), ("lst", NL), ("lev", NL), ("mx", NL)):
                 assert (g[k][n:] == ISENT).all(), k
             po = g["path_off"][:R + 1]
-            assert po[0] == 0 and (np.diff(po) >= 2).all() and po[-1] <= cap_total and (g["path"][3 * po[-1]:] == SENTINEL).all()
+            assert po[0] == 0 and (np.diff(po) >= min_pts).all() and po[-1] <= cap_total and (g["path"][3 * po[-1]:] == SENTINEL).all()
             got = dict(path_off=po, path=g["path"][:3 * po[-1]].reshape(-1, 3), route_status=g["rst"][:R], leg_status=g["lst"][:NL], levels=g["lev"][:NL],
                        max_level_cells=g["mx"][:NL])
             assert out is None or all(np.array_equal(out[k].view(np.uint8), got[k].view(np.uint8)) for k in got)   # run to run
