@@ -1,12 +1,11 @@
-// C ABI (include/frx.h) of the MI355X back-end: problem set-up, batched device evaluation, the trajectory
-// entries and the self-tests; the plan drivers behind frx_optimize live in frx_optimize.cpp.  Host-only translation
-// unit (g++); the kernels live in frx_device.hip.  No CPU fallback: without a HIP device create() fails.
+// C ABI (include/frx.h) of the MI355X back-end: problem set-up, batched device evaluation, the penalty on its own and the
+// self-tests; the plan drivers behind frx_optimize live in frx_optimize.cpp, the trajectory entries in frx_traj.cpp.  Host-only
+// translation unit (g++); the kernels live in frx_device.hip.  No CPU fallback: without a HIP device create() fails.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,13 +17,10 @@
 #include "../../include/frx.h"
 #include "../../include/frx_debug.h"
 #include "frx_handle.hpp"
-#include "frx_batch_host.hpp"
 #include "frx_launch_forms.hpp"
 #include "frx_problem_tables.hpp"
 #include "frx_host_pool.hpp"
 #include "frx_compact.hpp"
-#include "frx_traj_fold.hpp"
-#include "frx_gate_host.hpp"
 
 using frx::NumaScope;
 
@@ -278,8 +274,7 @@ int frx_problem_create(const frx_config *cfg, int device, int B, const int *coar
     if (cfg->qd_intervals < 1) return fail(FRX_ERR_INVALID_ARG, "qd_intervals must be >= 1");
     *out = nullptr;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return frx::no_device();
     if (device < 0 || device >= ndev) return fail(FRX_ERR_INVALID_ARG, "device ordinal out of range");
     if (hipSetDevice(device) != hipSuccess) return fail(FRX_ERR_NO_DEVICE, "hipSetDevice failed");
 
@@ -765,26 +760,8 @@ int frx_penalty_eval_device(frx_problem *p, const double *T_dev, const double *C
     return FRX_OK;
 }
 
-// The blocking entries that take (T, C) from the host - penalty, check, extrema, contain, clearance, sample - run: argument checks, stage_TC ((T, C) -> d_T, d_C through the
-// pinned h_T, h_C), their _device entry on the handle's stream, fetch_rows, then a fold on the host (frx_traj_fold.hpp for the four that have candidate rows).
-static int stage_TC(frx_problem *p, const double *T, const double *C) {
-    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
-    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
-    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
-    return FRX_OK;
-}
-// n <= 20 P doubles of piece rows -> h_out20, complete on return; piece_out, when given, gets a copy
-static int fetch_rows(frx_problem *p, const double *d_rows, size_t n, double *piece_out) {
-    HIP_TRY(hipMemcpyAsync(p->h_out20.p, d_rows, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (piece_out) std::memcpy(piece_out, p->h_out20.p, sizeof(double) * n);
-    return FRX_OK;
-}
-// a scratch buffer that grows to `need` doubles
-static int grow(DevBuf<double> &buf, size_t need, const char *entry) { return buf.n < need ? dev_alloc(buf, need, entry) : FRX_OK; }
-#define FRX_TRY(expr) do { const int rc_ = (expr); if (rc_ != FRX_OK) return rc_; } while (0)
-
+// The blocking penalty takes (T, C) from the host the way the trajectory entries do (frx_traj.cpp): stage_TC, its _device entry on the handle's stream, fetch_rows
+// (frx_handle.hpp), then the sum over each candidate's pieces.
 int frx_penalty_eval(frx_problem *p, const double *T, const double *C, double *cost, double *gdT, double *gdC) {
     if (!p || !T || !C || !cost || !gdT || !gdC) return fail(FRX_ERR_INVALID_ARG, "null argument");
     HIP_TRY(hipSetDevice(p->device));
@@ -802,361 +779,6 @@ int frx_penalty_eval(frx_problem *p, const double *T, const double *C, double *c
         }
         cost[b] += s;
     }
-    return FRX_OK;
-}
-
-int frx_trajectory_check_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, double *piece_out_dev, void *hip_stream) {
-    if (!p || !T_dev || !C_dev || !piece_out_dev) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
-    int lpp = 0, ppw = 0;
-    if (!frx::check_geometry(intervals, p->Kmax, &lpp, &ppw)) return fail(FRX_ERR_CAPACITY, "frx_trajectory_check: a corridor block of " + std::to_string(p->Kmax) + " half-spaces exceeds a wave's LDS");
-    HIP_TRY((hipError_t)frx::launch_check(p->dp, p->Kmax, T_dev, C_dev, intervals, piece_out_dev, hip_stream));
-    return FRX_OK;
-}
-
-int frx_trajectory_check(frx_problem *p, const double *T, const double *C, int intervals, double *piece_out, double *cand_out, unsigned *flags) {
-    if (!p || !T || !C || !cand_out) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
-    HIP_TRY(hipSetDevice(p->device));
-    if (!p->d_check.p) HIP_TRY(p->d_check.alloc((size_t)p->P * FRX_CHECK_FIELDS));
-    FRX_TRY(stage_TC(p, T, C));
-    FRX_TRY(frx_trajectory_check_device(p, p->d_T.p, p->d_C.p, intervals, p->d_check.p, p->stream));
-    FRX_TRY(fetch_rows(p, p->d_check.p, (size_t)FRX_CHECK_FIELDS * p->P, piece_out));
-    const double lim[4] = {p->cfg.vel_max, p->cfg.thr_acc_min, p->cfg.thr_acc_max, p->cfg.body_rate_max};
-    frx::fold_check(p->B, p->poff.data(), T, p->h_out20.p, lim, cand_out, flags);
-    return FRX_OK;
-}
-
-int frx_trajectory_extrema_device(frx_problem *p, const double *T_dev, const double *C_dev, double *piece_out_dev, void *hip_stream) {
-    if (!p || !T_dev || !C_dev || !piece_out_dev) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    HIP_TRY((hipError_t)frx::launch_extrema(p->P, p->dp.pc.gAcc, T_dev, C_dev, piece_out_dev, hip_stream));
-    return FRX_OK;
-}
-
-int frx_trajectory_extrema(frx_problem *p, const double *T, const double *C, double *piece_out, double *cand_out, unsigned *flags) {
-    static_assert(FRX_EXTREMA_FIELDS == (int)frx::EXTREMA_FIELDS && FRX_EXTREMA_FIELDS <= 20, "the rows fit the P x 20 staging");
-    if (!p || !T || !C || !cand_out) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t n_rows = (size_t)FRX_EXTREMA_FIELDS * p->P;
-    if (!p->d_extrema.p) HIP_TRY(p->d_extrema.alloc(n_rows));
-    FRX_TRY(stage_TC(p, T, C));
-    FRX_TRY(frx_trajectory_extrema_device(p, p->d_T.p, p->d_C.p, p->d_extrema.p, p->stream));
-    FRX_TRY(fetch_rows(p, p->d_extrema.p, n_rows, piece_out));
-    const double lim[4] = {p->cfg.vel_max, p->cfg.thr_acc_min, p->cfg.thr_acc_max, p->cfg.body_rate_max};
-    frx::fold_extrema(p->B, p->poff.data(), T, p->h_out20.p, lim, cand_out, flags);
-    return FRX_OK;
-}
-
-int frx_gate_from_corners(int n, const double *corners, double *gates, double *fit) {
-    if (n < 1 || !corners || !gates) return fail(FRX_ERR_INVALID_ARG, "frx_gate_from_corners: n must be >= 1 and corners, gates not NULL");
-    frx::gate_from_corners(n, corners, gates, fit);
-    return FRX_OK;
-}
-
-// gate_off of B candidates: starts at 0 and never falls
-static int gate_off_args(int B, const int *gate_off) {
-    if (gate_off[0] != 0) return fail(FRX_ERR_INVALID_ARG, "gate_off[0] must be 0");
-    for (int b = 0; b < B; b++)
-        if (gate_off[b + 1] < gate_off[b]) return fail(FRX_ERR_INVALID_ARG, "gate_off must not fall (candidate " + std::to_string(b) + ")");
-    return FRX_OK;
-}
-
-int frx_gate_flags(int B, const int *gate_off, const double *gate_rows, unsigned *flags) {
-    if (B < 1 || !gate_off || !gate_rows || !flags) return fail(FRX_ERR_INVALID_ARG, "frx_gate_flags: B must be >= 1 and no argument NULL");
-    FRX_TRY(gate_off_args(B, gate_off));
-    frx::gate_flags(B, gate_off, gate_rows, flags);
-    return FRX_OK;
-}
-
-int frx_trajectory_gates_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_gates, const int *gate_off_dev, const double *gates_dev,
-                                double *gate_out_dev, void *hip_stream) {
-    static_assert(FRX_GATE_FIELDS == (int)frx::GATE_FIELDS, "frx.h and frx_device.hpp agree");
-    if (!p || !T_dev || !C_dev || !gate_off_dev || !gates_dev || !gate_out_dev) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (n_gates < 1) return fail(FRX_ERR_INVALID_ARG, "n_gates must be >= 1");
-    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    HIP_TRY((hipError_t)frx::launch_gates(p->B, p->dp.poff, p->dp.pc.gAcc, p->dp.pc.ell, T_dev, C_dev, n_gates, gate_off_dev, gates_dev, gate_out_dev, hip_stream));
-    return FRX_OK;
-}
-
-int frx_trajectory_gates(frx_problem *p, const double *T, const double *C, const int *gate_off, const double *gates, double *gate_out, unsigned *flags) {
-    if (!p || !T || !C || !gate_off || !gates || !gate_out) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    FRX_TRY(gate_off_args(p->B, gate_off));
-    const int n_gates = gate_off[p->B];
-    if (n_gates < 1) return fail(FRX_ERR_INVALID_ARG, "frx_trajectory_gates: no gates (gate_off[B] < 1)");
-    HIP_TRY(hipSetDevice(p->device));
-    // one buffer: the rows [n_gates][10], the records [n_gates][9], then gate_off as B + 1 ints
-    const size_t n_rows = (size_t)FRX_GATE_FIELDS * n_gates, n_rec = 9 * (size_t)n_gates, n_off = ((size_t)p->B + 2) / 2;
-    FRX_TRY(grow(p->d_gates, n_rows + n_rec + n_off, "frx_trajectory_gates"));
-    double *d_rows = p->d_gates.p, *d_rec = d_rows + n_rows;
-    int *d_off = (int *)(d_rec + n_rec);
-    FRX_TRY(stage_TC(p, T, C));
-    HIP_TRY(hipMemcpyAsync(d_rec, gates, sizeof(double) * n_rec, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(d_off, gate_off, sizeof(int) * ((size_t)p->B + 1), hipMemcpyHostToDevice, p->stream));
-    FRX_TRY(frx_trajectory_gates_device(p, p->d_T.p, p->d_C.p, n_gates, d_off, d_rec, d_rows, p->stream));
-    HIP_TRY(hipMemcpyAsync(gate_out, d_rows, sizeof(double) * n_rows, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (flags) frx::gate_flags(p->B, gate_off, gate_out, flags);
-    return FRX_OK;
-}
-
-int frx_contain_fold(int B, const int *piece_off, const double *T, const double *rows, double *cand_out, unsigned *flags) {
-    if (B < 1 || !piece_off || !T || !rows) return fail(FRX_ERR_INVALID_ARG, "frx_contain_fold: B must be >= 1 and piece_off, T, rows not NULL");
-    if (piece_off[0] < 0) return fail(FRX_ERR_INVALID_ARG, "frx_contain_fold: piece_off[0] must be >= 0");
-    for (int b = 0; b < B; b++)
-        if (piece_off[b + 1] < piece_off[b]) return fail(FRX_ERR_INVALID_ARG, "frx_contain_fold: piece_off must not fall (candidate " + std::to_string(b) + ")");
-    frx::fold_contain(B, piece_off, T, rows, cand_out, flags);
-    return FRX_OK;
-}
-
-int frx_trajectory_contain_device(frx_problem *p, const double *T_dev, const double *C_dev, double slack, double *piece_out_dev, void *hip_stream) {
-    static_assert(FRX_CONTAIN_FIELDS == (int)frx::CONTAIN_FIELDS && FRX_CONTAIN_FIELDS <= 20, "frx.h and frx_device.hpp agree, and the rows fit the P x 20 staging");
-    if (!p || !T_dev || !C_dev || !piece_out_dev) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (!std::isfinite(slack)) return fail(FRX_ERR_INVALID_ARG, "slack must be finite");
-    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    HIP_TRY((hipError_t)frx::launch_contain(p->dp, p->Kmax, slack, T_dev, C_dev, piece_out_dev, hip_stream));
-    return FRX_OK;
-}
-
-int frx_trajectory_contain(frx_problem *p, const double *T, const double *C, double slack, double *piece_out, double *cand_out, unsigned *flags) {
-    if (!p || !T || !C || !cand_out) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (!std::isfinite(slack)) return fail(FRX_ERR_INVALID_ARG, "slack must be finite");
-    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t n_rows = (size_t)FRX_CONTAIN_FIELDS * p->P;
-    if (!p->d_contain.p) HIP_TRY(p->d_contain.alloc(n_rows));
-    FRX_TRY(stage_TC(p, T, C));
-    FRX_TRY(frx_trajectory_contain_device(p, p->d_T.p, p->d_C.p, slack, p->d_contain.p, p->stream));
-    FRX_TRY(fetch_rows(p, p->d_contain.p, n_rows, piece_out));
-    frx::fold_contain(p->B, p->poff.data(), T, p->h_out20.p, cand_out, flags);
-    return FRX_OK;
-}
-
-// argument rules of every form of frx_trajectory_clearance, checked before the handle is read; then the split of the cloud
-static int clear_args(frx_problem *p, const void *T, const void *C, int intervals, int n_obs, const void *obs, const void *out, int *chunk, int *nchunks) {
-    if (!p || !T || !C || !obs || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
-    if (n_obs < 1 || n_obs > FRX_CLEAR_MAX_POINTS) return fail(FRX_ERR_INVALID_ARG, "n_obs must lie in 1.." + std::to_string(FRX_CLEAR_MAX_POINTS));
-    if (!frx::clear_geometry(p->P, n_obs, p->clear_chunk, chunk, nchunks))
-        return fail(FRX_ERR_CAPACITY, "frx_trajectory_clearance: " + std::to_string(p->P) + " pieces x the cloud's chunks exceed a grid");
-    return FRX_OK;
-}
-
-int frx_trajectory_clearance_workspace(frx_problem *p, int intervals, int n_obs, size_t *bytes) {
-    int chunk = 0, nchunks = 0;
-    const int rc = clear_args(p, bytes, bytes, intervals, n_obs, bytes, bytes, &chunk, &nchunks);
-    if (rc != FRX_OK) return rc;
-    *bytes = nchunks > 1 ? sizeof(double) * FRX_CLEAR_FIELDS * (size_t)p->P * (size_t)nchunks : 0;   // one chunk: the kernel writes the rows itself
-    return FRX_OK;
-}
-
-int frx_trajectory_clearance_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, int n_obs, const double *obs_dev, void *work_dev,
-                                    double *piece_out_dev, void *hip_stream) {
-    int chunk = 0, nchunks = 0;
-    const int rc = clear_args(p, T_dev, C_dev, intervals, n_obs, obs_dev, piece_out_dev, &chunk, &nchunks);
-    if (rc != FRX_OK) return rc;
-    if (nchunks > 1 && !work_dev) return fail(FRX_ERR_INVALID_ARG, "work_dev is NULL and frx_trajectory_clearance_workspace asks for scratch");
-    HIP_TRY((hipError_t)frx::launch_clear(p->dp, T_dev, C_dev, intervals, n_obs, obs_dev, chunk, nchunks, (double *)work_dev, piece_out_dev, hip_stream));
-    return FRX_OK;
-}
-
-int frx_trajectory_clearance(frx_problem *p, const double *T, const double *C, int intervals, int n_obs, const double *obs, double *piece_out, double *cand_out,
-                             unsigned *flags) {
-    int chunk = 0, nchunks = 0;
-    FRX_TRY(clear_args(p, T, C, intervals, n_obs, obs, cand_out, &chunk, &nchunks));
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t n_rows = (size_t)FRX_CLEAR_FIELDS * p->P, n_cloud = 3 * (size_t)n_obs, n_work = nchunks > 1 ? n_rows * (size_t)nchunks : 0;
-    FRX_TRY(grow(p->d_clear, n_rows + n_cloud + n_work, "frx_trajectory_clearance"));
-    p->clx_last_work = nullptr;                                              // (the buffer is laid out anew: the exact form's partials in it are gone)
-    double *d_rows = p->d_clear.p, *d_obs = d_rows + n_rows, *d_work = n_work ? d_obs + n_cloud : nullptr;
-    FRX_TRY(stage_TC(p, T, C));
-    HIP_TRY(hipMemcpyAsync(d_obs, obs, sizeof(double) * n_cloud, hipMemcpyHostToDevice, p->stream));
-    FRX_TRY(frx_trajectory_clearance_device(p, p->d_T.p, p->d_C.p, intervals, n_obs, d_obs, d_work, d_rows, p->stream));
-    FRX_TRY(fetch_rows(p, d_rows, n_rows, piece_out));
-    frx::fold_clearance(p->B, p->poff.data(), T, p->h_out20.p, nullptr, cand_out, flags);
-    return FRX_OK;
-}
-
-// Tests: points > 0 makes every later clearance call on the handle split the cloud into chunks of that many points (the last one shorter), whatever the
-// number of pieces; 0 returns to the library's own split.  The workspace query follows it.
-int frx_debug_set_clear_chunk(frx_problem *p, int points) {
-    if (!p || points < 0) return fail(FRX_ERR_INVALID_ARG, "null handle or a negative chunk");
-    p->clear_chunk = points;
-    return FRX_OK;
-}
-
-int frx_clearance_exact_fold(int B, const int *piece_off, const double *T, const double *rows, double *cand_out, unsigned *flags) {
-    if (B < 1 || !piece_off || !T || !rows) return fail(FRX_ERR_INVALID_ARG, "frx_clearance_exact_fold: B must be >= 1 and piece_off, T, rows not NULL");
-    if (piece_off[0] < 0) return fail(FRX_ERR_INVALID_ARG, "frx_clearance_exact_fold: piece_off[0] must be >= 0");
-    for (int b = 0; b < B; b++)
-        if (piece_off[b + 1] < piece_off[b]) return fail(FRX_ERR_INVALID_ARG, "frx_clearance_exact_fold: piece_off must not fall (candidate " + std::to_string(b) + ")");
-    frx::fold_clearance_exact(B, piece_off, T, rows, cand_out, flags);
-    return FRX_OK;
-}
-
-// argument rules of every form of frx_trajectory_clearance_exact, checked before a device is looked for and before the handle is read; then the split of the cloud
-static int clear_exact_args(frx_problem *p, const void *T, const void *C, int n_obs, const void *obs, const void *work, const void *out, int *chunk, int *nchunks) {
-    static_assert(FRX_CLEAR_EXACT_FIELDS == (int)frx::CLEAR_EXACT_FIELDS && FRX_CLEAR_EXACT_FIELDS <= 20, "frx.h and frx_device.hpp agree, and the rows fit the P x 20 staging");
-    if (!p || !T || !C || !obs || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (!work) return fail(FRX_ERR_INVALID_ARG, "work_dev is NULL: frx_trajectory_clearance_exact_workspace says how much scratch the launches need");
-    if (n_obs < 1 || n_obs > FRX_CLEAR_MAX_POINTS) return fail(FRX_ERR_INVALID_ARG, "n_obs must lie in 1.." + std::to_string(FRX_CLEAR_MAX_POINTS));
-    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (!frx::clear_exact_geometry(p->P, n_obs, p->clx_chunk, chunk, nchunks))
-        return fail(FRX_ERR_CAPACITY, "frx_trajectory_clearance_exact: " + std::to_string(p->P) + " pieces x the cloud's chunks exceed a grid");
-    return FRX_OK;
-}
-
-int frx_trajectory_clearance_exact_workspace(frx_problem *p, int n_obs, size_t *bytes) {
-    int chunk = 0, nchunks = 0;
-    const int rc = clear_exact_args(p, bytes, bytes, n_obs, bytes, bytes, bytes, &chunk, &nchunks);
-    if (rc != FRX_OK) return rc;
-    *bytes = sizeof(double) * frx::CLEAR_EXACT_PARTIAL * (size_t)p->P * (size_t)nchunks;
-    return FRX_OK;
-}
-
-int frx_trajectory_clearance_exact_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_obs, const double *obs_dev, void *work_dev,
-                                          double *piece_out_dev, void *hip_stream) {
-    int chunk = 0, nchunks = 0;
-    const int rc = clear_exact_args(p, T_dev, C_dev, n_obs, obs_dev, work_dev, piece_out_dev, &chunk, &nchunks);
-    if (rc != FRX_OK) return rc;
-    HIP_TRY((hipError_t)frx::launch_clear_exact(p->dp, T_dev, C_dev, n_obs, obs_dev, chunk, nchunks, p->clx_cull, (double *)work_dev, piece_out_dev, hip_stream));
-    p->clx_last_work = (const double *)work_dev; p->clx_last_nchunks = nchunks;
-    return FRX_OK;
-}
-
-int frx_trajectory_clearance_exact(frx_problem *p, const double *T, const double *C, int n_obs, const double *obs, double *piece_out, double *cand_out,
-                                   unsigned *flags) {
-    int chunk = 0, nchunks = 0;
-    FRX_TRY(clear_exact_args(p, T, C, n_obs, obs, obs, cand_out, &chunk, &nchunks));
-    HIP_TRY(hipSetDevice(p->device));
-    // the handle's cloud buffer, as the dense form lays it out: the rows, the cloud, then the partials
-    const size_t n_rows = (size_t)FRX_CLEAR_EXACT_FIELDS * p->P, n_cloud = 3 * (size_t)n_obs, n_work = (size_t)frx::CLEAR_EXACT_PARTIAL * p->P * (size_t)nchunks;
-    FRX_TRY(grow(p->d_clear, n_rows + n_cloud + n_work, "frx_trajectory_clearance_exact"));
-    double *d_rows = p->d_clear.p, *d_obs = d_rows + n_rows, *d_work = d_obs + n_cloud;
-    FRX_TRY(stage_TC(p, T, C));
-    HIP_TRY(hipMemcpyAsync(d_obs, obs, sizeof(double) * n_cloud, hipMemcpyHostToDevice, p->stream));
-    FRX_TRY(frx_trajectory_clearance_exact_device(p, p->d_T.p, p->d_C.p, n_obs, d_obs, d_work, d_rows, p->stream));
-    FRX_TRY(fetch_rows(p, d_rows, n_rows, piece_out));
-    frx::fold_clearance_exact(p->B, p->poff.data(), T, p->h_out20.p, cand_out, flags);
-    return FRX_OK;
-}
-
-// Tests: points > 0 forces that many cloud points per chunk of every later exact clearance call and workspace query on the handle (0: the library's own split);
-// cull_on == 0 makes every point a survivor that runs both tasks.  Rows depend on neither.
-int frx_debug_set_clear_exact(frx_problem *p, int chunk_points, int cull_on) {
-    if (!p || chunk_points < 0) return fail(FRX_ERR_INVALID_ARG, "null handle or a negative chunk");
-    p->clx_chunk = chunk_points; p->clx_cull = cull_on ? 1 : 0;
-    return FRX_OK;
-}
-
-// Tests: per piece, the points that survived the cull and the degree-21 tasks that ran in the last exact clearance call on the handle, summed over the chunks of
-// the partials that call left in its workspace (which must still be alive).  Waits for the device.
-int frx_debug_clear_exact_counts(frx_problem *p, int *survivors, int *ell_tasks) {
-    if (!p || !survivors || !ell_tasks) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (!p->clx_last_work) return fail(FRX_ERR_INVALID_ARG, "frx_debug_clear_exact_counts: no exact clearance call on this handle since its cloud buffer was last laid out");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const int nc = p->clx_last_nchunks;
-    std::vector<double> part((size_t)frx::CLEAR_EXACT_PARTIAL * p->P * (size_t)nc);
-    HIP_TRY(hipMemcpy(part.data(), p->clx_last_work, sizeof(double) * part.size(), hipMemcpyDeviceToHost));
-    for (int k = 0; k < p->P; k++) {
-        double s = 0.0, e = 0.0;
-        for (int c = 0; c < nc; c++) { const double *w = part.data() + ((size_t)k * nc + c) * frx::CLEAR_EXACT_PARTIAL; s += w[6]; e += w[7]; }
-        survivors[k] = (int)s; ell_tasks[k] = (int)e;
-    }
-    return FRX_OK;
-}
-
-int frx_map_distance_fold(int B, const int *piece_off, const double *T, const double *rows, double margin, double *cand_out, unsigned *flags) {
-    if (B < 1 || !piece_off || !T || !rows) return fail(FRX_ERR_INVALID_ARG, "frx_map_distance_fold: B must be >= 1 and piece_off, T, rows not NULL");
-    if (margin != margin) return fail(FRX_ERR_INVALID_ARG, "frx_map_distance_fold: margin is not a number");
-    if (piece_off[0] < 0) return fail(FRX_ERR_INVALID_ARG, "frx_map_distance_fold: piece_off[0] must be >= 0");
-    for (int b = 0; b < B; b++)
-        if (piece_off[b + 1] < piece_off[b]) return fail(FRX_ERR_INVALID_ARG, "frx_map_distance_fold: piece_off must not fall (candidate " + std::to_string(b) + ")");
-    frx::fold_map_distance(B, piece_off, T, rows, margin, cand_out, flags);
-    return FRX_OK;
-}
-
-// argument rules of both forms of frx_trajectory_map_distance, checked before a device is looked for and before the handle is read
-static int map_distance_args(frx_problem *p, const void *T, const void *C, int intervals, const frx_voxel_map *map, const void *field, const void *out) {
-    if (!p || !T || !C || !map || !field || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (intervals < 1 || intervals > FRX_CHECK_MAX_INTERVALS) return fail(FRX_ERR_INVALID_ARG, "intervals must lie in 1.." + std::to_string(FRX_CHECK_MAX_INTERVALS));
-    FRX_TRY(frx::voxel_map_args(map, "frx_trajectory_map_distance", false));
-    if (frx_device_count() < 1) return fail(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    return FRX_OK;
-}
-
-int frx_trajectory_map_distance_device(frx_problem *p, const double *T_dev, const double *C_dev, int intervals, const frx_voxel_map *map, const double *field_dev,
-                                       double *piece_out_dev, void *hip_stream) {
-    static_assert(FRX_MAPDIST_FIELDS == (int)frx::MAPDIST_FIELDS && FRX_MAPDIST_FIELDS <= 20, "frx.h and frx_device.hpp agree, and the rows fit the P x 20 staging");
-    FRX_TRY(map_distance_args(p, T_dev, C_dev, intervals, map, field_dev, piece_out_dev));
-    HIP_TRY((hipError_t)frx::launch_map_distance(p->P, T_dev, C_dev, intervals, map->origin, map->dim, map->res, field_dev, piece_out_dev, hip_stream));
-    return FRX_OK;
-}
-
-int frx_trajectory_map_distance(frx_problem *p, const double *T, const double *C, int intervals, const frx_voxel_map *map, const double *field, double margin,
-                                double *piece_out, double *cand_out, unsigned *flags) {
-    FRX_TRY(map_distance_args(p, T, C, intervals, map, field, cand_out));
-    if (margin != margin) return fail(FRX_ERR_INVALID_ARG, "frx_trajectory_map_distance: margin is not a number");
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t n_rows = (size_t)FRX_MAPDIST_FIELDS * p->P, n_cells = (size_t)map->dim[0] * map->dim[1] * map->dim[2];
-    FRX_TRY(grow(p->d_mapdist, n_rows + n_cells, "frx_trajectory_map_distance"));
-    double *d_rows = p->d_mapdist.p, *d_field = d_rows + n_rows;
-    FRX_TRY(stage_TC(p, T, C));
-    HIP_TRY(hipMemcpyAsync(d_field, field, sizeof(double) * n_cells, hipMemcpyHostToDevice, p->stream));
-    FRX_TRY(frx_trajectory_map_distance_device(p, p->d_T.p, p->d_C.p, intervals, map, d_field, d_rows, p->stream));
-    FRX_TRY(fetch_rows(p, d_rows, n_rows, piece_out));
-    frx::fold_map_distance(p->B, p->poff.data(), T, p->h_out20.p, margin, cand_out, flags);
-    return FRX_OK;
-}
-
-// Tests: the fold of the blocking check (kind 0), extrema (1) and clearance (2) entries on piece rows the caller made up; no handle, no device.
-int frx_debug_fold_rows(int kind, int B, const int *piece_off, const double *T, const double *rows, const double *limits, double *cand_out, unsigned *flags) {
-    if (kind < 0 || kind > 2 || B < 1 || !piece_off || !T || !rows || !limits) return fail(FRX_ERR_INVALID_ARG, "kind must be 0, 1 or 2, B >= 1 and no input NULL");
-    (kind == 0 ? frx::fold_check : kind == 1 ? frx::fold_extrema : frx::fold_clearance)(B, piece_off, T, rows, limits, cand_out, flags);
-    return FRX_OK;
-}
-
-// argument rules of both forms of frx_trajectory_sample; *n_out = B x S x FRX_SAMPLE_FIELDS
-static int sample_args(frx_problem *p, const double *T, const double *C, int n_samples, double t0, double dt, const double *times, const double *out,
-                       size_t *n_out) {
-    if (!p || !T || !C || !out) return fail(FRX_ERR_INVALID_ARG, "null argument");
-    if (n_samples < 1) return fail(FRX_ERR_INVALID_ARG, "n_samples must be >= 1");
-    if (!std::isfinite(t0) || !std::isfinite(dt) || dt < 0.0) return fail(FRX_ERR_INVALID_ARG, "t0 and dt must be finite and dt >= 0");
-    if (!times && dt == 0.0 && n_samples < 2) return fail(FRX_ERR_INVALID_ARG, "n_samples must be >= 2 when dt == 0 (samples spread over each duration)");
-    size_t n = 0;
-    if (__builtin_mul_overflow((size_t)n_samples, (size_t)p->B, &n) || __builtin_mul_overflow(n, (size_t)FRX_SAMPLE_FIELDS, &n))
-        return fail(FRX_ERR_INVALID_ARG, "n_samples x B x FRX_SAMPLE_FIELDS overflows size_t");
-    if (!frx::sample_fits(p->maxN)) return fail(FRX_ERR_CAPACITY, "frx_trajectory_sample: the prefix sums of " + std::to_string(p->maxN) + " pieces exceed the kernel's LDS");
-    *n_out = n;
-    return FRX_OK;
-}
-
-int frx_trajectory_sample_device(frx_problem *p, const double *T_dev, const double *C_dev, int n_samples, double t0, double dt, const double *times_dev,
-                                 double *out_dev, void *hip_stream) {
-    size_t n_out = 0;
-    const int rc = sample_args(p, T_dev, C_dev, n_samples, t0, dt, times_dev, out_dev, &n_out);
-    if (rc != FRX_OK) return rc;
-    if ((uintptr_t)out_dev % 16) return fail(FRX_ERR_INVALID_ARG, "out_dev must be 16-byte aligned");
-    HIP_TRY((hipError_t)frx::launch_sample(p->dp, p->maxN, T_dev, C_dev, n_samples, t0, dt, times_dev, out_dev, hip_stream));
-    return FRX_OK;
-}
-
-int frx_trajectory_sample(frx_problem *p, const double *T, const double *C, int n_samples, double t0, double dt, const double *times, double *out) {
-    size_t n_out = 0;
-    FRX_TRY(sample_args(p, T, C, n_samples, t0, dt, times, out, &n_out));
-    HIP_TRY(hipSetDevice(p->device));
-    const size_t n_times = times ? n_out / FRX_SAMPLE_FIELDS : 0, need = n_out + n_times;   // (rows first: 16-byte aligned)
-    if (need > SIZE_MAX / sizeof(double)) return fail(FRX_ERR_ALLOC, "frx_trajectory_sample: output too large");
-    FRX_TRY(grow(p->d_sample, need, "frx_trajectory_sample"));
-    double *d_out = p->d_sample.p, *d_times = times ? p->d_sample.p + n_out : nullptr;
-    FRX_TRY(stage_TC(p, T, C));
-    if (times) HIP_TRY(hipMemcpyAsync(d_times, times, sizeof(double) * n_times, hipMemcpyHostToDevice, p->stream));
-    FRX_TRY(frx_trajectory_sample_device(p, p->d_T.p, p->d_C.p, n_samples, t0, dt, d_times, d_out, p->stream));
-    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, p->stream));   // (the rows go to the caller as they are: no fold, no staging)
-    HIP_TRY(hipStreamSynchronize(p->stream));
     return FRX_OK;
 }
 

@@ -23,7 +23,7 @@
 namespace {
 
 int invalid(const char *who, const char *what) { return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": " + what); }
-int no_device() { return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)"); }
+using frx::no_device;
 int hip_failed(const char *who, hipError_t e) { return frx::set_error(FRX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
 template <class T> hipError_t to_device(T *dst, const T *src, size_t n) { return hipMemcpy(dst, src, sizeof(T) * n, hipMemcpyHostToDevice); }
 template <class T> hipError_t to_host(T *dst, const T *src, size_t n) { return hipMemcpy(dst, src, sizeof(T) * n, hipMemcpyDeviceToHost); }

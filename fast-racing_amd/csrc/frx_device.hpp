@@ -151,20 +151,7 @@ enum { CLEAR_TILE = 64,                  // sample states a workgroup holds in L
        CLEAR_PASS = 1024,                // cloud points a workgroup holds in registers at a time (256 lanes x 4)
        CLEAR_TARGET_WGS = 2048 };        // workgroups the cloud is split for when there are few pieces: 8 per CU of a 256-CU device, a constant so that
                                          // the split (and with it the workspace) depends on (P, n_obs) alone
-// points per cloud chunk and chunks per piece: force > 0 takes that many points per chunk, else enough chunks of whole passes to reach CLEAR_TARGET_WGS
-// workgroups (one chunk when P alone does).  0 when P x chunks does not fit a grid.
-inline int clear_geometry(int P, int n_obs, int force, int *chunk, int *nchunks) {
-    long long c = force;
-    if (force <= 0) {
-        const long long want = P < CLEAR_TARGET_WGS ? CLEAR_TARGET_WGS / P : 1;
-        c = ((long long)n_obs + want - 1) / want;
-        c = (c + CLEAR_PASS - 1) / CLEAR_PASS * CLEAR_PASS;
-    }
-    const long long nc = ((long long)n_obs + c - 1) / c;
-    if ((long long)P * nc > 0x7fffffffLL) return 0;
-    *chunk = (int)(c < n_obs ? c : n_obs); *nchunks = (int)nc;
-    return 1;
-}
+// (points per cloud chunk and chunks per piece: cloud_split of frx_traj_host.hpp with CLEAR_PASS and CLEAR_TARGET_WGS)
 // rows: [P][4] (frx.h FRX_CLEAR_*) of the pieces (T, C) against obs [n_obs][3]; work: [P][nchunks][4] partials, not touched when nchunks == 1;
 // every pointer is a device pointer.  Pure launches: two kernels, one when nchunks == 1.
 int launch_clear(const DevProblem &dp, const double *T, const double *C, int intervals, int n_obs, const double *obs, int chunk, int nchunks,
@@ -176,19 +163,7 @@ enum { CLEAR_EXACT_FIELDS = 6,           // doubles of a piece row
        CLEAR_EXACT_CHUNK = 1024,         // the split takes whole multiples of this many points
        CLEAR_EXACT_TARGET_WGS = 1024 };  // workgroups the cloud is split for when there are few pieces (one wave each, three per CU): a constant so that
                                          // the split (and with it the workspace) depends on (P, n_obs) alone
-// points per cloud chunk and chunks per piece, as clear_geometry; 0 when P x chunks does not fit a grid
-inline int clear_exact_geometry(int P, int n_obs, int force, int *chunk, int *nchunks) {
-    long long c = force;
-    if (force <= 0) {
-        const long long want = P < CLEAR_EXACT_TARGET_WGS ? CLEAR_EXACT_TARGET_WGS / P : 1;
-        c = ((long long)n_obs + want - 1) / want;
-        c = (c + CLEAR_EXACT_CHUNK - 1) / CLEAR_EXACT_CHUNK * CLEAR_EXACT_CHUNK;
-    }
-    const long long nc = ((long long)n_obs + c - 1) / c;
-    if ((long long)P * nc > 0x7fffffffLL) return 0;
-    *chunk = (int)(c < n_obs ? c : n_obs); *nchunks = (int)nc;
-    return 1;
-}
+// (the split likewise: cloud_split with CLEAR_EXACT_CHUNK and CLEAR_EXACT_TARGET_WGS)
 // rows: [P][6] (frx.h FRX_CLEAR_EXACT_*) of the pieces (T, C) against obs [n_obs][3] for the body diag(ell[0], ell[0], ell[2]); work: [P][nchunks][10] partials,
 // always written (they hold the counts frx_debug_clear_exact_counts reads); cull == 0: every point is a survivor and runs both tasks.  Every pointer is a
 // device pointer.  Pure launches: three kernels (bounds, certificate, fold of the chunks), two when nchunks == 1.

@@ -1,5 +1,5 @@
 // Host side of the gate passage certificate (frx_trajectory_gates, include/frx.h): gate records from corner poses and the flag words from gate
-// rows.  Plain C++: no HIP and no handle, so the blocking entry (frx_api.cpp), a caller of the _device form and a host-only program share this one implementation.
+// rows.  Plain C++: no HIP and no handle, so the blocking entry (frx_traj.cpp), a caller of the _device form and a host-only program share this one implementation.
 #pragma once
 #include <cmath>
 

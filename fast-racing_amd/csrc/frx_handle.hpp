@@ -1,5 +1,5 @@
-// The handle behind the C ABI (struct frx_problem) and the small HIP helpers its translation units share (device buffers: frx_hip_scope.hpp): frx_api.cpp (creation, evaluation and trajectory
-// entries, self-tests), frx_optimize.cpp (the plan drivers) and frx_host_cpus.cpp (CPU budget, NUMA placement).  Private to libfrx.so; host code only.
+// The handle behind the C ABI (struct frx_problem) and the small HIP helpers its translation units share (device buffers: frx_hip_scope.hpp): frx_api.cpp (creation, evaluation,
+// self-tests), frx_traj.cpp (the trajectory entries), frx_optimize.cpp (the plan drivers) and frx_host_cpus.cpp (CPU budget, NUMA placement).  Private to libfrx.so; host code only.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -29,6 +29,7 @@ inline int fail(int code, const std::string &msg) { return frx::set_error(code, 
         if (e_ != hipSuccess)                                                                           \
             return fail(FRX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                \
     } while (0)
+#define FRX_TRY(expr) do { const int rc_ = (expr); if (rc_ != FRX_OK) return rc_; } while (0)
 
 // a pair of HIP events that is destroyed on every exit path
 struct HipEventPair {
@@ -92,13 +93,8 @@ struct frx_problem {
     DevBuf<double> d_wq;                                    // [P][4]: per waypoint {|xi|^2, sum_a V_a xi_a^2}, forward map -> adjoint of the same evaluation
     // pinned staging
     PinBuf<double> h_x, h_f, h_g, h_T, h_C, h_out20;
-    DevBuf<double> d_check;                                 // [P][8] rows of frx_trajectory_check, allocated on its first call
-    DevBuf<double> d_extrema;                               // [P][10] rows of frx_trajectory_extrema, allocated on its first call
-    DevBuf<double> d_contain;                               // [P][8] rows of frx_trajectory_contain, allocated on its first call
-    DevBuf<double> d_sample;                                // frx_trajectory_sample: [B][S][20] rows, then [B][S] times; grown as needed
-    DevBuf<double> d_gates;                                 // frx_trajectory_gates: [n_gates][10] rows, the records [n_gates][9], then gate_off [B + 1] as ints; grown as needed
-    DevBuf<double> d_clear;                                 // frx_trajectory_clearance: [P][4] rows, the cloud [n_obs][3], then the partials [P][chunks][4]; grown as needed
-    DevBuf<double> d_mapdist;                               // frx_trajectory_map_distance: [P][4] rows, then the field over the map's grid; grown as needed
+    DevBuf<double> d_rows;                                  // [P][20]: the piece rows of the blocking frx_trajectory_check, _extrema and _contain, allocated by whichever runs first
+    DevBuf<double> d_sample, d_gates, d_clear, d_mapdist;   // scratch of the blocking frx_trajectory_sample, _gates, _clearance[_exact] and _map_distance, grown as needed: carve_* (frx_traj_host.hpp) lay them out
     int clear_chunk = 0;                                    // tests (frx_debug_set_clear_chunk): > 0 = cloud points per chunk, 0 = the library's own split
     int clx_chunk = 0, clx_cull = 1;                        // tests (frx_debug_set_clear_exact): cloud points per chunk of frx_trajectory_clearance_exact (0 = the library's own split), the cull on / off
     const double *clx_last_work = nullptr; int clx_last_nchunks = 0;   // the partials of the last exact clearance call on the handle (frx_debug_clear_exact_counts reads its counts)
@@ -154,6 +150,24 @@ struct frx_problem {
     int lbfgs_mode = 0;                     // 0 = device vectors (default), 1 = host vectors
     frx::PlanTimes stats;                   // frx_optimize_stats: what the last plan took
 };
+
+// What the blocking entries that take (T, C) from the host share (frx_penalty_eval, frx_traj.cpp): (T, C) -> d_T, d_C through the pinned h_T, h_C on the handle's stream
+inline int stage_TC(frx_problem *p, const double *T, const double *C) {
+    std::memcpy(p->h_T.p, T, sizeof(double) * p->P);
+    std::memcpy(p->h_C.p, C, sizeof(double) * 18 * (size_t)p->P);
+    HIP_TRY(hipMemcpyAsync(p->d_T.p, p->h_T.p, sizeof(double) * p->P, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(p->d_C.p, p->h_C.p, sizeof(double) * 18 * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+    return FRX_OK;
+}
+// n <= 20 P doubles of piece rows -> h_out20, complete on return; piece_out, when given, gets a copy
+inline int fetch_rows(frx_problem *p, const double *d_rows, size_t n, double *piece_out) {
+    HIP_TRY(hipMemcpyAsync(p->h_out20.p, d_rows, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (piece_out) std::memcpy(piece_out, p->h_out20.p, sizeof(double) * n);
+    return FRX_OK;
+}
+// a scratch buffer that grows to `need` doubles
+inline int grow(DevBuf<double> &buf, size_t need, const char *entry) { return buf.n < need ? dev_alloc(buf, need, entry) : FRX_OK; }
 
 namespace frx {
 // frx_api.cpp: one evaluation of the batch in the form the handle's state selects (hipError_t as int), and the one-launch form's sticky error word

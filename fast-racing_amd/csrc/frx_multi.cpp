@@ -102,7 +102,7 @@ int frx_multi_create(const frx_config *cfg, int n_devices, const int *devices, i
         return frx::set_error(FRX_ERR_INVALID_ARG, "frx_multi_create: null argument or B <= 0");
     *out = nullptr;
     const int ndev = frx_device_count();
-    if (ndev <= 0) return frx::set_error(FRX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (ndev <= 0) return frx::no_device();
     DeviceGuard restore_device;
     int G = n_devices > 0 ? n_devices : ndev;
     G = std::min(G, B);                                                         // "only when it exceeds one device": never more shards than candidates

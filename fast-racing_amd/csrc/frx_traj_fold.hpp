@@ -1,5 +1,5 @@
 // Piece rows -> candidate rows and flag words of frx_trajectory_check / _extrema / _clearance / _clearance_exact / _contain / _map_distance (include/frx.h documents the rows).  Plain C++: no HIP
-// and no handle, so the blocking entries (frx_api.cpp), frx_debug_fold_rows, frx_contain_fold and a host-only program share this one implementation.
+// and no handle, so the blocking entries (frx_traj.cpp), frx_debug_fold_rows, frx_contain_fold and a host-only program share this one implementation.
 //
 // One shape: the candidates b = 0..B-1 own the pieces poff[b]..poff[b+1]-1 of T[] and of rows[] (piece rows, FIELDS doubles each), folded in piece order;
 // a time is counted from the candidate's start on the prefix of durations summed left to right.  limits = {vel_max, thr_acc_min, thr_acc_max,

@@ -145,13 +145,13 @@ int frx_debug_taken_over(const frx_problem *p, int *candidates);
 int frx_debug_set_takeover_at(frx_problem *p, long rounds);
 int frx_debug_compact_from_history(int m, int n, int hs, int bound, int newest, const double *S, const double *Y, double *rinv129, double *yy, double *vd);
 
-/* Tests: frx_trajectory_clearance splits the cloud into chunks, one workgroup per (piece, chunk), by a rule of its own (fast-racing_amd/csrc/frx_device.hpp,
- * clear_geometry).  points > 0 forces that many cloud points per chunk (the last one shorter) for every later clearance call and workspace query on the
+/* Tests: frx_trajectory_clearance splits the cloud into chunks, one workgroup per (piece, chunk), by a rule of its own (fast-racing_amd/csrc/frx_traj_host.hpp,
+ * cloud_split).  points > 0 forces that many cloud points per chunk (the last one shorter) for every later clearance call and workspace query on the
  * handle, 0 returns to the library's rule.  Rows do not depend on it. */
 int frx_debug_set_clear_chunk(frx_problem *p, int points);
 
-/* Tests: frx_trajectory_clearance_exact splits the cloud into chunks, one one-wave workgroup per (piece, chunk) (fast-racing_amd/csrc/frx_device.hpp,
- * clear_exact_geometry), and leaves out the points its cull proves irrelevant.  chunk_points > 0 forces that many cloud points per chunk (the last one shorter)
+/* Tests: frx_trajectory_clearance_exact splits the cloud into chunks, one one-wave workgroup per (piece, chunk) (fast-racing_amd/csrc/frx_traj_host.hpp,
+ * cloud_split), and leaves out the points its cull proves irrelevant.  chunk_points > 0 forces that many cloud points per chunk (the last one shorter)
  * for every later exact clearance call and workspace query on the handle, 0 returns to the library's rule; cull_on == 0 makes every point a survivor that
  * runs both tasks.  Rows depend on neither.
  * frx_debug_clear_exact_counts: per piece (survivors[P], ell_tasks[P]) how many points survived the cull and how many ran the degree-21 task in the last exact

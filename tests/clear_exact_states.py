@@ -4,7 +4,7 @@
                    every minimum has a closed form; a piece in free fall; a handle whose ellipsoid is a sphere.  Each state: dict(params, T (N,), C (6N, 3),
                    obs (n, 3), expect (per piece: field -> value, or "nan"), cand (field -> value or None), set / clear (flag bits of the candidate)).
   clouds           near_cloud: points within `reach` metres of a point on the batch's paths; spread_cloud: points over the batch's bounding box.
-  chunks           the launch rule of frx_device.hpp (clear_exact_geometry) restated.
+  chunks           the launch rule (cloud_split of frx_traj_host.hpp with the constants of frx_device.hpp) restated.
 """
 import os
 import sys

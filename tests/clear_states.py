@@ -1,7 +1,7 @@
 """States of the clearance check against the obstacle cloud (frx_trajectory_clearance, frx_clear_kernel.hpp) - test infrastructure, not a test
 module.
 
-The kernel's launch rule (frx_device.hpp: clear_geometry), restated here as chunks(P, n_obs, force): the cloud is split into chunks of whole
+The kernel's launch rule (frx_traj_host.hpp: cloud_split with the constants of frx_device.hpp), restated here as chunks(P, n_obs, force): the cloud is split into chunks of whole
 passes of PASS = 1024 points so that P x chunks reaches 2048 workgroups (one chunk when P alone does); force > 0 = that many points per chunk.
 A workgroup holds TILE = 64 sample states at a time.
 

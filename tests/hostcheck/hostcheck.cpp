@@ -389,3 +389,6 @@ extern "C" void hostcheck_eval_solo_choice(int lds_solo, int solo_char, int min_
 
 // ---- what the handle-less batch entries decide on the host (batch_host_main.cpp), for tests/test_batch_host_cpu.py ----
 #include "batch_host_main.cpp"
+
+// ---- what the trajectory entries decide on the host (traj_host_main.cpp), for tests/test_traj_host_cpu.py ----
+#include "traj_host_main.cpp"
