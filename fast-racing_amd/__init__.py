@@ -77,6 +77,7 @@ ABI_SYMBOLS = [
     "frx_map_esdf", "frx_map_esdf_workspace", "frx_map_esdf_device", "frx_map_esdf_on_device", "frx_map_mark_cloud_device",
     "frx_trajectory_map_distance", "frx_trajectory_map_distance_device", "frx_map_distance_fold",
     "frx_grid_search_levels", "frx_route_plan_levels_batch", "frx_route_search_workspace", "frx_route_plan_batch_device", "frx_route_plan_batch",
+    "frx_route_plan_levels_window_batch", "frx_route_window_workspace", "frx_route_plan_window_batch_device", "frx_route_plan_window_batch",
 ]
 # diagnostics, include/frx_debug.h: not part of the drop-in boundary
 DEBUG_SYMBOLS = [
@@ -249,6 +250,10 @@ def lib():
         L.frx_route_search_workspace.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.frx_route_plan_batch_device.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 8
         L.frx_route_plan_batch.argtypes = [C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 7
+        L.frx_route_plan_levels_window_batch.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 8
+        L.frx_route_window_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_size_t)]
+        L.frx_route_plan_window_batch_device.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 9
+        L.frx_route_plan_window_batch.argtypes = [C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int] + [_vp] * 8
         for name in ABI_SYMBOLS + DEBUG_SYMBOLS:
             fn = getattr(L, name)
             if name not in ("frx_version", "frx_last_error", "frx_device_count", "frx_lbfgs_default_params",
@@ -555,6 +560,53 @@ class VoxelMap:
         """frx_route_plan_batch: the same batch searched on the device (upload, four launches, download); the same dict, bit for bit."""
         return self._route_batch(routes, lambda *a: lib().frx_route_plan_batch(int(device), *a), cap_level, cap_raw, cap_pts, cap_total)
 
+    def _route_batch_window(self, routes, call, pad, cap_window, cap_level, cap_raw, cap_pts, cap_total):
+        off, _ = pack_routes(routes)
+        win = np.zeros((max(int(off[-1]) - len(routes), 1), 8), np.int32)
+        out = self._route_batch(routes, lambda m, R, o, p, cl, cr, cp, ct, *rest: call(m, R, o, p, int(pad), int(cap_window), cl, cr, cp, ct, *rest[:6], win.ctypes.data,
+                                                                                   rest[6]), cap_level, cap_raw, cap_pts, cap_total)
+        out["leg_window"] = win[:len(out["leg_status"])]
+        return out
+
+    def route_batch_window_host(self, routes, pad: int, cap_window: int, cap_level: int = 1 << 16, cap_raw: int = 1 << 16, cap_pts: int = 1 << 12, cap_total=None):
+        """frx_route_plan_levels_window_batch on one host thread, the referee of route_batch_window: every leg searched inside the box of its two end cells widened
+        by `pad` cells (at most cap_window cells).  The dict of route_batch_host plus leg_window (n_legs x 8: lo xyz, size xyz, limit or -1 for a whole-map
+        window, 0).  leg_status 0: bit for bit the leg of route_batch_host; 6: the window holds more than cap_window cells; 7: the window certifies nothing."""
+        return self._route_batch_window(routes, lib().frx_route_plan_levels_window_batch, pad, cap_window, cap_level, cap_raw, cap_pts, cap_total)
+
+    def route_batch_window(self, routes, pad: int, cap_window: int, device: int = 0, cap_level: int = 1 << 16, cap_raw: int = 1 << 16, cap_pts: int = 1 << 12,
+                           cap_total=None, fallback: bool = False):
+        """frx_route_plan_window_batch: the same batch on the device (upload, three launches, download); the same dict, bit for bit.  fallback=True reruns
+        through route_batch, the whole-map form, exactly the routes that have a leg with status 6 or 7 and puts their rows in place, in route order: paths,
+        path, path_off, route_status, levels and max_level_cells are then those of route_batch on the same routes, and leg_status keeps 6 or 7 on the legs
+        that needed the whole map and found their path there (a leg the whole map fails as well shows the whole map's status).  `need` is the points of the
+        result and `fits` compares it with cap_total where one was given."""
+        out = self._route_batch_window(routes, lambda *a: lib().frx_route_plan_window_batch(int(device), *a), pad, cap_window, cap_level, cap_raw, cap_pts, cap_total)
+        if not fallback:
+            return out
+        first = np.concatenate([[0], np.cumsum([len(np.asarray(r).reshape(-1, 3)) - 1 for r in routes])]).astype(int)
+        again = [r for r in range(len(routes)) if np.isin(out["leg_status"][first[r]:first[r + 1]], (6, 7)).any()]
+        if not again:
+            return out
+        whole = self.route_batch([routes[r] for r in again], device=device, cap_level=cap_level, cap_raw=cap_raw, cap_pts=cap_pts)
+        paths = list(out["paths"])
+        rst, lst, lev, mx = (out[k].copy() for k in ("route_status", "leg_status", "levels", "max_level_cells"))
+        at = 0
+        for i, r in enumerate(again):
+            n = first[r + 1] - first[r]
+            paths[r] = whole["paths"][i]
+            rst[r] = whole["route_status"][i]
+            w = whole["leg_status"][at:at + n]
+            seg = lst[first[r]:first[r + 1]]
+            lst[first[r]:first[r + 1]] = np.where(np.isin(seg, (6, 7)) & (w == 0), seg, w)
+            lev[first[r]:first[r + 1]] = whole["levels"][at:at + n]
+            mx[first[r]:first[r + 1]] = whole["max_level_cells"][at:at + n]
+            at += n
+        path_off = np.zeros(len(routes) + 1, np.int32); path_off[1:] = np.cumsum([len(p) for p in paths])
+        need = int(path_off[-1])
+        return dict(path_off=path_off, path=np.concatenate(paths).reshape(-1, 3), paths=paths, route_status=rst, leg_status=lst, levels=lev, max_level_cells=mx,
+                    need=need, fits=cap_total is None or need <= int(cap_total), leg_window=out["leg_window"])
+
 
 def pack_routes(routes):
     """(pt_off int32 [n + 1], pts float64 [sum, 3]) of a list of routes, each an (n_i, 3) array of waypoints: start, gates in order, goal."""
@@ -579,6 +631,25 @@ def route_plan_batch_device(map_struct: VoxelMapStruct, n_routes: int, n_legs: i
     _check(lib().frx_route_plan_batch_device(C.byref(map_struct), int(n_routes), int(n_legs), pt_off_dev or None, pts_dev or None, int(cap_level), int(cap_raw),
                                              int(cap_pts), int(cap_total), work_dev or None, path_off_dev or None, path_dev or None, route_status_dev or None,
                                              leg_status_dev or None, leg_levels_dev or None, leg_max_level_dev or None, stream))
+
+
+def route_window_workspace(n_legs: int, cap_level: int, cap_raw: int, cap_pts: int, cap_window: int) -> int:
+    """frx_route_window_workspace: bytes of device scratch route_plan_window_batch_device needs, whatever the map's size; FrxError with code -1 / -5 for
+    arguments it refuses."""
+    n = C.c_size_t(0)
+    _check(lib().frx_route_window_workspace(int(n_legs), int(cap_level), int(cap_raw), int(cap_pts), int(cap_window), C.byref(n)))
+    return int(n.value)
+
+
+def route_plan_window_batch_device(map_struct: VoxelMapStruct, n_routes: int, n_legs: int, pt_off_dev: int, pts_dev: int, pad: int, cap_window: int, cap_level: int,
+                                   cap_raw: int, cap_pts: int, cap_total: int, work_dev: int, path_off_dev: int, path_dev: int, route_status_dev: int,
+                                   leg_status_dev: int, leg_levels_dev: int, leg_max_level_dev: int, leg_window_dev: int, stream: int = 0):
+    """frx_route_plan_window_batch_device: three launches on `stream`; the arguments of route_plan_batch_device with the pad and cap_window of the windows, a
+    workspace of route_window_workspace bytes and leg_window [n_legs][8]."""
+    _check(lib().frx_route_plan_window_batch_device(C.byref(map_struct), int(n_routes), int(n_legs), pt_off_dev or None, pts_dev or None, int(pad), int(cap_window),
+                                                    int(cap_level), int(cap_raw), int(cap_pts), int(cap_total), work_dev or None, path_off_dev or None,
+                                                    path_dev or None, route_status_dev or None, leg_status_dev or None, leg_levels_dev or None,
+                                                    leg_max_level_dev or None, leg_window_dev or None, stream))
 
 
 def grid_search_levels(cmap, dim, start, goal, cap: int = 1 << 20):

@@ -19,6 +19,7 @@
 #include "frx_hip_scope.hpp"
 #include "frx_internal.hpp"
 #include "frx_route_host.hpp"
+#include "frx_route_window_host.hpp"
 
 namespace {
 
@@ -306,27 +307,30 @@ int frx_route_plan_batch_device(const frx_voxel_map *map, int n_routes, int n_le
     return e == hipSuccess ? FRX_OK : hip_failed(who, e);
 }
 
-int frx_route_plan_batch(int device, const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
-                         int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels, int *leg_max_level, int *n_pts) {
-    const char *who = "frx_route_plan_batch";
+// The blocking form of both searches: leg_window NULL is the whole-map search; otherwise the search inside per-leg windows, whose rows come back in leg_window.
+static int route_blocking(const char *who, int device, const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int pad, long long cap_window,
+                          int cap_level, int cap_raw, int cap_pts, int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels,
+                          int *leg_max_level, int *leg_window, int *n_pts) {
     if (!pt_off || !pts || !path_off || !path || !route_status || !leg_status || !leg_levels || !leg_max_level || !n_pts) return invalid(who, "null argument");
     if (int rc = frx::route_batch_args(map, who, n_routes, cap_level, cap_raw, cap_pts, cap_total)) return rc;
+    if (leg_window)
+        if (int rc = frx::route_window_args(who, pad, cap_window)) return rc;
     long long legs = 0;
     if (int rc = frx::route_offset_args(who, n_routes, pt_off, &legs)) return rc;
-    const frx::RouteWork w = frx::route_work(map->dim, legs, cap_level, cap_raw, cap_pts);
+    const frx::RouteWork w = leg_window ? frx::route_window_work(legs, cap_level, cap_raw, cap_pts, cap_window) : frx::route_work(map->dim, legs, cap_level, cap_raw, cap_pts);
     if (w.verdict != frx::ROUTE_WORK_FITS) return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": the workspace exceeds 4e18 bytes");
     if (frx_device_count() < 1) return no_device();
     DeviceGuard restore_device;
     if (hipSetDevice(device) != hipSuccess) return invalid(who, "device ordinal out of range");
-    const size_t R = (size_t)n_routes, NL = (size_t)legs, n_wp = (size_t)pt_off[n_routes], n_cells = (size_t)w.cells;
+    const size_t R = (size_t)n_routes, NL = (size_t)legs, n_wp = (size_t)pt_off[n_routes], n_cells = (size_t)map->dim[0] * map->dim[1] * map->dim[2];
     DevBuf<signed char> d_cells;
     DevBuf<unsigned char> d_work;
-    DevBuf<int> d_off, d_poff, d_rst, d_lst, d_lev, d_max;
+    DevBuf<int> d_off, d_poff, d_rst, d_lst, d_lev, d_max, d_win;
     DevBuf<double> d_pts, d_path;
     int rc;
     if ((rc = dev_alloc(d_cells, n_cells, who)) || (rc = dev_alloc(d_work, w.bytes, who)) || (rc = dev_alloc(d_off, R + 1, who)) || (rc = dev_alloc(d_poff, R + 1, who)) ||
         (rc = dev_alloc(d_rst, R, who)) || (rc = dev_alloc(d_lst, NL, who)) || (rc = dev_alloc(d_lev, NL, who)) || (rc = dev_alloc(d_max, NL, who)) ||
-        (rc = dev_alloc(d_pts, 3 * n_wp, who)) || (rc = dev_alloc(d_path, 3 * (size_t)cap_total, who)))
+        (leg_window && (rc = dev_alloc(d_win, 8 * NL, who))) || (rc = dev_alloc(d_pts, 3 * n_wp, who)) || (rc = dev_alloc(d_path, 3 * (size_t)cap_total, who)))
         return rc;
     hipError_t e = to_device(d_cells.p, map->cells, n_cells);
     if (e == hipSuccess) e = to_device(d_off.p, pt_off, R + 1);
@@ -334,8 +338,10 @@ int frx_route_plan_batch(int device, const frx_voxel_map *map, int n_routes, con
     if (e != hipSuccess) return hip_failed(who, e);
     frx_voxel_map dmap = *map;
     dmap.cells = d_cells.p;
-    rc = frx_route_plan_batch_device(&dmap, n_routes, (int)legs, d_off.p, d_pts.p, cap_level, cap_raw, cap_pts, cap_total, d_work.p, d_poff.p, d_path.p, d_rst.p,
-                                     d_lst.p, d_lev.p, d_max.p, nullptr);
+    rc = leg_window ? frx_route_plan_window_batch_device(&dmap, n_routes, (int)legs, d_off.p, d_pts.p, pad, cap_window, cap_level, cap_raw, cap_pts, cap_total, d_work.p,
+                                                         d_poff.p, d_path.p, d_rst.p, d_lst.p, d_lev.p, d_max.p, d_win.p, nullptr)
+                    : frx_route_plan_batch_device(&dmap, n_routes, (int)legs, d_off.p, d_pts.p, cap_level, cap_raw, cap_pts, cap_total, d_work.p, d_poff.p, d_path.p,
+                                                  d_rst.p, d_lst.p, d_lev.p, d_max.p, nullptr);
     if (rc != FRX_OK) return rc;
     std::vector<int> npts(NL);
     e = hipStreamSynchronize(nullptr);
@@ -344,6 +350,7 @@ int frx_route_plan_batch(int device, const frx_voxel_map *map, int n_routes, con
     if (e == hipSuccess) e = to_host(leg_status, d_lst.p, NL);
     if (e == hipSuccess) e = to_host(leg_levels, d_lev.p, NL);
     if (e == hipSuccess) e = to_host(leg_max_level, d_max.p, NL);
+    if (e == hipSuccess && leg_window) e = to_host(leg_window, d_win.p, 8 * NL);
     if (e == hipSuccess) e = to_host(npts.data(), (const int *)(d_work.p + w.npts_off), NL);
     if (e == hipSuccess && path_off[n_routes] > 0) e = to_host(path, d_path.p, 3 * (size_t)path_off[n_routes]);
     if (e != hipSuccess) return hip_failed(who, e);
@@ -359,6 +366,49 @@ int frx_route_plan_batch(int device, const frx_voxel_map *map, int n_routes, con
     if (!frx::need_fits(need, cap_total, n_pts))
         return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": " + std::to_string(need) + " points, cap_total is " + std::to_string(cap_total));
     return FRX_OK;
+}
+
+int frx_route_plan_batch(int device, const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
+                         int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels, int *leg_max_level, int *n_pts) {
+    return route_blocking("frx_route_plan_batch", device, map, n_routes, pt_off, pts, -1, 0, cap_level, cap_raw, cap_pts, cap_total, path_off, path, route_status, leg_status,
+                          leg_levels, leg_max_level, nullptr, n_pts);
+}
+
+// ---- the same batch inside certified per-leg windows (frx_route_window_kernel.hpp): three launches, the labels of a leg sized by cap_window, not by the map ----
+int frx_route_plan_window_batch_device(const frx_voxel_map *map, int n_routes, int n_legs, const int *pt_off_dev, const double *pts_dev, int pad,
+                                       long long cap_window, int cap_level, int cap_raw, int cap_pts, int cap_total, void *work_dev, int *path_off_dev,
+                                       double *path_dev, int *route_status_dev, int *leg_status_dev, int *leg_levels_dev, int *leg_max_level_dev,
+                                       int *leg_window_dev, void *hip_stream) {
+    const char *who = "frx_route_plan_window_batch_device";
+    if (!pt_off_dev || !pts_dev || !work_dev || !path_off_dev || !path_dev || !route_status_dev || !leg_status_dev || !leg_levels_dev || !leg_max_level_dev ||
+        !leg_window_dev)
+        return invalid(who, "null argument");
+    if (int rc = frx::route_batch_args(map, who, n_routes, cap_level, cap_raw, cap_pts, cap_total)) return rc;
+    if (int rc = frx::route_window_args(who, pad, cap_window)) return rc;
+    if (n_legs < n_routes) return invalid(who, "n_legs < n_routes (every route has at least two waypoints)");
+    if ((size_t)work_dev % 8 != 0) return invalid(who, "work_dev is not 8-byte aligned (the workspace begins with doubles)");
+    if (frx::route_window_work(n_legs, cap_level, cap_raw, cap_pts, cap_window).verdict != frx::ROUTE_WORK_FITS)
+        return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": the workspace exceeds 4e18 bytes");
+    if (frx_device_count() < 1) return no_device();
+    frx::RouteWindowLaunch W;
+    frx::RouteLaunch &L = W.r;
+    for (int i = 0; i < 3; i++) { L.origin[i] = map->origin[i]; L.dim[i] = map->dim[i]; }
+    L.res = map->res; L.cells = map->cells; L.pt_off = pt_off_dev; L.pts = pts_dev;
+    L.n_routes = n_routes; L.n_legs = n_legs; L.cap_level = cap_level; L.cap_raw = cap_raw; L.cap_pts = cap_pts; L.cap_total = cap_total;
+    L.work = work_dev; L.path_off = path_off_dev; L.path = path_dev; L.route_status = route_status_dev; L.leg_status = leg_status_dev;
+    L.leg_levels = leg_levels_dev; L.leg_max_level = leg_max_level_dev;
+    W.pad = pad; W.cap_window = cap_window; W.leg_window = leg_window_dev;
+    const hipError_t e = (hipError_t)frx::launch_route_window(W, hip_stream);
+    return e == hipSuccess ? FRX_OK : hip_failed(who, e);
+}
+
+int frx_route_plan_window_batch(int device, const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int pad, long long cap_window,
+                                int cap_level, int cap_raw, int cap_pts, int cap_total, int *path_off, double *path, int *route_status, int *leg_status,
+                                int *leg_levels, int *leg_max_level, int *leg_window, int *n_pts) {
+    const char *who = "frx_route_plan_window_batch";
+    if (!leg_window) return invalid(who, "null argument");
+    return route_blocking(who, device, map, n_routes, pt_off, pts, pad, cap_window, cap_level, cap_raw, cap_pts, cap_total, path_off, path, route_status, leg_status,
+                          leg_levels, leg_max_level, leg_window, n_pts);
 }
 
 // Tests: the device's sight line (map_blocked, frx_chain_kernel.hpp) on n_pairs pairs of points, host buffers in and out; out[i] = 0 / 1 as frx_map_is_blocked.

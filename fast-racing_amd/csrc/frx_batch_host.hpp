@@ -33,6 +33,12 @@ static inline int route_batch_args(const frx_voxel_map *map, const char *who, in
     if ((long long)cap_total < 2LL * n_routes) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": cap_total < 2 n_routes (every route keeps room for its two-point placeholder)");
     return FRX_OK;
 }
+// The rules the window forms add: a pad in [0, 1 << 20] cells and a cap_window in [1, 2^31 - 4] cells (window-local indices stay ints).
+static inline int route_window_args(const char *who, int pad, long long cap_window) {
+    if (pad < 0 || pad > (1 << 20)) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": pad must lie in [0, 1 << 20]");
+    if (cap_window < 1 || cap_window > 0x7fffffffLL - 3) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": cap_window must lie in [1, 2^31 - 4]");
+    return FRX_OK;
+}
 // The rules that walk the waypoint offsets of host forms; *n_legs: the legs of all routes.
 static inline int route_offset_args(const char *who, int n_routes, const int *pt_off, long long *n_legs) {
     if (pt_off[0] < 0) return set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": pt_off[0] < 0");

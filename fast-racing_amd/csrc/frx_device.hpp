@@ -196,6 +196,15 @@ struct RouteLaunch {
 };
 // Pure launches: four kernels (label clear, search and tail per leg, the splice's offsets, the splice).  hipErrorInvalidValue for arguments route_work refuses.
 int launch_route(const RouteLaunch &r, void *stream);
+// The same batch inside per-leg windows (frx_route_window_kernel.hpp): work holds route_window_work(n_legs, caps, cap_window).bytes (frx_route_window_host.hpp),
+// leg_window [n_legs][8].  Pure launches: three kernels (search and tail per leg, which clears its own window's labels; the splice's offsets; the splice).
+// hipErrorInvalidValue for arguments route_window_work refuses and a pad outside [0, 1 << 20].
+struct RouteWindowLaunch {
+    RouteLaunch r;
+    int pad; long long cap_window;
+    int *leg_window;
+};
+int launch_route_window(const RouteWindowLaunch &r, void *stream);
 
 // ---- device-vector L-BFGS (frx_lbfgs_kernels.hpp) ----
 struct DvBuffers;

@@ -29,6 +29,7 @@
 #include "frx_esdf_host.hpp"
 #include "frx_internal.hpp"
 #include "frx_route_host.hpp"
+#include "frx_route_window_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -693,8 +694,9 @@ void plan_leg(const frx_voxel_map *m, const signed char *cmap, V3 start, V3 goal
 
 // A leg of the level search (frx_route_host.hpp) with plan_leg's tail on the cell centres: the checks of start and goal by route_end_cell, the same three simplification
 // passes and the same sampling, and the three capacities of the device form as statuses.  r.sample holds the leg's points when r.status is 0.
+// pad >= 0: the search runs inside the leg's window (frx_route_window_host.hpp) of at most cap_window cells, and *win receives the window.
 void plan_leg_levels(const frx_voxel_map *m, V3 start, V3 goal, int cap_level, int cap_raw, int cap_pts, frx::RouteScratch &w, std::vector<int> &raw,
-                     LegResult &r, frx::RouteSearchOut &o) {
+                     LegResult &r, frx::RouteSearchOut &o, int pad = -1, long long cap_window = 0, frx::RouteWindow *win = nullptr) {
     VoxelMap map{m};
     o = frx::RouteSearchOut();
     int s[3], g[3];
@@ -707,7 +709,8 @@ void plan_leg_levels(const frx_voxel_map *m, V3 start, V3 goal, int cap_level, i
         r.status = o.status = frx::ROUTE_GOAL;
         return;
     }
-    o = frx::route_search(m->cells, m->dim, s, g, cap_level, cap_raw, w, raw);
+    o = pad < 0 ? frx::route_search(m->cells, m->dim, s, g, cap_level, cap_raw, w, raw)
+                : frx::route_search_window(m->cells, m->dim, s, g, pad, cap_window, cap_level, cap_raw, w, raw, win);
     r.status = o.status;
     if (o.status != frx::ROUTE_OK) return;
     const int nx = m->dim[0], ny = m->dim[1];
@@ -834,13 +837,15 @@ int frx_grid_search_levels(const signed char *cmap, const int *dim, const int *s
     return FRX_OK;
 }
 
-int frx_route_plan_levels_batch(const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
-                                int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels, int *leg_max_level,
-                                int *n_pts) {
-    const char *who = "frx_route_plan_levels_batch";
+// The host batch of both forms: pad < 0 the whole-map search, pad >= 0 the search inside per-leg windows, whose rows go to leg_window [n_legs][8].
+static int route_levels_batch(const char *who, const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int pad, long long cap_window,
+                              int cap_level, int cap_raw, int cap_pts, int cap_total, int *path_off, double *path, int *route_status, int *leg_status,
+                              int *leg_levels, int *leg_max_level, int *leg_window, int *n_pts) {
     if (!pt_off || !pts || !path_off || !path || !route_status || !leg_status || !leg_levels || !leg_max_level || !n_pts)
         return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null argument");
     if (int rc = frx::route_batch_args(map, who, n_routes, cap_level, cap_raw, cap_pts, cap_total)) return rc;
+    if (leg_window)
+        if (int rc = frx::route_window_args(who, pad, cap_window)) return rc;
     long long n_legs = 0;
     if (int rc = frx::route_offset_args(who, n_routes, pt_off, &n_legs)) return rc;
     frx::RouteScratch w;
@@ -858,8 +863,15 @@ int frx_route_plan_levels_batch(const frx_voxel_map *map, int n_routes, const in
         for (int l = 0; l < legs; l++, leg++) {
             LegResult lr;
             frx::RouteSearchOut o;
-            plan_leg_levels(map, {p[3 * l], p[3 * l + 1], p[3 * l + 2]}, {p[3 * l + 3], p[3 * l + 4], p[3 * l + 5]}, cap_level, cap_raw, cap_pts, w, raw, lr, o);
+            frx::RouteWindow win;
+            plan_leg_levels(map, {p[3 * l], p[3 * l + 1], p[3 * l + 2]}, {p[3 * l + 3], p[3 * l + 4], p[3 * l + 5]}, cap_level, cap_raw, cap_pts, w, raw, lr, o,
+                            leg_window ? pad : -1, cap_window, &win);
             leg_status[leg] = o.status, leg_levels[leg] = o.levels, leg_max_level[leg] = o.max_level_cells;
+            if (leg_window) {
+                int *row = leg_window + 8 * size_t(leg);
+                if (o.status == frx::ROUTE_START || o.status == frx::ROUTE_GOAL) std::fill(row, row + 8, 0);   // an end that is no free cell has no window
+                else frx::route_window_row(win, row);
+            }
             if (o.status != frx::ROUTE_OK) {
                 whole = false;
                 continue;
@@ -881,6 +893,33 @@ int frx_route_plan_levels_batch(const frx_voxel_map *map, int n_routes, const in
     }
     if (!frx::need_fits(need, cap_total, n_pts))
         return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": " + std::to_string(need) + " points, cap_total is " + std::to_string(cap_total));
+    return FRX_OK;
+}
+
+int frx_route_plan_levels_batch(const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
+                                int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels, int *leg_max_level,
+                                int *n_pts) {
+    return route_levels_batch("frx_route_plan_levels_batch", map, n_routes, pt_off, pts, -1, 0, cap_level, cap_raw, cap_pts, cap_total, path_off, path, route_status,
+                              leg_status, leg_levels, leg_max_level, nullptr, n_pts);
+}
+
+int frx_route_plan_levels_window_batch(const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int pad, long long cap_window, int cap_level,
+                                       int cap_raw, int cap_pts, int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels,
+                                       int *leg_max_level, int *leg_window, int *n_pts) {
+    const char *who = "frx_route_plan_levels_window_batch";
+    if (!leg_window) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    return route_levels_batch(who, map, n_routes, pt_off, pts, pad, cap_window, cap_level, cap_raw, cap_pts, cap_total, path_off, path, route_status, leg_status,
+                              leg_levels, leg_max_level, leg_window, n_pts);
+}
+
+int frx_route_window_workspace(int n_legs, int cap_level, int cap_raw, int cap_pts, long long cap_window, size_t *bytes) {
+    const char *who = "frx_route_window_workspace";
+    if (!bytes) return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    const frx::RouteWork w = frx::route_window_work(n_legs, cap_level, cap_raw, cap_pts, cap_window);
+    if (w.verdict == frx::ROUTE_WORK_INVALID)
+        return frx::set_error(FRX_ERR_INVALID_ARG, std::string(who) + ": n_legs and every cap at least 1, cap_window at most 2^31 - 4");
+    if (w.verdict == frx::ROUTE_WORK_CAPACITY) return frx::set_error(FRX_ERR_CAPACITY, std::string(who) + ": the workspace exceeds 4e18 bytes");
+    *bytes = w.bytes;
     return FRX_OK;
 }
 

@@ -325,8 +325,9 @@ int frx_route_plan(const frx_voxel_map *map, const double *start, const double *
  *   frx_route_plan_batch          blocking, host pointers: upload, the device form, download.
  * The batch forms report in *n_pts the points all routes need and return FRX_ERR_CAPACITY only when that exceeds cap_total (every output is valid then).
  * FRX_ERR_INVALID_ARG (reported before a device is looked for): NULL arguments, n_routes < 1, a route with fewer than two waypoints, non-monotone pt_off, a cap
- * < 1, cap_total < 2 n_routes, res <= 0, a dim <= 0, more than 2^31 - 1 cells.  FRX_ERR_NO_DEVICE without a device (the device forms).  Not built: 2-bit labels, a
- * search window for very large maps, one leg split over several workgroups, JPS and eps != 1 (frx_grid_search, frx_jps_plan and frx_route_plan keep those). */
+ * < 1, cap_total < 2 n_routes, res <= 0, a dim <= 0, more than 2^31 - 1 cells.  FRX_ERR_NO_DEVICE without a device (the device forms).  Not built: 2-bit labels,
+ * one leg split over several workgroups, JPS and eps != 1 (frx_grid_search, frx_jps_plan and frx_route_plan keep those).  For maps too large for
+ * one label byte per cell and leg, frx_route_plan_window_batch below searches inside per-leg windows. */
 int frx_grid_search_levels(const signed char *cmap, const int *dim, const int *start, const int *goal, int cap, int *n_path, int *path_xyz, int *levels,
                            int *max_level_cells);
 int frx_route_plan_levels_batch(const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
@@ -338,6 +339,41 @@ int frx_route_plan_batch_device(const frx_voxel_map *map, int n_routes, int n_le
                                 int *leg_levels_dev, int *leg_max_level_dev, void *hip_stream);
 int frx_route_plan_batch(int device, const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int cap_level, int cap_raw, int cap_pts,
                          int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels, int *leg_max_level, int *n_pts);
+/* The same batch searched INSIDE CERTIFIED PER-LEG WINDOWS of the map (csrc/frx_route_window_kernel.hpp, csrc/frx_route_window_host.hpp), so that a
+ * leg's label memory is cap_window bytes whatever the map's size and its flood ends near the leg.  The window of a leg with end cells s, g is the box of s and g
+ * widened by pad cells on every side and clipped to the map.  A side on the map's face is closed (nothing lies beyond it); any other side is open and lies
+ * exactly pad cells from the box of s, g; a window without an open side is the whole map.  With M = |s - g|_1 a path that leaves through an open side holds at
+ * least M + 2 (pad + 1) steps, so a start labelled at a level <= limit = M + 2 pad by the search confined to the window certifies that no shortest path of the
+ * whole map leaves it: the leg's path, leg_levels and sample points are then bit for bit those of frx_route_plan_batch.  Otherwise the leg says so and returns no
+ * path.  Per leg, beside the statuses above: leg_status = 6 the window holds more than cap_window cells (no label is touched: leg_levels -1, leg_max_level 0);
+ * 7 the window is open and the search inside it certifies nothing (a level came out empty, or limit levels were built without labelling the start: no leg
+ * builds more than limit levels); -1 is returned only by a window that is the whole map.  The order of the verdicts: 1, 2, 6, then per level 3, found, -1 / 7
+ * for an empty level, 7 at the limit; then 4 and 5.  A leg with status 6 or 7 is a failed leg to the splice (route_status 1, the two-point placeholder).
+ * leg_max_level is the largest level built inside the window and may be smaller than the whole-map entries' value, also where the path is identical.
+ * leg_window [n_legs][8] ints: lo xyz, size xyz, limit (-1 for a whole-map window), 0; every row is written, zeros for a leg whose ends are not free cells
+ * (status 1, 2).  The entries above never return 6 or 7.
+ *   frx_route_plan_levels_window_batch   host, one thread: the referee of the device form.
+ *   frx_route_window_workspace           bytes of scratch the device form needs: per leg 24 cap_pts + 4 + 4 (2 cap_level + cap_raw) + 4 ceil(cap_window / 4),
+ *                                        the regions 8-byte aligned.  A function of its arguments alone - the map's size does not enter - answered without a device.
+ *   frx_route_plan_window_batch_device   pure launches on hip_stream of the current device (three kernels: search and tail, splice offsets, splice; each
+ *                                        workgroup of the search clears the labels of its own window, so work_dev needs no preparation and a replayed graph
+ *                                        clears again): no copy, no synchronisation, no allocation (capturable).  Pointer conventions, n_legs, the alignment of
+ *                                        work_dev and the rule for a batch with a route without a waypoint as frx_route_plan_batch_device (the leg_window rows
+ *                                        of a batch refused that way are written and carry no meaning).
+ *   frx_route_plan_window_batch          blocking, host pointers: upload, the device form, download.
+ * *n_pts and FRX_ERR_CAPACITY as above.  FRX_ERR_INVALID_ARG (reported before a device is looked for) as above, and for pad < 0, pad > 1 << 20, cap_window < 1,
+ * cap_window > 2^31 - 4 (window-local cell indices stay below 2^31).  Not built: labels in LDS for windows small enough to fit, 2-bit labels. */
+int frx_route_plan_levels_window_batch(const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int pad, long long cap_window, int cap_level,
+                                       int cap_raw, int cap_pts, int cap_total, int *path_off, double *path, int *route_status, int *leg_status, int *leg_levels,
+                                       int *leg_max_level, int *leg_window, int *n_pts);
+int frx_route_window_workspace(int n_legs, int cap_level, int cap_raw, int cap_pts, long long cap_window, size_t *bytes);
+int frx_route_plan_window_batch_device(const frx_voxel_map *map, int n_routes, int n_legs, const int *pt_off_dev, const double *pts_dev, int pad,
+                                       long long cap_window, int cap_level, int cap_raw, int cap_pts, int cap_total, void *work_dev, int *path_off_dev,
+                                       double *path_dev, int *route_status_dev, int *leg_status_dev, int *leg_levels_dev, int *leg_max_level_dev,
+                                       int *leg_window_dev, void *hip_stream);
+int frx_route_plan_window_batch(int device, const frx_voxel_map *map, int n_routes, const int *pt_off, const double *pts, int pad, long long cap_window,
+                                int cap_level, int cap_raw, int cap_pts, int cap_total, int *path_off, double *path, int *route_status, int *leg_status,
+                                int *leg_levels, int *leg_max_level, int *leg_window, int *n_pts);
 
 /* Asynchronous evaluation on host buffers (blocking and asynchronous variants): frx_objective_eval_async returns once
  * the work is enqueued on the handle's stream, frx_wait completes it and fills f and g (valid until then; one evaluation in flight per
