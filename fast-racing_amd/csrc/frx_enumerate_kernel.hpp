@@ -21,6 +21,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "frx_enumerate_rank.hpp"
+
 namespace frx {
 
 enum { HV_OK = 0, HV_UNBOUNDED = 1, HV_FLAT = 2, HV_PLANES = 3, HV_VERTICES = 4, HV_NONFINITE = 5, HV_SKIPPED = 6 };   // FRX_HV_* of include/frx.h
@@ -34,27 +36,7 @@ struct EnumArgs {
     int *nv, *status;            // [n_tasks]
 };
 
-__device__ __forceinline__ int hv_c3(int n) { return n * (n - 1) * (n - 2) / 6; }             // C(n, 3), n <= 256: below 2^24
-__device__ __forceinline__ int hv_before(int m, int i) { return i * (2 * m - i - 1) / 2; }    // pairs (p < q) of m elements with p < i
-
-// the triple of rank r in the lexicographic order of a < b < c < K
-__device__ __forceinline__ void hv_unrank(int K, int r, int &a, int &b, int &c) {
-    const int tot = hv_c3(K);
-    int lo = 0, hi = K - 3;                                            // largest a with (triples whose first index is below a) <= r
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tot - hv_c3(K - mid) <= r) lo = mid; else hi = mid - 1; }
-    a = lo;
-    const int r1 = r - (tot - hv_c3(K - a)), m = K - a - 1;
-    lo = 0; hi = m - 2;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (hv_before(m, mid) <= r1) lo = mid; else hi = mid - 1; }
-    b = a + 1 + lo;
-    c = b + 1 + (r1 - hv_before(m, lo));
-}
-__device__ __forceinline__ void hv_unrank_pair(int K, int r, int &a, int &b) {
-    int lo = 0, hi = K - 2;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (hv_before(K, mid) <= r) lo = mid; else hi = mid - 1; }
-    a = lo;
-    b = a + 1 + (r - hv_before(K, lo));
-}
+// hv_c3, hv_before, hv_unrank, hv_unrank_pair: frx_enumerate_rank.hpp (plain C++, checked rank by rank on the host)
 
 // frx_geometry.cpp:42-46
 __device__ __forceinline__ void hv_plane(const double *r, double *pl) {

@@ -35,22 +35,36 @@ def triples(K):
     return np.array(list(itertools.combinations(range(K), 3)), dtype=np.int64).reshape(-1, 3)
 
 
-def enumerate_ref(rec):
-    """dict(vertices [nv][3] in the host's order, verdict, ranks [F] of the feasible triples ascending, keys [F][3] int64, points [F][3], owner [nv] = the rank
-    whose point each vertex is)"""
-    pl = planes(rec)
-    K = len(pl)
-    T = triples(K)
+def solve(pl, T):
+    """the points of the plane triples T [n][3] and which of them the determinant keeps: (keep, x0, x1, x2)"""
     A, B, C = pl[T[:, 0]], pl[T[:, 1]], pl[T[:, 2]]
     with np.errstate(all="ignore"):
         cx = B[:, 1] * C[:, 2] - B[:, 2] * C[:, 1]; cy = B[:, 2] * C[:, 0] - B[:, 0] * C[:, 2]; cz = B[:, 0] * C[:, 1] - B[:, 1] * C[:, 0]
         det = A[:, 0] * cx + A[:, 1] * cy + A[:, 2] * cz
-        feas = ~(np.abs(det) <= 1e-10)
+        keep = ~(np.abs(det) <= 1e-10)
         ax = C[:, 1] * A[:, 2] - C[:, 2] * A[:, 1]; ay = C[:, 2] * A[:, 0] - C[:, 0] * A[:, 2]; az = C[:, 0] * A[:, 1] - C[:, 1] * A[:, 0]
         bx = A[:, 1] * B[:, 2] - A[:, 2] * B[:, 1]; by = A[:, 2] * B[:, 0] - A[:, 0] * B[:, 2]; bz = A[:, 0] * B[:, 1] - A[:, 1] * B[:, 0]
         x0 = (A[:, 3] * cx + B[:, 3] * ax + C[:, 3] * bx) / det
         x1 = (A[:, 3] * cy + B[:, 3] * ay + C[:, 3] * by) / det
         x2 = (A[:, 3] * cz + B[:, 3] * az + C[:, 3] * bz) / det
+    return keep, x0, x1, x2
+
+
+def triple_point(rec, a, b, c):
+    """the point of planes a < b < c of rec as the enumeration computes it (its feasibility is not judged)"""
+    _, x0, x1, x2 = solve(planes(rec), np.array([[a, b, c]], dtype=np.int64))
+    return np.array([x0[0], x1[0], x2[0]])
+
+
+def enumerate_ref(rec):
+    """dict(vertices [nv][3] in the host's order, verdict, ranks [F] of the feasible triples ascending, keys [F][3] int64, points [F][3], owner [nv] = the rank
+    whose point each vertex is, spans = some plane is not parallel to some pair's line, ray_pairs = the ranks of the plane pairs with a free ray,
+    slacks [K] = every plane's slack at the centroid, or None where the host does not get that far)"""
+    pl = planes(rec)
+    K = len(pl)
+    T = triples(K)
+    feas, x0, x1, x2 = solve(pl, T)
+    with np.errstate(all="ignore"):
         for k in range(K):
             feas &= pl[k, 0] * x0 + pl[k, 1] * x1 + pl[k, 2] * x2 <= pl[k, 3] + TOL
     ranks = np.nonzero(feas)[0]
@@ -78,6 +92,8 @@ def enumerate_ref(rec):
             fneg &= -dot <= 1e-12
             fpos &= dot <= 1e-12
     spans = bool((live & sp).any()); ray = bool((live & (fneg | fpos)).any())
+    ray_pairs = np.nonzero(live & (fneg | fpos))[0]                          # ranks of the plane pairs a < b, in lexicographic order, that have a free ray
+    slacks = None
     verdict = POLY_OK
     if not spans or ray:
         verdict = POLY_UNBOUNDED
@@ -89,18 +105,34 @@ def enumerate_ref(rec):
             c[0] += float(v[0]); c[1] += float(v[1]); c[2] += float(v[2])
         c = [q / float(len(verts)) for q in c]
         slack = np.finfo(np.float64).max
+        slacks = np.empty(K)
         for k in range(K):
             s = float(pl[k, 3]) - (float(pl[k, 0]) * c[0] + float(pl[k, 1]) * c[1] + float(pl[k, 2]) * c[2])
+            slacks[k] = s
             slack = s if s < slack else slack                               # std::min
         if not slack > TOL:
             verdict = POLY_FLAT
-    return dict(vertices=verts, verdict=verdict, ranks=ranks, keys=keys, points=pts, owner=owner)
+    return dict(vertices=verts, verdict=verdict, ranks=ranks, keys=keys, points=pts, owner=owner, spans=spans, ray_pairs=ray_pairs, slacks=slacks)
 
 
 def host_enum(frx, rec):
     """frx_enumerate_vertices on rec [K][6]: (nv, vertices [nv][3] or None when the host refuses the polytope, verdict)"""
-    import ctypes as C
     rec = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1)
+    if len(rec) // 6 >= 128:                                                # the large states take the host seconds: once a process, the result read-only
+        key = rec.tobytes()
+        if key not in _large:
+            _large[key] = _host_enum(frx, rec)
+            if _large[key][1] is not None:
+                _large[key][1].setflags(write=False)
+        return _large[key]
+    return _host_enum(frx, rec)
+
+
+_large = {}
+
+
+def _host_enum(frx, rec):
+    import ctypes as C
     K = len(rec) // 6
     nv = C.c_int()
     rc = frx.lib().frx_enumerate_vertices(K, rec, None, 0, C.byref(nv))

@@ -13,10 +13,24 @@ Every state is a record array [K][6] (outer normal, point), the input of frx_enu
                       on the edge between the staging areas of the kernel's first two waves; K = 12 has 220 triples, a part-filled single window, with the
                       vertex on its last rank 219.
   open_cube()         the cube without one face: unbounded.       two_cubes()   two unit cubes sharing a face as ONE 12-plane task: flat, 4 vertices.
+
+Above 64 planes and 256 vertices (the kernel's workgroup is four waves of 64 lanes, one lane per plane; its order loop takes 256 vertices a trip):
+  sphere(K, 1)        K in CEILING_K = 63 ... 256: the plane count on either side of every wave edge and at the ceiling of 256.
+  sphere(256, s, 0.0) every plane tangent to ONE sphere: none is redundant, 2 K - 4 = 508 vertices, one feasible triple each.
+  prism(d)            d side planes tangent to a cylinder and two caps, turned and shifted like the pyramid: 2 d vertices from K = d + 2 planes; for even d the
+                      opposite sides are antiparallel, so triples and pairs of them are skipped for their determinant and their cross product.
+  pyramid(254 | 255)  255 and 256 vertices from 255 and 256 planes; C(255, 3) = 2 731 135 feasible triples of one key over 10 669 windows.
+  flat_late()         64 redundant planes far outside, then two_cubes(): flat, and only planes of index >= 64 have no slack at the centroid.
+  open_late()         64 redundant planes far outside with n_z > 0, then open_cube() (open towards -z): unbounded, and the first plane pair with a free ray comes
+                      after every pair of the far planes.
+  open_sides()        the 70 sides of prism(70) without the caps: the normals do not span, unbounded, no vertex.
 """
 import numpy as np
 
 SEED_13, SEED_12, SEED_62 = 5, 0, 9
+CEILING_K = (63, 64, 65, 128, 129, 192, 193, 255, 256)
+CEILING_NV = (68, 76, 76, 106, 106, 136, 122, 140, 142)                      # vertices of sphere(K, 1), K in CEILING_K
+FAR_RADIUS, FAR_PLANES, FAR_SEED = 30.0, 64, 7
 ROT_AXIS, ROT_ANGLE, SHIFT = np.array([0.3, -0.5, 0.8]), 0.7, np.array([1.234567, -2.345678, 0.876543])
 
 
@@ -56,6 +70,37 @@ def pyramid(d, height=1.5, slope=0.8):
     p = np.concatenate([np.tile([0.0, 0.0, height], (d, 1)), [[0.0, 0.0, 0.0]]])
     R = rotation(ROT_AXIS, ROT_ANGLE)
     return records(n @ R.T, p @ R.T + SHIFT)
+
+
+def prism(d, half=0.5):
+    th = 2 * np.pi * (np.arange(d) + 0.25) / d
+    side = np.stack([np.cos(th), np.sin(th), np.zeros(d)], axis=1)          # tangent to the unit cylinder around z
+    n = np.concatenate([side, [[0.0, 0.0, 1.0], [0.0, 0.0, -1.0]]])         # the caps z = +-half, last
+    p = np.concatenate([side, [[0.0, 0.0, half], [0.0, 0.0, -half]]])
+    R = rotation(ROT_AXIS, ROT_ANGLE)
+    return records(n @ R.T, p @ R.T + SHIFT)
+
+
+def open_sides():
+    return prism(70)[:70]
+
+
+def far_planes(upward=False):
+    """FAR_PLANES planes tangent to the sphere of radius FAR_RADIUS around the origin: redundant beside the cubes; upward: every normal has n_z > 0 and a
+    horizontal part"""
+    rng = np.random.default_rng(FAR_SEED)
+    n = rng.normal(0, 1, (FAR_PLANES, 3)); n /= np.linalg.norm(n, axis=1, keepdims=True)
+    if upward:
+        n[:, 2] = np.abs(n[:, 2])
+    return records(n, FAR_RADIUS * n)
+
+
+def flat_late():
+    return np.concatenate([far_planes(), two_cubes()])
+
+
+def open_late():
+    return np.concatenate([far_planes(upward=True), open_cube()])
 
 
 def sphere(K, seed, spread=0.35):

@@ -1,6 +1,8 @@
 """frx_enumerate_vertices_batch without a device: the numpy restatement (tests/enumerate_reference.py) equals the host's frx_enumerate_vertices bit for bit on
 every state of tests/enumerate_states.py, the states have the edge properties their docstring claims (asserted from the restatement's ranks and keys), and the
-three new entries report their argument errors before a device is looked for."""
+three new entries report their argument errors before a device is looked for.  The states above 64 planes and 256 vertices have the counts and properties
+their docstring claims; the restatement is run on those of up to 131 planes and on two of 256, the host alone judges the others.  The unranking of the kernel
+(frx_enumerate_rank.hpp) is run rank by rank against the nested loops as a sanitized program of its own."""
 import ctypes as C
 import os
 import sys
@@ -96,6 +98,121 @@ def test_window_states_put_a_vertex_on_the_named_rank():
         assert tuple(e["keys"][list(e["ranks"]).index(r)]) == key, name    # the same vertex, now found by the triple of that rank
         assert er.rank_of(len(rec), *es.unrank(len(rec), r)) == r
     assert all(er.rank_of(9, *t) == i for i, t in enumerate(er.triples(9)))
+
+
+# ---- above 64 planes and 256 vertices ----
+def ceiling_states_small():
+    """the new states the restatement is run on: K <= 131"""
+    named = [(f"sphere{K}", es.sphere(K, 1)) for K in es.CEILING_K if K <= 131]
+    named += [("prism128", es.prism(128)), ("prism129", es.prism(129)), ("flat_late", es.flat_late()), ("open_late", es.open_late()), ("open_sides", es.open_sides())]
+    return named
+
+
+_ref = {}
+
+
+def ref_of(name, rec):
+    if name not in _ref:
+        _ref[name] = er.enumerate_ref(rec)
+    return _ref[name]
+
+
+def test_restatement_equals_the_host_on_the_ceiling_states(frx):
+    named = ceiling_states_small()
+    assert [len(rec) for _, rec in named] == [63, 64, 65, 128, 129, 130, 131, 76, 69, 70]
+    for name, rec in named + [("sphere256_tangent", es.sphere(256, 1, 0.0)), ("prism254", es.prism(254))]:      # (two K = 256 states: seconds and most of a gigabyte each)
+        e = ref_of(name, rec) if len(rec) <= 131 else er.enumerate_ref(rec)
+        nv, verts, verdict = er.host_enum(frx, rec)
+        assert nv == len(e["vertices"]) and verdict == e["verdict"], (name, nv, len(e["vertices"]), verdict, e["verdict"])
+        if verts is not None:
+            assert np.array_equal(verts, e["vertices"]), name
+        else:
+            assert name in ("flat_late", "open_late", "open_sides")
+        if name == "sphere256_tangent":
+            assert nv == 508 and len(e["ranks"]) == 508 and len(set(map(tuple, e["keys"]))) == 508        # one feasible triple per vertex
+
+
+def test_plane_count_states(frx):
+    assert es.CEILING_K == (63, 64, 65, 128, 129, 192, 193, 255, 256)
+    got = [er.host_enum(frx, es.sphere(K, 1)) for K in es.CEILING_K]
+    assert [g[2] for g in got] == [er.POLY_OK] * 9 and [g[0] for g in got] == [68, 76, 76, 106, 106, 136, 122, 140, 142] == list(es.CEILING_NV)
+    for seed in (1, 2, 3):
+        rec = es.sphere(256, seed, spread=0.0)
+        nv, verts, verdict = er.host_enum(frx, rec)
+        assert len(rec) == 256 and verdict == er.POLY_OK and nv == 508 == 2 * 256 - 4
+        assert len(set(map(tuple, np.rint(verts / 1e-7).astype(np.int64)))) == 508
+
+
+def test_prism_states(frx):
+    for d, K, nv_want in ((128, 130, 256), (129, 131, 258), (254, 256, 508)):
+        rec = es.prism(d)
+        nv, verts, verdict = er.host_enum(frx, rec)
+        assert len(rec) == K and verdict == er.POLY_OK and nv == nv_want == 2 * d
+    # even d: opposite sides are antiparallel - triples of them fall to the determinant, pairs of them to the cross product
+    pl = er.planes(es.prism(128))
+    keep, _, _, _ = er.solve(pl, np.array([[0, 64, 128], [0, 64, 129], [1, 65, 3]]))
+    assert not keep.any()
+    u = np.cross(pl[:64, :3], pl[64:128, :3])
+    assert (np.sqrt((u * u).sum(axis=1)) <= 1e-10).all()
+    e = ref_of("prism128", es.prism(128))
+    assert len(e["ranks"]) == 256 and e["verdict"] == er.POLY_OK                               # one feasible triple per vertex: (side i, side i + 1, cap)
+
+
+@pytest.mark.parametrize("d", [254, 255])
+def test_ceiling_pyramids(frx, d):
+    rec = es.pyramid(d)
+    nv, verts, verdict = er.host_enum(frx, rec)
+    assert len(rec) == d + 1 and verdict == er.POLY_OK and nv == d + 1
+    assert 255 * 254 * 253 // 6 == 2731135 and -(-2731135 // 256) == 10669                    # C(255, 3) triples of side planes, in that many windows of 256 ranks
+    first = er.triple_point(rec, 0, 1, 2)                                   # the apex as the first triple in rank order finds it
+    keys = np.rint(verts / 1e-7).astype(np.int64)
+    at = np.nonzero((keys == np.rint(first / 1e-7).astype(np.int64)).all(axis=1))[0]
+    assert len(at) == 1 and np.array_equal(verts[at[0]], first)
+    other = er.triple_point(rec, 3, d // 2, d - 1)
+    assert np.array_equal(np.rint(other / 1e-7), np.rint(first / 1e-7)) and not np.array_equal(other, first)      # a twin of the same key with other last bits
+
+
+def test_verdicts_decided_beyond_the_first_wave(frx):
+    flat = ref_of("flat_late", es.flat_late())
+    assert len(es.flat_late()) == 76 and flat["verdict"] == er.POLY_FLAT and len(flat["vertices"]) == 4
+    assert er.host_enum(frx, es.flat_late())[::2] == (4, er.POLY_FLAT)
+    tight = np.nonzero(flat["slacks"] <= 1e-9)[0]
+    assert len(tight) > 0 and tight.min() >= 64 and flat["slacks"][:64].min() > 1.0          # no plane of the first wave is without slack
+    open_ = ref_of("open_late", es.open_late())
+    rec = es.open_late()
+    assert len(rec) == 69 and (rec[:64, 2] > 0).all() and (np.hypot(rec[:64, 0], rec[:64, 1]) > 0).all()
+    assert open_["verdict"] == er.POLY_UNBOUNDED and open_["spans"] and er.host_enum(frx, rec)[2] == er.POLY_UNBOUNDED
+    assert len(open_["ray_pairs"]) > 0 and open_["ray_pairs"].min() >= 256                   # the first trip of the pair loop finds no free ray
+    sides = ref_of("open_sides", es.open_sides())
+    assert len(es.open_sides()) == 70 and sides["verdict"] == er.POLY_UNBOUNDED and not sides["spans"] and len(sides["vertices"]) == 0
+    assert er.host_enum(frx, es.open_sides())[::2] == (0, er.POLY_UNBOUNDED)
+
+
+def test_unranking_against_the_nested_loops(tmp_path):
+    """fast-racing_amd/csrc/frx_enumerate_rank.hpp (what k_enumerate unranks with) as a program of its own under the address and undefined-behaviour sanitizers:
+    tests/hostcheck/enumerate_rank_main.cpp, every rank of every K in 3 ... 96 and around 128, 192 and 256"""
+    import math
+    import re
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.fail("no g++: the host check cannot be built")
+    exe = str(tmp_path / "enumerate_rank_san")
+    src = os.path.join(root, "tests", "hostcheck", "enumerate_rank_main.cpp")
+    b = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, src],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert b.returncode == 0, b.stdout[-3000:]
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0 and not r.stderr.strip(), (r.stdout[-1000:], r.stderr[-3000:])
+    m = re.search(r"(\d+) triples, (\d+) pairs, (\d+) disagreements", r.stdout)
+    assert m, r.stdout
+    Ks = list(range(3, 97)) + [127, 128, 129, 191, 192, 193, 255, 256]
+    assert sum(math.comb(K, 3) for K in Ks) == 13467781 and sum(math.comb(K, 2) for K in Ks) == 291858
+    assert (int(m.group(1)), int(m.group(2)), int(m.group(3))) == (13467781, 291858, 0)
+    big = re.search(r"largest intermediate (\d+)", r.stdout)
+    assert big and int(big.group(1)) == 256 * 255 * 254 < 2 ** 31             # n (n - 1) (n - 2) at n = 256, before the division
 
 
 # ---- arguments ----
